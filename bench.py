@@ -2,6 +2,12 @@
 """Benchmark of the MI355X encoder hot path (BASELINE.json metric: encoder audio-frames/s on 30 s clips).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {q4k64,f16x1,f16x64,q80x64,q80bf16x64}]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if asked (--dump-outputs) and prints the result
+line: value, ms_per_step, the workload and the set-up times. --full adds every further leg to that line: the roofline
+objects and per-kernel breakdown (HIP events, passes of their own), MFMA util from the committed profile set, the
+PCIe-inclusive and host-API rates, the one-process multi-GPU C ABI leg and the reference CPU baseline.
 
 A "step" = one pass of the hot path (PCM -> log-mel -> conv -> 32 blocks -> pool+LN) over one batch of
 synthetic 30 s / 16 kHz clips per GPU, PCM already resident in HBM when the timed region starts.
@@ -385,6 +391,25 @@ def c_group_child(args) -> None:
     print(json.dumps(res), flush=True)
 
 
+DUMP_MAX_BYTES = 64_000_000 - 4096   # the files stay under 64 MB (10^6 bytes each), .npy header included
+DUMP_SEED = 0x51A2
+
+
+def dump_outputs(dirname: str, emb: np.ndarray, rank: int, ws: int) -> None:
+    """--dump-outputs: what the timed path handed back in its last step, embd_enc [clips, frames, D] of this rank, as
+    DIR/embd_enc.npy (rank r > 0 of a multi-GPU run: embd_enc_rank<r>.npy), float32. An array over 64 MB is sampled:
+    whole (clip, frame) rows drawn without replacement by numpy's default_rng(DUMP_SEED), in ascending order, as many
+    as fit — the same rows in every run of the same arguments, so two builds compare row for row."""
+    emb = np.ascontiguousarray(emb, dtype=np.float32)
+    rows = emb.reshape(-1, emb.shape[-1])
+    keep = DUMP_MAX_BYTES // (rows.shape[1] * 4)
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=keep, replace=False))
+        emb = rows[idx]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "embd_enc.npy" if rank == 0 else f"embd_enc_rank{rank}.npy"), emb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -392,6 +417,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="q4k64", choices=sorted(CONFIGS))
     ap.add_argument("--clips", type=int, default=0, help="override clips per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: roofline objects, per-kernel breakdown, MFMA util, PCIe-inclusive and "
+                         "host-API rates, the one-process multi-GPU C ABI leg and the reference CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embd_enc to DIR/embd_enc.npy (float32; a fixed seeded sample of its "
+                         "rows when the whole array exceeds 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-legs", action="store_true",
                     help="skip the PCIe-inclusive and host-API legs (profiles/collect.sh: every launch is then the workload's own batch)")
@@ -433,7 +464,16 @@ def main():
     if args.clips:
         clips_per_gpu = args.clips
     threads = min(16, os.cpu_count() or 8)
-    os.makedirs(args.workdir, exist_ok=True)
+    try:
+        os.makedirs(args.workdir, exist_ok=True)
+        usable = os.access(args.workdir, os.W_OK | os.X_OK)
+    except OSError:
+        usable = False
+    if not usable:   # e.g. the default directory left behind by another user: generate the model files afresh
+        import atexit
+        import shutil
+        args.workdir = tempfile.mkdtemp(prefix="q2a_bench_")
+        atexit.register(shutil.rmtree, args.workdir, ignore_errors=True)
 
     # ---- model: rank 0 generates + quantizes + packs; one RCCL broadcast of the packed blob over xGMI
     t0 = time.time()
@@ -477,21 +517,23 @@ def main():
     lib.q2a_profile_enable_mask.argtypes = [C.c_void_p, C.c_uint]
     prof_ms = (C.c_double * 11)()
     prof_n = (C.c_int64 * 11)()
-    # the dominant matrix-core class (QKV, attention, O, fc1, fc2 = Q2A_PROF_* 4, 5, 7, 8, 9) from one profiled step
-    # before the timed region; inside the timed region HIP events bracket only that class's launches (on the stream
+    # --full: the dominant matrix-core class (QKV, attention, O, fc1, fc2 = Q2A_PROF_* 4, 5, 7, 8, 9) from one profiled
+    # step before the timed region; inside the timed region HIP events bracket only that class's launches (on the stream
     # the kernels run on). An event pair costs ~9 us of GPU time per launch (profiles/r06e_vrows_persistent_qkv_ab.json:
     # 128 pairs = 1.1 ms per step at one clip), under 0.2 % of a step from 8 clips up; below that the same events run
     # over an identical pass right after the timed region instead, so `value` carries none. The per-kernel breakdown of
-    # every class comes from a separate fully-profiled pass.
-    lib.q2a_profile_enable_mask(C.c_void_p(eng.h), sum(1 << i for i in ROOF_CLASSES))
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
-    step()
-    torch.cuda.synchronize()
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
-    dominant = max(ROOF_CLASSES, key=lambda i: prof_ms[i])
-    events_in_timed = clips_per_gpu >= 8
-    lib.q2a_profile_enable_mask(C.c_void_p(eng.h), (1 << dominant) if events_in_timed else 0)
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
+    # every class comes from a separate fully-profiled pass. A plain run records no events at all.
+    dominant, events_in_timed = None, False
+    if args.full:
+        lib.q2a_profile_enable_mask(C.c_void_p(eng.h), sum(1 << i for i in ROOF_CLASSES))
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
+        step()
+        torch.cuda.synchronize()
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
+        dominant = max(ROOF_CLASSES, key=lambda i: prof_ms[i])
+        events_in_timed = clips_per_gpu >= 8
+        lib.q2a_profile_enable_mask(C.c_void_p(eng.h), (1 << dominant) if events_in_timed else 0)
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
 
     if dist is not None:
         dist.barrier()
@@ -503,26 +545,63 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - ts
-    if not events_in_timed:   # the dominant class's events over an identical pass (small batches)
-        lib.q2a_profile_enable_mask(C.c_void_p(eng.h), 1 << dominant)
-        for _ in range(args.steps):
+    if args.dump_outputs:   # the last timed step's embd_enc, before any later pass writes `out` again
+        dump_outputs(args.dump_outputs, out.cpu().numpy(), rank, ws)
+    if args.full:
+        if not events_in_timed:   # the dominant class's events over an identical pass (small batches)
+            lib.q2a_profile_enable_mask(C.c_void_p(eng.h), 1 << dominant)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 0)
+        timed_ms, timed_n = list(prof_ms), list(prof_n)
+        # breakdown pass (not timed): every kernel class bracketed by events
+        brk_steps = max(1, min(args.steps, 3))
+        lib.q2a_profile_enable(C.c_void_p(eng.h), 1)
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
+        for _ in range(brk_steps):
             step()
         torch.cuda.synchronize()
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 0)
-    timed_ms, timed_n = list(prof_ms), list(prof_n)
-    # breakdown pass (not timed): every kernel class bracketed by events
-    brk_steps = max(1, min(args.steps, 3))
-    lib.q2a_profile_enable(C.c_void_p(eng.h), 1)
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 1)
-    for _ in range(brk_steps):
-        step()
-    torch.cuda.synchronize()
-    lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 0)
-    lib.q2a_profile_enable(C.c_void_p(eng.h), 0)
-    if not os.environ.get("Q2A_DIAG_BUILD"):   # diagnostic A/B libraries (diag/) compute garbage on purpose
-        assert torch.isfinite(out).all().item(), "non-finite encoder output"
+        lib.q2a_profile_read(C.c_void_p(eng.h), prof_ms, prof_n, 11, 0)
+        lib.q2a_profile_enable(C.c_void_p(eng.h), 0)
+        if not os.environ.get("Q2A_DIAG_BUILD"):   # diagnostic A/B libraries (diag/) compute garbage on purpose
+            assert torch.isfinite(out).all().item(), "non-finite encoder output"
 
     elapsed = qd.max_over_ranks(dist, elapsed, coll_dev)
+    total_clips = clips_per_gpu * ws * args.steps
+    value = total_clips * T_MEL / elapsed
+    res = {
+        "metric": "encoder audio-frames/sec (30 s clips) at 1/2/4/8 MI355X; MFMA util %",
+        "value": round(value, 1),
+        "unit": "audio-frames/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16 MFMA (fp32 acc), q8_0 weights dequantized to bf16, bf16 activations" if "bf16" in args.config else
+                 {"q4_k": "q4_k x q8_k integer dots on fp16 MFMA (fp32 acc)", "f16": "fp16 MFMA (fp32 acc)",
+                  "q8_0": "q8_0 x q8_0 integer dots on fp16 MFMA (fp32 acc)"}[wt],
+        "data": "synthetic (deterministic 30 s / 16 kHz clips; random-init weights at Qwen2-Audio encoder shapes)",
+        "config": {"workload": workload, "model": "qwen2-audio-encoder L32 D1280 H20 F5120 (synthetic weights)",
+                   "weights": wt, "clips_per_gpu": clips_per_gpu, "global_batch": clips_per_gpu * ws,
+                   "seq_len": T_MEL, "parallelism": f"dp{ws}"},
+        "clips_per_s": round(total_clips / elapsed, 3),
+        "tflops_total": round(FLOP_PER_CLIP * total_clips / elapsed / 1e12, 1),
+        "full": args.full,
+        "setup_s": {"total": round(t_setup, 1), "weight_h2d_plus_rccl_broadcast": round(t_bcast, 4), "weight_blob_bytes": nbytes, "weight_device_bytes": int(eng.info.weight_bytes),
+                    "weight_expand_on_gpu": round(t_expand, 4),
+                    "collective_backend": dist.get_backend() if dist is not None else None},
+    }
+    if not args.full:   # a plain run: the headline figure alone (every further leg is behind --full)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        eng.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # PCIe-inclusive rate (outside `value`): a serving loop over consecutive batches from pinned host memory, double
     # buffered — batch i+1's PCM goes host -> HBM and batch i-1's embd_enc HBM -> host on a copy stream while batch i
@@ -565,8 +644,6 @@ def main():
         eng.encode_host(pcm_np, out=out_np)
         host_rate = qd.max_over_ranks(dist, time.perf_counter() - th, coll_dev)
         host_rate = clips_per_gpu * ws * T_MEL / host_rate
-    total_clips = clips_per_gpu * ws * args.steps
-    value = total_clips * T_MEL / elapsed
 
     if rank != 0:
         eng.close()
@@ -617,26 +694,7 @@ def main():
     if ws == 1 and not args.no_c_group and not args.no_host_legs:
         c_group = c_group_leg(args, model_path, clips_per_gpu)
 
-    res = {
-        "metric": "encoder audio-frames/sec (30 s clips) at 1/2/4/8 MI355X; MFMA util %",
-        "value": round(value, 1),
-        "unit": "audio-frames/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16 MFMA (fp32 acc), q8_0 weights dequantized to bf16, bf16 activations" if "bf16" in args.config else
-                 {"q4_k": "q4_k x q8_k integer dots on fp16 MFMA (fp32 acc)", "f16": "fp16 MFMA (fp32 acc)",
-                  "q8_0": "q8_0 x q8_0 integer dots on fp16 MFMA (fp32 acc)"}[wt],
-        "data": "synthetic (deterministic 30 s / 16 kHz clips; random-init weights at Qwen2-Audio encoder shapes)",
-        "config": {"workload": workload, "model": "qwen2-audio-encoder L32 D1280 H20 F5120 (synthetic weights)",
-                   "weights": wt, "clips_per_gpu": clips_per_gpu, "global_batch": clips_per_gpu * ws,
-                   "seq_len": T_MEL, "parallelism": f"dp{ws}"},
-        "clips_per_s": round(total_clips / elapsed, 3),
-        "tflops_total": round(FLOP_PER_CLIP * total_clips / elapsed / 1e12, 1),
+    res.update({
         "roofline": roofline,
         "roofline_gemm_fc1": roofline_fc1,
         "mfma_util": mfma_util_of(args.config, clips_per_gpu),
@@ -647,10 +705,7 @@ def main():
         "host_api_frames_per_s": round(host_rate, 1) if host_rate else None,
         "per_kernel": per_kernel,
         "per_kernel_source": f"separate pass of {brk_steps} step(s), every kernel class bracketed by HIP events",
-        "setup_s": {"total": round(t_setup, 1), "weight_h2d_plus_rccl_broadcast": round(t_bcast, 4), "weight_blob_bytes": nbytes, "weight_device_bytes": int(eng.info.weight_bytes),
-                    "weight_expand_on_gpu": round(t_expand, 4),
-                    "collective_backend": dist.get_backend() if dist is not None else None},
-    }
+    })
     print(json.dumps(res), flush=True)
     eng.close()
     if dist is not None:

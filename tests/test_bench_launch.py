@@ -44,7 +44,7 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     """`python bench.py --gpus 2` (2 ranks, every rank on device 0, gloo) -> one JSON line, n_gpus 2, dp2, weak
     scaling over the 2 x 2 clips, setup timing of the blob broadcast present."""
     r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--clips", "2",
-                        "--config", "f16x1", "--no-cpu-baseline", "--workdir", str(tmp_path)],
+                        "--config", "f16x1", "--full", "--no-cpu-baseline", "--workdir", str(tmp_path)],
                        capture_output=True, text=True, timeout=600, env=_env(Q2A_BENCH_REHEARSE="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     # (gloo prints its rendezvous notes to stdout; the bench's result is the one JSON line)
@@ -55,6 +55,9 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     assert res["config"]["global_batch"] == 4 and res["scaling"] == "weak"
     assert res["value"] > 0 and res["steps"] == 2
     assert res["setup_s"]["weight_h2d_plus_rccl_broadcast"] > 0
+    # --full: the further legs are in the line (the host legs run on every rank, the roofline objects on rank 0)
+    assert res["full"] is True and res["roofline"]["dominant"] and res["per_kernel"]["attention"]["ms_per_step"] > 0
+    assert res["pcie_inclusive_frames_per_s"] > 0 and res["host_api_frames_per_s"] > 0
 
 
 @pytest.mark.gpu
@@ -71,7 +74,7 @@ def test_bench_rccl_world_size_one(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(port), BENCH, "--gpus", "1", "--steps", "2",
            "--warmup", "1", "--clips", "2", "--config", "f16x1", "--no-cpu-baseline", "--no-host-legs",
-           "--workdir", str(tmp_path)]
+           "--workdir", str(tmp_path), "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=_env(Q2A_BENCH_PG="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -80,6 +83,35 @@ def test_bench_rccl_world_size_one(tmp_path):
     assert res["setup_s"]["collective_backend"] == "nccl"
     assert res["n_gpus"] == 1 and res["config"]["parallelism"] == "dp1" and res["value"] > 0
     assert res["setup_s"]["weight_h2d_plus_rccl_broadcast"] > 0
+    # a plain run: the headline figure alone, and the last timed step's embd_enc of the 2 clips where asked for
+    assert res["full"] is False and res["ms_per_step"] > 0 and res["steps"] == 2
+    assert not {"roofline", "per_kernel", "cpu_baseline", "c_group", "mfma_util"} & set(res)
+    import numpy as np
+    emb = np.load(tmp_path / "dump" / "embd_enc.npy")
+    assert emb.dtype == np.float32 and emb.shape == (2, 750, 1280)
+    assert np.isfinite(emb).all() and np.abs(emb).max() > 0
+
+
+def test_dump_outputs_whole_or_seeded_sample(tmp_path):
+    """CPU-only: --dump-outputs writes a small output whole and a large one as the same seeded sample of whole rows in
+    every run, float32, under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    small = np.arange(2 * 5 * 8, dtype=np.float64).reshape(2, 5, 8)
+    bench.dump_outputs(str(tmp_path / "s"), small, 0, 1)
+    got = np.load(tmp_path / "s" / "embd_enc.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.astype(np.float32))
+    rows = 2 * bench.DUMP_MAX_BYTES // (1280 * 4)
+    big = np.arange(rows, dtype=np.float32)[:, None] * np.ones((1, 1280), dtype=np.float32)
+    big = big.reshape(2, rows // 2, 1280)
+    bench.dump_outputs(str(tmp_path / "a"), big, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), big + 0.5, 1, 2)
+    a, b = np.load(tmp_path / "a" / "embd_enc.npy"), np.load(tmp_path / "b" / "embd_enc_rank1.npy")
+    assert os.path.getsize(tmp_path / "a" / "embd_enc.npy") <= 64_000_000
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_BYTES // (1280 * 4), 1280)
+    assert (np.diff(a[:, 0]) > 0).all() and (a == a[:, :1]).all()      # whole rows, ascending, no repeats
+    assert np.array_equal(b, a + 0.5)                                  # the same rows whatever the values
 
 
 def test_bench_constants_and_profile_selection():

@@ -66,7 +66,7 @@ def test_ggml_backend_tiny_f32(make_model, make_clip, golden_f32, tmp_path):
     """The reference's own whisper_full on the Q2A backend with an F32 file (weights on the exact-f32 GEMM)."""
     from test_gpu_ggml_backend import HARNESS, run
     if not os.path.exists(HARNESS):
-        pytest.fail("oracle/_ref/ggml_harness missing")
+        pytest.fail("oracle/_ref/ggml_q2a_harness missing")
     _, g = golden_f32
     emb, info = run(HARNESS, make_model("tiny", "f32"), make_clip(0), tmp_path)
     assert info["mul_mat_f32"] == 6 * 2 and info["attn_fused"] == 2, info

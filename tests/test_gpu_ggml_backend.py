@@ -1,6 +1,6 @@
 """The reference's own whisper_full() on the Q2A ggml backend (lib/libggml-q2a.so, include/ggml-q2a.h).
 
-oracle/_ref/ggml_harness is src/qwen2-whisper.cpp + ggml compiled unmodified from the reference sources, with the
+oracle/_ref/ggml_q2a_harness is src/qwen2-whisper.cpp + ggml compiled unmodified from the reference sources, with the
 GPU-backend branch of whisper_backend_init_gpu / whisper_default_buffer_type (qwen2-whisper.cpp:1217-1337) pointed
 at our backend (oracle/ggml_harness.cpp). The reference's loader puts the weights in our buffers, its graph builders
 and ggml_backend_sched hand the conv and encoder graphs to our graph_compute, and embd_enc is read back from our
@@ -24,13 +24,13 @@ pytestmark = pytest.mark.gpu
 # which GELU's fp16 table turned into flips downstream; with every 64-deep K-step's partial summed in f64
 # (Q2A_BLK_EXACT) the path sits at 0.90 / 0.92 of the tiny / full-size bars.
 
-HARNESS = os.path.join(ROOT, "oracle", "_ref", "ggml_harness")
+HARNESS = os.path.join(ROOT, "oracle", "_ref", "ggml_q2a_harness")
 
 
 @pytest.fixture(scope="module")
 def harness():
     if not os.path.exists(HARNESS):
-        pytest.fail("oracle/_ref/ggml_harness missing: build it where /root/reference exists (make -C oracle)")
+        pytest.fail("oracle/_ref/ggml_q2a_harness missing: build it where the reference sources are (make -C oracle)")
     return HARNESS
 
 
