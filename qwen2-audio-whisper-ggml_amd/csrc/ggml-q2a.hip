@@ -753,9 +753,17 @@ void buf_memset_tensor(ggml_backend_buffer_t b, ggml_tensor * t, uint8_t v, size
     invalidate(c->device, (char *) t->data + off, n);
     Q2A_HIP(hipMemset((char *) t->data + off, v, n));
 }
+
+// a weight the fast MUL_MAT path takes: contiguous 2-D (ne00 = K, ne01 = N) of a type the GEMM has a packing for
+bool mm_weight_ok(const ggml_tensor * w) {
+    const int64_t K = w->ne[0], N = w->ne[1];
+    return (w->type == GGML_TYPE_F16 || w->type == GGML_TYPE_Q4_K || w->type == GGML_TYPE_Q8_0 || w->type == GGML_TYPE_Q4_0) &&
+           ggml_is_contiguous(w) && w->ne[2] == 1 && w->ne[3] == 1 && N % 128 == 0 && K % 256 == 0 && K <= 8192 && N <= (1 << 30);
+}
+
 // Upload-time repack: the model loader writes each weight whole from host memory (qwen2-whisper.cpp:1845-1849),
 // before it marks the buffer WEIGHTS (:1867), so a whole write of a 2-D tensor that the fast MUL_MAT path could take
-// (mm_fast_ok's shape rule) is packed here from the host bytes, and the first whisper_full finds it in the cache
+// (mm_weight_ok) is packed here from the host bytes, and the first whisper_full finds it in the cache
 // instead of paying a device->host copy + host repack per weight. Anything else is packed lazily by get_packed.
 void prepack(int device, const ggml_tensor * t, const void * host, size_t off, size_t n) {
     if (off != 0 || n != ggml_nbytes(t) || t->view_src) return;
@@ -763,13 +771,9 @@ void prepack(int device, const ggml_tensor * t, const void * host, size_t off, s
     // its cache entry would outlive a kernel's later overwrite of the same address): only weight-bearing buffers,
     // which are still ANY while the loader uploads (qwen2-whisper.cpp:1845-1867)
     if (t->buffer && ggml_backend_buffer_get_usage(t->buffer) == GGML_BACKEND_BUFFER_USAGE_COMPUTE) return;
-    if (t->type != GGML_TYPE_F16 && t->type != GGML_TYPE_Q4_K && t->type != GGML_TYPE_Q8_0 && t->type != GGML_TYPE_Q4_0)
-        return;
-    if (t->ne[2] != 1 || t->ne[3] != 1 || !ggml_is_contiguous(t)) return;
-    const int64_t K = t->ne[0], N = t->ne[1];
-    if (N % 128 != 0 || K % 256 != 0 || K > 8192 || N > (1 << 30)) return;
+    if (!mm_weight_ok(t)) return;
     packed_w p;
-    p.raw = (const char *) t->data; p.raw_bytes = n; p.type = t->type; p.N = (int) N; p.K = (int) K;
+    p.raw = (const char *) t->data; p.raw_bytes = n; p.type = t->type; p.N = (int) t->ne[1]; p.K = (int) t->ne[0];
     std::vector<uint8_t> out;
     if (q2a_pack_linear((const uint8_t *) host, t->type, p.N, p.K, out, p.off) != 0) return;
     Q2A_HIP(hipMalloc(&p.dev, out.size()));
@@ -904,25 +908,26 @@ tview tv(const ggml_tensor * t) {
 
 dim3 grid1(int64_t n) { return dim3((unsigned) ((n + 255) / 256)); }
 
-// Captured HIP graphs bake in the addresses of the scratch, V^T and fp16-shadow buffers: whenever one of them is
-// reallocated, every captured exec is destroyed (its cgraph is re-captured on its next sightings against the new
-// buffers), so no replay can touch freed memory.
-// A buffer must grow while graph_compute is capturing (the second sighting of a cgraph whose node sequence needs more
-// than its first run did): a capturing stream cannot be synchronised and the capture would bake in the buffer about
-// to be freed. End the capture and discard it (nothing captured has run). The node that asked for the buffer would
-// otherwise go on launching its kernels directly, on inputs that earlier nodes only captured and never computed, so
-// once the buffer has grown a DISCARD capture is begun (resume_discard): whatever the rest of that node launches is
-// captured into it and thrown away. run_nodes stops at the next node, and graph_compute ends the discard capture and
-// runs the cgraph again directly, against the new buffers.
-void abort_capture(q2a_backend_ctx * b) {
+// a GGML_Q2A_* switch: set to a non-zero number (callers read it once per process)
+bool env_on(const char * name) {
+    const char * v = getenv(name);
+    return v && atoi(v);
+}
+
+// end the capture in progress on the stream, if any, and drop what it recorded (true: there was one)
+bool drop_capture(q2a_backend_ctx * b) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(b->stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive) {
-        hipGraph_t gr = nullptr;
-        (void) hipStreamEndCapture(b->stream, &gr);
-        if (gr) (void) hipGraphDestroy(gr);
-        (void) hipGetLastError();
-        b->capture_aborted = true;
-    }
+    if (hipStreamIsCapturing(b->stream, &st) != hipSuccess || st != hipStreamCaptureStatusActive) return false;
+    hipGraph_t gr = nullptr;
+    (void) hipStreamEndCapture(b->stream, &gr);
+    if (gr) (void) hipGraphDestroy(gr);
+    (void) hipGetLastError();
+    return true;
+}
+
+// a buffer is about to grow under graph_compute's capture (nothing captured has run); see grow
+void abort_capture(q2a_backend_ctx * b) {
+    if (drop_capture(b)) b->capture_aborted = true;
 }
 
 // after the growth that abort_capture allowed: route the aborted node's remaining launches into a discarded capture
@@ -933,12 +938,7 @@ void resume_discard(q2a_backend_ctx * b) {
 
 // end (and drop) the discard capture, if one is open
 void end_discard(q2a_backend_ctx * b) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(b->stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive) {
-        hipGraph_t gr = nullptr;
-        (void) hipStreamEndCapture(b->stream, &gr);
-        if (gr) (void) hipGraphDestroy(gr);
-    }
+    (void) drop_capture(b);
     (void) hipGetLastError();
 }
 
@@ -951,59 +951,97 @@ void drop_graphs(q2a_backend_ctx * b) {
     ++b->n_buffer_reallocs;
 }
 
-void * scratch(q2a_backend_ctx * b, size_t bytes) {
-    if (bytes > b->scratch_bytes) {
-        b->quant_src = nullptr;
+// Captured HIP graphs bake in the addresses of the scratch, V^T and fp16-shadow buffers: whenever one of them is
+// reallocated, every captured exec is destroyed (its cgraph is re-captured on its next sightings against the new
+// buffers), so no replay can touch freed memory.
+// A buffer must grow while graph_compute is capturing (the second sighting of a cgraph whose node sequence needs more
+// than its first run did): a capturing stream cannot be synchronised and the capture would bake in the buffer about
+// to be freed. End the capture and discard it (nothing captured has run). The node that asked for the buffer would
+// otherwise go on launching its kernels directly, on inputs that earlier nodes only captured and never computed, so
+// once the buffer has grown a DISCARD capture is begun (resume_discard): whatever the rest of that node launches is
+// captured into it and thrown away. run_nodes stops at the next node, and graph_compute ends the discard capture and
+// runs the cgraph again directly, against the new buffers.
+// Every device buffer grows here, and the order of the steps matters (zero: the new block is zero-filled first).
+template <typename T>
+T * grow(q2a_backend_ctx * b, T ** ptr, size_t * have, size_t need, bool zero = false) {
+    if (need > *have) {
         abort_capture(b);
         Q2A_HIP(hipStreamSynchronize(b->stream));
-        if (b->scratch) Q2A_HIP(hipFree(b->scratch));
-        b->scratch = nullptr;
-        Q2A_HIP(hipMalloc(&b->scratch, bytes));
-        b->scratch_bytes = bytes;
+        if (*ptr) Q2A_HIP(hipFree(*ptr));
+        *ptr = nullptr;
+        Q2A_HIP(hipMalloc((void **) ptr, need));
+        if (zero) {
+            Q2A_HIP(hipMemsetAsync(*ptr, 0, need, b->stream));
+            Q2A_HIP(hipStreamSynchronize(b->stream));
+        }
+        *have = need;
         drop_graphs(b);
         resume_discard(b);
     }
-    return b->scratch;
+    return *ptr;
 }
 
-bool is_weight_type(int t) {
-    return t == GGML_TYPE_F16 || t == GGML_TYPE_Q4_K || t == GGML_TYPE_Q8_0 || t == GGML_TYPE_Q4_0;
+void * scratch(q2a_backend_ctx * b, size_t bytes) {
+    if (bytes > b->scratch_bytes) b->quant_src = nullptr;   // the quantized image goes with the old block
+    return grow(b, &b->scratch, &b->scratch_bytes, bytes);
 }
 
-// the fast MUL_MAT path: contiguous 2-D weight (ne00 = K, ne01 = N) x contiguous F32 rows
+// the fast MUL_MAT path: such a weight x contiguous F32 rows
 bool mm_fast_ok(const ggml_tensor * op) {
-    const ggml_tensor * w = op->src[0];
     const ggml_tensor * x = op->src[1];
-    if (!is_weight_type(w->type) || x->type != GGML_TYPE_F32 || op->type != GGML_TYPE_F32) return false;
-    if (!ggml_is_contiguous(w) || !ggml_is_contiguous(x) || !ggml_is_contiguous(op)) return false;
-    if (w->ne[2] != 1 || w->ne[3] != 1) return false;
-    const int64_t K = w->ne[0], N = w->ne[1];
-    return N % 128 == 0 && K % 256 == 0 && K <= 8192 && N <= (1 << 30);
+    return mm_weight_ok(op->src[0]) && x->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && ggml_is_contiguous(x) &&
+           ggml_is_contiguous(op);
 }
 
+// packed_w::type of the cache entries that are not a weight tensor's own repack (never a ggml type)
+constexpr int TAG_DUP16 = -16;       // - P: the conv kernel repeated P times per row (get_dup16)
+constexpr int TAG_QKV_W = -64;       // - ggml type: the Q | K | V weights as one operand (get_qkv_weight)
+constexpr int TAG_QKV_BIAS = -200;   // [bq | 0 | bv] (get_qkv_bias)
+
+struct cache_key {         // the fields of the packed_w it names; raw_bytes and K are compared only where asked
+    const char * raw; size_t raw_bytes; int type, N, K;
+    bool match_bytes, match_K;
+};
+
+// The weight cache's one lookup-or-build: the entry matching `key`, found under the device lock; or else `build`
+// fills a new entry's dev / off outside the lock (between two syncs of the stream: it copies and launches), and the
+// entry is pushed under the lock, after `before_insert(device ctx)` ran under that same acquisition.
 // (returned by value: the cache vector may grow or swap-remove entries under another backend's lock)
-packed_w get_packed(q2a_backend_ctx * b, const ggml_tensor * w) {
+template <typename Build, typename BeforeInsert = void (*)(q2a_device_ctx *)>
+packed_w cache_get(q2a_backend_ctx * b, const cache_key & key, Build build,
+                   BeforeInsert before_insert = [](q2a_device_ctx *) {}) {
     q2a_device_ctx * d = dev_ctx(b->device);
     {
         std::lock_guard<std::mutex> lk(d->mu);
         for (const packed_w & p : d->wcache)
-            if (p.raw == (const char *) w->data && p.type == w->type && p.N == w->ne[1] && p.K == w->ne[0]) return p;
+            if (p.raw == key.raw && (!key.match_bytes || p.raw_bytes == key.raw_bytes) && p.type == key.type &&
+                p.N == key.N && (!key.match_K || p.K == key.K))
+                return p;
     }
-    // first use: repack on the host from the device bytes (one-time, per weight tensor)
-    ++b->n_repack_lazy;
-    const size_t nb = ggml_nbytes(w);
-    std::vector<uint8_t> raw(nb);
+    packed_w p{};
+    p.raw = key.raw; p.raw_bytes = key.raw_bytes; p.type = key.type; p.N = key.N; p.K = key.K;
     Q2A_HIP(hipStreamSynchronize(b->stream));
-    Q2A_HIP(hipMemcpy(raw.data(), w->data, nb, hipMemcpyDeviceToHost));
-    packed_w p;
-    p.raw = (const char *) w->data; p.raw_bytes = nb; p.type = w->type; p.N = (int) w->ne[1]; p.K = (int) w->ne[0];
-    std::vector<uint8_t> out;
-    if (q2a_pack_linear(raw.data(), w->type, p.N, p.K, out, p.off) != 0) GGML_ABORT("ggml-q2a: cannot pack %s", w->name);
-    Q2A_HIP(hipMalloc(&p.dev, out.size()));
-    Q2A_HIP(hipMemcpy(p.dev, out.data(), out.size(), hipMemcpyHostToDevice));
+    build(p);
+    Q2A_HIP(hipStreamSynchronize(b->stream));
     std::lock_guard<std::mutex> lk(d->mu);
+    before_insert(d);
     d->wcache.push_back(p);
     return p;
+}
+
+packed_w get_packed(q2a_backend_ctx * b, const ggml_tensor * w) {
+    const size_t nb = ggml_nbytes(w);
+    const cache_key key{(const char *) w->data, nb, w->type, (int) w->ne[1], (int) w->ne[0], false, true};
+    return cache_get(b, key, [&](packed_w & p) {
+        // first use: repack on the host from the device bytes (one-time, per weight tensor)
+        ++b->n_repack_lazy;
+        std::vector<uint8_t> raw(nb);
+        Q2A_HIP(hipMemcpy(raw.data(), w->data, nb, hipMemcpyDeviceToHost));
+        std::vector<uint8_t> out;
+        if (q2a_pack_linear(raw.data(), w->type, p.N, p.K, out, p.off) != 0) GGML_ABORT("ggml-q2a: cannot pack %s", w->name);
+        Q2A_HIP(hipMalloc(&p.dev, out.size()));
+        Q2A_HIP(hipMemcpy(p.dev, out.data(), out.size(), hipMemcpyHostToDevice));
+    });
 }
 
 struct mm_chain {          // a fast MUL_MAT and the nodes its epilogue absorbs
@@ -1014,12 +1052,6 @@ struct mm_chain {          // a fast MUL_MAT and the nodes its epilogue absorbs
     float oscale;
     int last;              // graph index of `out`
     int nfused;            // nodes absorbed
-};
-struct mm_second {         // the second GEMM of a grouped launch (same activation, fp16 weight of the same shape)
-    const ggml_tensor * w;
-    ggml_tensor * out;
-    const float * bias;
-    float oscale;
 };
 
 // the activation operand of a fast MUL_MAT, in the scratch: fp16 rows (F16 weights; the producer's fp16 shadow when it
@@ -1045,16 +1077,13 @@ act_operand act_slots(q2a_backend_ctx * b, int M, int K, int blk, size_t extra) 
 }
 
 act_operand activation_operand(q2a_backend_ctx * b, const ggml_tensor * x, int M, int K, int blk, size_t extra) {
-    const act_operand slots = act_slots(b, M, K, blk, extra);
-    const int MP = slots.MP;
-    q2a_half * A = (q2a_half *) slots.A;
-    float * dy = slots.dy;
-    q2a_half * aext = slots.aext;
+    act_operand ao = act_slots(b, M, K, blk, extra);
+    q2a_half * A = (q2a_half *) ao.A;
     const _Float16 * shadow = nullptr;
     if (blk == 0)
         for (int k = 0; k < 2; ++k) if (b->a16_src[k] == x) shadow = b->a16[k];
     if (shadow) {
-        A = (q2a_half *) shadow;   // the producer already wrote the fp16 operand
+        ao.A = (const q2a_half *) shadow;   // the producer already wrote the fp16 operand
     } else if (blk == 0) {
         const int64_t n = (int64_t) M * K;
         if (n % 8 == 0 && ((uintptr_t) x->data & 15) == 0 && ((uintptr_t) A & 15) == 0)
@@ -1062,14 +1091,14 @@ act_operand activation_operand(q2a_backend_ctx * b, const ggml_tensor * x, int M
         else
             hipLaunchKernelGGL(k_f32_to_f16, grid1(n), dim3(256), 0, b->stream, (const float *) x->data, A, n);
     } else if (b->quant_src != x || b->quant_blk != blk) {
-        q2a_quant_args qa{(const float *) x->data, nullptr, M, K, blk == 256 ? 1 : 2, A, dy, aext, MP};
+        q2a_quant_args qa{(const float *) x->data, nullptr, M, K, blk == 256 ? 1 : 2, A, ao.dy, ao.aext, ao.MP};
         Q2A_HIP(q2a_launch_quant_act(qa, b->stream));
     }
     // the scratch now holds x's quantized image (Q8_K / Q8_0 codes and scales): the next quantized-weight MUL_MAT of
     // the same activation (the Q, K, V projections) reuses it; an fp16 conversion overwrote it
     b->quant_src = blk ? x : nullptr;
     b->quant_blk = blk;
-    return {A, dy, aext, MP, slots.extra};
+    return ao;
 }
 
 int blk_of_type(int t) { return t == GGML_TYPE_Q4_K ? 256 : t == GGML_TYPE_F16 ? 0 : 32; }
@@ -1081,12 +1110,40 @@ size_t mm_part_bytes(int epi, int blk, int M, int N, int K, bool grouped) {
     return nsplit > 1 ? (size_t) nsplit * M * N * 4 : 0;
 }
 
-// epi: Q2A_EPI_STORE_F (bias optional), Q2A_EPI_GELU_F (bias, GELU), Q2A_EPI_RESID (bias, + resid rows); the result
-// goes to `out` (op itself, or the last node of a fused MUL_MAT -> ADD [-> GELU | ADD] chain)
-void run_mm_fast(q2a_backend_ctx * b, ggml_tensor * op, ggml_tensor * out = nullptr, int epi = Q2A_EPI_STORE_F,
-                 const float * bias = nullptr, const float * resid = nullptr, float oscale = 0.0f,
-                 _Float16 * out16 = nullptr, const mm_second * sec = nullptr) {
-    if (!out) out = op;
+// point the GEMM at a packed image's sections (q2a_pack_linear layout, K / blk blocks) and at the activation's block
+// scales; second: the second weight of a grouped Q4_K launch, which shares the first's activation operand
+void set_packed_operand(q2a_gemm_args & a, const packed_w & p, int blk, const act_operand & ao, bool second = false) {
+    const char * base = (const char *) p.dev;
+    if (second) {
+        a.W2 = (const q2a_half *) (base + p.off[0]);
+        a.dx2 = (const float *) (base + p.off[1]);
+        a.dmin2 = (const float *) (base + p.off[2]);
+        a.wext2 = (const q2a_half *) (base + p.off[3]);
+        a.beta2 = (const float *) (base + p.off[4]);
+        a.gamma2 = (const float *) (base + p.off[5]);
+        return;
+    }
+    a.W = (const q2a_half *) (base + p.off[0]);
+    if (blk == 0) return;
+    a.nblk = p.K / blk;
+    a.dx = (const float *) (base + p.off[1]);
+    a.dy = ao.dy; a.dy_ld = ao.MP;
+    if (blk == 256) {
+        a.dmin = (const float *) (base + p.off[2]);
+        a.wext = (const q2a_half *) (base + p.off[3]);
+        a.beta = (const float *) (base + p.off[4]);
+        a.gamma = (const float *) (base + p.off[5]);
+        a.aext = ao.aext;
+    }
+}
+
+// c.epi: Q2A_EPI_STORE_F (bias optional), Q2A_EPI_GELU_F (bias, GELU), Q2A_EPI_RESID (bias, + resid rows); the result
+// goes to c.out (op itself, or the last node of a fused MUL_MAT -> ADD [-> GELU | ADD] chain). w2, c2: the second GEMM
+// of a grouped launch (same activation, weight of the same type and shape, a STORE_F chain)
+void run_mm_fast(q2a_backend_ctx * b, ggml_tensor * op, const mm_chain & c, _Float16 * out16 = nullptr,
+                 const ggml_tensor * w2 = nullptr, const mm_chain * c2 = nullptr) {
+    ggml_tensor * out = c.out;
+    const int epi = c.epi;
     const ggml_tensor * w = op->src[0];
     const ggml_tensor * x = op->src[1];
     const int K = (int) w->ne[0], N = (int) w->ne[1];
@@ -1094,7 +1151,7 @@ void run_mm_fast(q2a_backend_ctx * b, ggml_tensor * op, ggml_tensor * out = null
     const int blk = blk_of_type(w->type);
     // fp16 small-tile GEMMs (a single clip) split K like the engine's residual GEMMs (q2a_gemm_resid_ksplit: up to
     // 4 partial [M][N] f32 planes, reduced in split order with the bias / residual / scale of the epilogue)
-    const size_t part_bytes = mm_part_bytes(epi, blk, M, N, K, sec != nullptr);
+    const size_t part_bytes = mm_part_bytes(epi, blk, M, N, K, w2 != nullptr);
     const bool split = part_bytes > 0;
     const act_operand ao = activation_operand(b, x, M, K, blk, part_bytes);
     q2a_gemm_args a;
@@ -1102,27 +1159,18 @@ void run_mm_fast(q2a_backend_ctx * b, ggml_tensor * op, ggml_tensor * out = null
     a.A = ao.A; a.lda = K; a.a_rpg = M; a.a_gstride = 0; a.a_step = 1;
     a.M = M; a.N = N; a.K = K; a.ldw = K;
     a.outF = (float *) out->data; a.ldo = N;
-    a.bias = bias; a.store_bias = bias != nullptr; a.resid = resid; a.out_scale = oscale;
+    a.bias = c.bias; a.store_bias = c.bias != nullptr; a.resid = c.resid; a.out_scale = c.oscale;
     if (epi == Q2A_EPI_GELU_F) a.outH = (q2a_half *) out16;
     if (epi == Q2A_EPI_GELU_H || epi == Q2A_EPI_PRE_H) {   // fp16 [M][N] only (no row remap)
         a.outH = (q2a_half *) out16;
         a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
     }
-    if (sec) {
+    if (w2) {
         a.ngroup = 2;
-        a.W2 = (const q2a_half *) sec->w->data;
-        a.bias2 = sec->bias; a.store_bias2 = sec->bias != nullptr;
-        a.outF2 = (float *) sec->out->data; a.out_scale2 = sec->oscale;
-        if (blk == 256) {   // the second weight's packed image: operand and block scales like the first's below
-            const packed_w p2 = get_packed(b, sec->w);
-            const char * base2 = (const char *) p2.dev;
-            a.W2 = (const q2a_half *) (base2 + p2.off[0]);
-            a.dx2 = (const float *) (base2 + p2.off[1]);
-            a.dmin2 = (const float *) (base2 + p2.off[2]);
-            a.wext2 = (const q2a_half *) (base2 + p2.off[3]);
-            a.beta2 = (const float *) (base2 + p2.off[4]);
-            a.gamma2 = (const float *) (base2 + p2.off[5]);
-        }
+        a.W2 = (const q2a_half *) w2->data;
+        a.bias2 = c2->bias; a.store_bias2 = c2->bias != nullptr;
+        a.outF2 = (float *) c2->out->data; a.out_scale2 = c2->oscale;
+        if (blk == 256) set_packed_operand(a, get_packed(b, w2), blk, ao, true);
     }
     if (split) {
         a.part = (float *) ao.extra;
@@ -1131,40 +1179,18 @@ void run_mm_fast(q2a_backend_ctx * b, ggml_tensor * op, ggml_tensor * out = null
         a.split_kq = 1;
     }
     a.gelu_tab = gelu_table(b->device);
-    if (blk == 0) {
-        a.W = (const q2a_half *) w->data;
-    } else {
-        const packed_w p = get_packed(b, w);
-        const char * base = (const char *) p.dev;
-        a.W = (const q2a_half *) (base + p.off[0]);
-        a.nblk = K / blk;
-        a.dx = (const float *) (base + p.off[1]);
-        a.dy = ao.dy; a.dy_ld = ao.MP;
-        if (blk == 256) {
-            a.dmin = (const float *) (base + p.off[2]);
-            a.wext = (const q2a_half *) (base + p.off[3]);
-            a.beta = (const float *) (base + p.off[4]);
-            a.gamma = (const float *) (base + p.off[5]);
-            a.aext = ao.aext;
-        }
-    }
+    if (blk == 0) a.W = (const q2a_half *) w->data;
+    else set_packed_operand(a, get_packed(b, w), blk, ao);
     Q2A_HIP(q2a_launch_gemm(a, epi, blk, b->stream));
 }
 
-_Float16 * claim_a16(q2a_backend_ctx * b, const ggml_tensor * t);
-
-_Float16 * pre16_buffer(q2a_backend_ctx * b, size_t bytes) {
-    if (bytes > b->pre16_bytes) {
-        abort_capture(b);
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        if (b->pre16) Q2A_HIP(hipFree(b->pre16));
-        b->pre16 = nullptr;
-        Q2A_HIP(hipMalloc((void **) &b->pre16, bytes));
-        b->pre16_bytes = bytes;
-        drop_graphs(b);
-        resume_discard(b);
-    }
-    return b->pre16;
+// a shadow slot for the fp16 copy of tensor t (the slot not written last)
+_Float16 * claim_a16(q2a_backend_ctx * b, const ggml_tensor * t) {
+    const int k = 1 - b->a16_last;
+    grow(b, &b->a16[k], &b->a16_bytes[k], (size_t) ggml_nelements(t) * 2);
+    b->a16_last = k;
+    b->a16_src[k] = t;
+    return b->a16[k];
 }
 
 // fc1 -> ADD(bias) -> GELU whose output only fc2 reads (qwen2-whisper.cpp:2136-2154): fc1's epilogue writes what fc2
@@ -1176,15 +1202,17 @@ void run_fc1_for_fc2(q2a_backend_ctx * b, ggml_tensor * op, const mm_chain & c, 
     const ggml_tensor * gelu = c.out;
     const int M = (int) (op->src[1]->ne[1] * op->src[1]->ne[2] * op->src[1]->ne[3]), F = (int) op->src[0]->ne[1];
     const int blk2 = blk_of_type(fc2->src[0]->type);
+    mm_chain h = c;   // (a GELU_F chain: no residual, no scale) with the fp16 epilogue fc2's operand needs
+    h.epi = blk2 == 256 ? Q2A_EPI_PRE_H : Q2A_EPI_GELU_H;
     if (blk2 == 0) {
-        run_mm_fast(b, op, c.out, Q2A_EPI_GELU_H, c.bias, nullptr, 0.0f, claim_a16(b, gelu));
+        run_mm_fast(b, op, h, claim_a16(b, gelu));
         return;
     }
     // fc2's operand slots first: a scratch growth now loses nothing (fc1's own operand is produced after it)
     const int N2 = (int) fc2->src[0]->ne[1];
     (void) act_slots(b, M, F, blk2, mm_part_bytes(Q2A_EPI_RESID, blk2, M, N2, F, false));
-    _Float16 * pre = pre16_buffer(b, (size_t) M * F * 2);
-    run_mm_fast(b, op, c.out, blk2 == 256 ? Q2A_EPI_PRE_H : Q2A_EPI_GELU_H, c.bias, nullptr, 0.0f, pre);
+    _Float16 * pre = grow(b, &b->pre16, &b->pre16_bytes, (size_t) M * F * 2);
+    run_mm_fast(b, op, h, pre);
     const act_operand d = act_slots(b, M, F, blk2, 0);
     if (blk2 == 256) {
         Q2A_HIP(q2a_launch_gelu_quant_q8k((const q2a_half *) pre, M, F, gelu_table(b->device), (q2a_half *) d.A, d.dy,
@@ -1206,23 +1234,12 @@ bool is_weight_buffer(const ggml_tensor * w) {
 }
 
 packed_w get_dup16(q2a_backend_ctx * b, const ggml_tensor * w, int N, int K, int P) {
-    const int DUP16 = -16 - P;   // cache tag (not a ggml type)
-    q2a_device_ctx * d = dev_ctx(b->device);
-    {
-        std::lock_guard<std::mutex> lk(d->mu);
-        for (const packed_w & p : d->wcache)
-            if (p.raw == (const char *) w->data && p.type == DUP16 && p.N == N && p.K == K) return p;
-    }
-    packed_w p{};
-    p.raw = (const char *) w->data; p.raw_bytes = ggml_nbytes(w); p.type = DUP16; p.N = N; p.K = K;
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    Q2A_HIP(hipMalloc(&p.dev, (size_t) N * P * K * 2));
-    const int n = N * K;
-    hipLaunchKernelGGL(k_dup_rows, grid1(n), dim3(256), 0, b->stream, (const _Float16 *) w->data, (_Float16 *) p.dev, K, P, n);
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    std::lock_guard<std::mutex> lk(d->mu);
-    d->wcache.push_back(p);
-    return p;
+    const cache_key key{(const char *) w->data, ggml_nbytes(w), TAG_DUP16 - P, N, K, false, true};
+    return cache_get(b, key, [&](packed_w & p) {
+        Q2A_HIP(hipMalloc(&p.dev, (size_t) N * P * K * 2));
+        const int n = N * K;
+        hipLaunchKernelGGL(k_dup_rows, grid1(n), dim3(256), 0, b->stream, (const _Float16 *) w->data, (_Float16 *) p.dev, K, P, n);
+    });
 }
 
 // The hi/lo split writes each f32 activation x as fp16 hi = fp16(x) plus fp16 lo = fp16(x - hi) (22 significant
@@ -1232,7 +1249,7 @@ packed_w get_dup16(q2a_backend_ctx * b, const ggml_tensor * w, int N, int K, int
 // (absolute error < 2^-25, far below the f32 rounding of the 384/3840-term dot products). Outside that range
 // (GGML_Q2A_NO_CONV_HILO=1) the exact-f32 MFMA GEMM (run_mm_f32) computes the node.
 bool conv_hilo_ok(const ggml_tensor * op) {
-    static const bool off = [] { const char * v = getenv("GGML_Q2A_NO_CONV_HILO"); return v && atoi(v); }();
+    static const bool off = env_on("GGML_Q2A_NO_CONV_HILO");
     const ggml_tensor * x = op->src[0];
     const ggml_tensor * w = op->src[1];
     if (off || x->type != GGML_TYPE_F32 || w->type != GGML_TYPE_F16 || op->type != GGML_TYPE_F32) return false;
@@ -1321,7 +1338,7 @@ __global__ void k_conv_f64(const float * x, const _Float16 * w, float * out, int
     out[(int64_t) n * M + m] = (float) acc;
 }
 bool conv_f64_diag(const ggml_tensor * op) {
-    static const bool on = [] { const char * v = getenv("GGML_Q2A_CONV_F64"); return v && atoi(v); }();
+    static const bool on = env_on("GGML_Q2A_CONV_F64");
     const ggml_tensor * x = op->src[0];
     const ggml_tensor * w = op->src[1];
     return on && x->type == GGML_TYPE_F32 && w->type == GGML_TYPE_F16 && op->type == GGML_TYPE_F32 &&
@@ -1352,12 +1369,11 @@ void run_mm_f32(q2a_backend_ctx * b, ggml_tensor * op) {
 }
 
 // KQ = MUL_MAT(K, Q) -> SOFT_MAX(KQ, no mask) -> KQV = MUL_MAT(V, KQ_soft_max), heads of 64 (qwen2-whisper.cpp:
-// 2052-2106): when nodes i..i+2 form exactly this chain and KQ / KQ_soft_max feed nothing else, run it as the
-// engine's flash kernel and skip the 20 x T x T score tensors. Returns the number of nodes consumed (0 = no match).
-// KQ -> SOFT_MAX -> KQV at nodes i..i+2 with K, Q, V views the fused kernel accepts (no other consumer of the score
-// tensors); returns the KQV node or null
+// 2052-2106): when nodes i..i+2 form exactly this chain, with K, Q, V views the fused kernel accepts, and KQ /
+// KQ_soft_max feed nothing else, it runs as the engine's flash kernel and skips the 20 x T x T score tensors.
+// Returns the KQV node or null
 ggml_tensor * match_attention(ggml_cgraph * g, int i) {
-    static const bool off = [] { const char * v = getenv("GGML_Q2A_NO_FUSED_ATTN"); return v && atoi(v); }();
+    static const bool off = env_on("GGML_Q2A_NO_FUSED_ATTN");
     if (off || i + 2 >= ggml_graph_n_nodes(g)) return nullptr;
     ggml_tensor * kq = ggml_graph_node(g, i);
     ggml_tensor * sm = ggml_graph_node(g, i + 1);
@@ -1389,133 +1405,106 @@ ggml_tensor * match_attention(ggml_cgraph * g, int i) {
     return kqv;
 }
 
-_Float16 * vt_buffer(q2a_backend_ctx * b, size_t bytes) {
-    if (bytes > b->vt_bytes) {
-        abort_capture(b);
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        if (b->vt_buf) Q2A_HIP(hipFree(b->vt_buf));
-        b->vt_buf = nullptr;
-        Q2A_HIP(hipMalloc((void **) &b->vt_buf, bytes));
-        b->vt_bytes = bytes;
-        drop_graphs(b);
-        resume_discard(b);
-    }
-    return b->vt_buf;
+// The fused attention's operands for T rows of D = 64 H columns, wherever they live (the scratch, qkv_buf, vt_buf):
+// four [T][D] fp16 images Q hi | Q lo | K hi | K lo of hb bytes each, then V^T [H][64][TP] hi of vb1 bytes and, when
+// the attention kernel wants it (vlo), the lo image right behind it
+struct attn_layout {
+    int TP; size_t hb, vb1; bool vlo;
+    size_t vb() const { return vlo ? 2 * vb1 : vb1; }
+    _Float16 * vtl(_Float16 * vt) const { return vlo ? (_Float16 *) ((char *) vt + vb1) : nullptr; }
+};
+attn_layout attn_layout_of(int64_t T, int64_t D) {
+    const int TP = (int) ((T + 63) / 64 * 64);
+    return {TP, ((size_t) T * D * 2 + 255) & ~size_t(255), ((size_t) D * TP * 2 + 255) & ~size_t(255),
+            q2a_attention_wants_vlo()};
 }
 
-// a shadow slot for the fp16 copy of tensor t (the slot not written last)
-_Float16 * claim_a16(q2a_backend_ctx * b, const ggml_tensor * t) {
-    const int k = 1 - b->a16_last;
-    const size_t bytes = (size_t) ggml_nelements(t) * 2;
-    if (bytes > b->a16_bytes[k]) {
-        abort_capture(b);
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        if (b->a16[k]) Q2A_HIP(hipFree(b->a16[k]));
-        b->a16[k] = nullptr;
-        Q2A_HIP(hipMalloc((void **) &b->a16[k], bytes));
-        b->a16_bytes[k] = bytes;
-        drop_graphs(b);
-        resume_discard(b);
-    }
-    b->a16_last = k;
-    b->a16_src[k] = t;
-    return b->a16[k];
-}
-
-// vt_ready: V^T was already written into b->vt_buf at V's CONT node. merged: the CONT of permute(KQV, 0,2,1,3)
-// that follows (qwen2-whisper.cpp:2105-2107), whose [t][h*64+d] rows are exactly the fused kernel's output rows —
-// the kernel writes them there directly. Returns the number of nodes consumed.
-struct qkv_ops {                   // the attention operands as the fused Q|K|V GEMM wrote them (qkv_buffer layout)
+struct qkv_ops {                   // the attention operands, e.g. as the fused Q|K|V GEMM wrote them into qkv_buf
     _Float16 *qh, *ql, *kh, *kl, *vt, *vtl;
 };
+qkv_ops attn_operands(char * base, const attn_layout & L, _Float16 * vt) {
+    return {(_Float16 *) base, (_Float16 *) (base + L.hb), (_Float16 *) (base + 2 * L.hb), (_Float16 *) (base + 3 * L.hb),
+            vt, L.vtl(vt)};
+}
 
+#ifdef Q2A_DIAG_DUMP_ATTN   // diagnostic builds only
+// the first attention's operands of a process -> $Q2A_DUMP_ATTN
+void dump_attn_operands(q2a_backend_ctx * b, const qkv_ops & ops, size_t nq, size_t nv) {
+    static bool done = false;
+    const char * path = getenv("Q2A_DUMP_ATTN");
+    if (done || !path) return;
+    done = true;
+    Q2A_HIP(hipStreamSynchronize(b->stream));
+    FILE * f = fopen(path, "wb");
+    std::vector<char> h(std::max(nq, nv));
+    for (const _Float16 * x : {ops.qh, ops.ql, ops.kh, ops.kl}) { Q2A_HIP(hipMemcpy(h.data(), x, nq, hipMemcpyDeviceToHost)); fwrite(h.data(), 1, nq, f); }
+    for (const _Float16 * x : {ops.vt, ops.vtl}) { if (!x) continue; Q2A_HIP(hipMemcpy(h.data(), x, nv, hipMemcpyDeviceToHost)); fwrite(h.data(), 1, nv, f); }
+    fclose(f);
+}
+// the Q tensor the separate route feeds its operand pass (f32 [T][D]) -> $Q2A_DUMP_ATTN.q
+void dump_attn_q(q2a_backend_ctx * b, const ggml_tensor * Q, size_t n) {
+    static bool qdone = false;
+    const char * path = getenv("Q2A_DUMP_ATTN");
+    if (qdone || !path) return;
+    qdone = true;
+    Q2A_HIP(hipStreamSynchronize(b->stream));
+    std::vector<float> h(n);
+    Q2A_HIP(hipMemcpy(h.data(), Q->data, n * 4, hipMemcpyDeviceToHost));
+    FILE * f = fopen((std::string(path) + ".q").c_str(), "wb");
+    fwrite(h.data(), 4, h.size(), f);
+    fclose(f);
+}
+#else
+void dump_attn_operands(q2a_backend_ctx *, const qkv_ops &, size_t, size_t) {}
+void dump_attn_q(q2a_backend_ctx *, const ggml_tensor *, size_t) {}
+#endif
+
+// The matched KQ -> SOFT_MAX -> KQV chain (match_attention) as the engine's flash kernel.
+// vt_ready: V^T was already written into b->vt_buf at V's CONT node. merged: the CONT of permute(KQV, 0,2,1,3)
+// that follows (qwen2-whisper.cpp:2105-2107), whose [t][h*64+d] rows are exactly the fused kernel's output rows —
+// the kernel writes them there directly. ready: the operands already in place (run_qkv_fused), so only the kernel
+// (and the output re-layout) runs.
 // out16: the merged output's fp16 shadow (its only consumer an F16-weight MUL_MAT): written instead of the f32 rows
-int run_fused_attention(q2a_backend_ctx * b, ggml_cgraph * g, int i, bool vt_ready, ggml_tensor * merged,
-                        const qkv_ops * ready = nullptr, _Float16 * out16 = nullptr) {
-    ggml_tensor * kq = ggml_graph_node(g, i);
-    ggml_tensor * kqv = ggml_graph_node(g, i + 2);
+void run_fused_attention(q2a_backend_ctx * b, ggml_tensor * kq, ggml_tensor * kqv, bool vt_ready, ggml_tensor * merged,
+                         const qkv_ops * ready, _Float16 * out16) {
     const ggml_tensor * K = kq->src[0];
     const ggml_tensor * Q = kq->src[1];
     const ggml_tensor * V = kqv->src[0];
     const int64_t T = Q->ne[1], H = Q->ne[2];
-    const int TP = (int) ((T + 63) / 64 * 64);
     const int64_t D = H * 64, n = T * D;
-    const size_t hb = ((size_t) n * 2 + 255) & ~size_t(255);
-    const bool vlo = q2a_attention_wants_vlo();
-    const size_t vb1 = ((size_t) H * 64 * TP * 2 + 255) & ~size_t(255);
-    const size_t vb = vlo ? 2 * vb1 : vb1;   // V^T [| V^T lo]
-#ifdef Q2A_DIAG_DUMP_ATTN   // diagnostic builds only: the first attention's operands of a process -> $Q2A_DUMP_ATTN
-    auto dump = [&](const _Float16 * qh, const _Float16 * ql, const _Float16 * kh, const _Float16 * kl, const _Float16 * vt,
-                    const _Float16 * vtl) {
-        static bool done = false;
-        const char * path = getenv("Q2A_DUMP_ATTN");
-        if (done || !path) return;
-        done = true;
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        FILE * f = fopen(path, "wb");
-        const size_t nq = (size_t) n * 2, nv = (size_t) H * 64 * TP * 2;
-        std::vector<char> h(std::max(nq, nv));
-        for (const _Float16 * x : {qh, ql, kh, kl}) { Q2A_HIP(hipMemcpy(h.data(), x, nq, hipMemcpyDeviceToHost)); fwrite(h.data(), 1, nq, f); }
-        for (const _Float16 * x : {vt, vtl}) { if (!x) continue; Q2A_HIP(hipMemcpy(h.data(), x, nv, hipMemcpyDeviceToHost)); fwrite(h.data(), 1, nv, f); }
-        fclose(f);
-    };
-    if (ready) dump(ready->qh, ready->ql, ready->kh, ready->kl, ready->vt, ready->vtl);
-    {   // the Q tensor the separate route feeds its operand pass (f32 [T][D]) -> $Q2A_DUMP_ATTN.q
-        static bool qdone = false;
-        const char * path = getenv("Q2A_DUMP_ATTN");
-        if (!ready && !qdone && path) {
-            qdone = true;
-            Q2A_HIP(hipStreamSynchronize(b->stream));
-            std::vector<float> h((size_t) n);
-            Q2A_HIP(hipMemcpy(h.data(), Q->data, (size_t) n * 4, hipMemcpyDeviceToHost));
-            FILE * f = fopen((std::string(path) + ".q").c_str(), "wb");
-            fwrite(h.data(), 4, h.size(), f);
-            fclose(f);
+    const attn_layout L = attn_layout_of(T, D);
+    const int TP = L.TP;
+    qkv_ops ops;
+    float * o;
+    if (ready) {
+        ops = *ready;
+        o = merged ? (float *) merged->data : (float *) scratch(b, (size_t) n * 4);
+        if (!merged) b->quant_src = nullptr;
+    } else {
+        dump_attn_q(b, Q, (size_t) n);
+        char * s = (char *) scratch(b, 4 * L.hb + L.vb() + (size_t) n * 4);
+        b->quant_src = nullptr;   // the attention operands overwrite the scratch
+        ops = attn_operands(s, L, vt_ready ? b->vt_buf : (_Float16 *) (s + 4 * L.hb));
+        o = merged ? (float *) merged->data : (float *) (s + 4 * L.hb + L.vb());
+        if (vt_ready) {
+            hipLaunchKernelGGL(k_attn_prep<false>, grid1(n), dim3(256), 0, b->stream, tv(Q), tv(K), tv(V), ops.qh, ops.ql,
+                               ops.kh, ops.kl, ops.vt, ops.vtl, (int) T, (int) H, TP, n);
+        } else {
+            Q2A_HIP(hipMemsetAsync(ops.vt, 0, L.vb(), b->stream));   // V^T tail columns past T are read as zero weights
+            hipLaunchKernelGGL(k_attn_prep<true>, grid1(n), dim3(256), 0, b->stream, tv(Q), tv(K), tv(V), ops.qh, ops.ql,
+                               ops.kh, ops.kl, ops.vt, ops.vtl, (int) T, (int) H, TP, n);
         }
     }
-#define Q2A_DUMP_PREP() dump(qh, ql, kh, kl, vt, vtl)
-#else
-#define Q2A_DUMP_PREP() do { } while (0)
-#endif
-    if (ready) {   // operands already in place (run_qkv_fused): only the kernel (and the output re-layout) runs
-        float * o = merged ? (float *) merged->data : (float *) scratch(b, (size_t) n * 4);
-        if (!merged) b->quant_src = nullptr;
-        q2a_attn_args at{(const q2a_half *) ready->qh, (const q2a_half *) ready->ql, (const q2a_half *) ready->kh,
-                         (const q2a_half *) ready->kl, (const q2a_half *) ready->vt, 1, (int) T, (int) D, (int) H, TP, nullptr, o};
-        at.vtl = ready->vtl;
-        at.v_rows = 1;   // (run_qkv_fused writes V row-major)
-        if (out16 && merged) { at.outH = (q2a_half *) out16; at.outF = nullptr; }
-        Q2A_HIP(q2a_launch_attention(at, b->stream));
-        if (!merged)
-            hipLaunchKernelGGL(k_attn_out, grid1(n), dim3(256), 0, b->stream, (const float *) o, tv(kqv), (int) T, (int) H, n);
-        b->stats.n_attn_fused++;
-        return merged ? 5 : 3;
-    }
-    char * s = (char *) scratch(b, 4 * hb + vb + (size_t) n * 4);
-    b->quant_src = nullptr;   // the attention operands overwrite the scratch
-    _Float16 *qh = (_Float16 *) s, *ql = (_Float16 *) (s + hb), *kh = (_Float16 *) (s + 2 * hb), *kl = (_Float16 *) (s + 3 * hb);
-    _Float16 * vt = vt_ready ? b->vt_buf : (_Float16 *) (s + 4 * hb);
-    _Float16 * vtl = vlo ? (_Float16 *) ((char *) vt + vb1) : nullptr;
-    float * o = merged ? (float *) merged->data : (float *) (s + 4 * hb + vb);
-    if (vt_ready) {
-        hipLaunchKernelGGL(k_attn_prep<false>, grid1(n), dim3(256), 0, b->stream, tv(Q), tv(K), tv(V), qh, ql, kh, kl, vt,
-                           vtl, (int) T, (int) H, TP, n);
-    } else {
-        Q2A_HIP(hipMemsetAsync(vt, 0, vb, b->stream));   // V^T tail columns past T are read as zero weights
-        hipLaunchKernelGGL(k_attn_prep<true>, grid1(n), dim3(256), 0, b->stream, tv(Q), tv(K), tv(V), qh, ql, kh, kl, vt,
-                           vtl, (int) T, (int) H, TP, n);
-    }
-    Q2A_DUMP_PREP();
-#undef Q2A_DUMP_PREP
-    q2a_attn_args at{(const q2a_half *) qh, (const q2a_half *) ql, (const q2a_half *) kh, (const q2a_half *) kl,
-                     (const q2a_half *) vt, 1, (int) T, (int) D, (int) H, TP, nullptr, o};
-    at.vtl = vtl;
+    dump_attn_operands(b, ops, (size_t) n * 2, (size_t) D * TP * 2);
+    q2a_attn_args at{(const q2a_half *) ops.qh, (const q2a_half *) ops.ql, (const q2a_half *) ops.kh,
+                     (const q2a_half *) ops.kl, (const q2a_half *) ops.vt, 1, (int) T, (int) D, (int) H, TP, nullptr, o};
+    at.vtl = (const q2a_half *) ops.vtl;
+    at.v_rows = ready ? 1 : 0;   // (run_qkv_fused writes V row-major)
     if (out16 && merged) { at.outH = (q2a_half *) out16; at.outF = nullptr; }
     Q2A_HIP(q2a_launch_attention(at, b->stream));
     if (!merged)
         hipLaunchKernelGGL(k_attn_out, grid1(n), dim3(256), 0, b->stream, (const float *) o, tv(kqv), (int) T, (int) H, n);
     b->stats.n_attn_fused++;
-    return merged ? 5 : 3;
 }
 
 // ---- the Q | K | V projections as ONE GEMM whose epilogue writes the fused attention's operands (the engine's
@@ -1526,133 +1515,95 @@ struct qkv_route {
     ggml_tensor * mm[3];            // Q, K, V MUL_MATs (same activation, same weight type and shape)
     const ggml_tensor * bq, * bv;   // bias rows of Q and V (the reference's K has none, :2039)
     float qscale;                   // ggml_scale after Q's bias (a power of two: KQscale = 1/8 for heads of 64)
+    const ggml_tensor * kq;         // the attention's KQ node
 };
 
 // the weights as one [3N][K] operand: fp16 rows concatenated (F16), or the three packed images' sections concatenated
 // along N (every section of q2a_pack_linear's layout is row- or block-major over N, so this IS the packed image of the
 // concatenated rows). Cached with the repacks under a key spanning the three source tensors: a write to any drops it.
 packed_w get_qkv_weight(q2a_backend_ctx * b, const ggml_tensor * const w[3]) {
-    const int TAG = -64 - (int) w[0]->type;   // cache tag (not a ggml type)
     const int N = (int) w[0]->ne[1], K = (int) w[0]->ne[0];
     const char * lo = (const char *) w[0]->data, * hi = lo + ggml_nbytes(w[0]);
     for (int i = 1; i < 3; ++i) {
         lo = std::min(lo, (const char *) w[i]->data);
         hi = std::max(hi, (const char *) w[i]->data + ggml_nbytes(w[i]));
     }
-    q2a_device_ctx * d = dev_ctx(b->device);
-    {
-        std::lock_guard<std::mutex> lk(d->mu);
-        for (const packed_w & p : d->wcache)
-            if (p.raw == lo && p.raw_bytes == (size_t) (hi - lo) && p.type == TAG && p.N == 3 * N && p.K == K) return p;
-    }
-    packed_w p{};
-    p.raw = lo; p.raw_bytes = (size_t) (hi - lo); p.type = TAG; p.N = 3 * N; p.K = K;
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    if (w[0]->type == GGML_TYPE_F16) {
-        const size_t rb = (size_t) N * K * 2;
-        Q2A_HIP(hipMalloc(&p.dev, 3 * rb));
-        for (int i = 0; i < 3; ++i) Q2A_HIP(hipMemcpyAsync((char *) p.dev + i * rb, w[i]->data, rb, hipMemcpyDeviceToDevice, b->stream));
-    } else {
-        const int blk = w[0]->type == GGML_TYPE_Q4_K ? 256 : 32, nblk = K / blk;
-        const uint64_t bytes = q2a_pack_layout(w[0]->type, 3 * N, K, p.off);
-        if (!bytes) GGML_ABORT("ggml-q2a: cannot pack the Q|K|V weights of %s", w[0]->name);
-        Q2A_HIP(hipMalloc(&p.dev, bytes));
-        char * dst = (char *) p.dev;
-        for (int i = 0; i < 3; ++i) {
-            const packed_w s = get_packed(b, w[i]);
-            const char * src = (const char *) s.dev;
-            Q2A_HIP(hipMemcpyAsync(dst + p.off[0] + (size_t) i * N * K * 2, src + s.off[0], (size_t) N * K * 2,
-                                   hipMemcpyDeviceToDevice, b->stream));
-            // block-major sections [nblk][N] x element bytes: dx (and dmin, wext (16 halves), beta, gamma for Q4_K)
-            const int secs[5] = {1, 2, 3, 4, 5};
-            const int esz[6] = {0, 4, 4, 32, 4, 4};
-            for (int k = 0; k < (blk == 256 ? 5 : 1); ++k) {
-                const int sc = secs[k];
-                const size_t e = (size_t) esz[sc];
-                Q2A_HIP(hipMemcpy2DAsync(dst + p.off[sc] + i * N * e, 3 * N * e, src + s.off[sc], N * e, N * e, nblk,
-                                         hipMemcpyDeviceToDevice, b->stream));
+    const cache_key key{lo, (size_t) (hi - lo), TAG_QKV_W - (int) w[0]->type, 3 * N, K, true, true};
+    auto build = [&](packed_w & p) {
+        if (w[0]->type == GGML_TYPE_F16) {
+            const size_t rb = (size_t) N * K * 2;
+            Q2A_HIP(hipMalloc(&p.dev, 3 * rb));
+            for (int i = 0; i < 3; ++i) Q2A_HIP(hipMemcpyAsync((char *) p.dev + i * rb, w[i]->data, rb, hipMemcpyDeviceToDevice, b->stream));
+        } else {
+            const int blk = blk_of_type(w[0]->type), nblk = K / blk;
+            const uint64_t bytes = q2a_pack_layout(w[0]->type, 3 * N, K, p.off);
+            if (!bytes) GGML_ABORT("ggml-q2a: cannot pack the Q|K|V weights of %s", w[0]->name);
+            Q2A_HIP(hipMalloc(&p.dev, bytes));
+            char * dst = (char *) p.dev;
+            for (int i = 0; i < 3; ++i) {
+                const packed_w s = get_packed(b, w[i]);
+                const char * src = (const char *) s.dev;
+                Q2A_HIP(hipMemcpyAsync(dst + p.off[0] + (size_t) i * N * K * 2, src + s.off[0], (size_t) N * K * 2,
+                                       hipMemcpyDeviceToDevice, b->stream));
+                // block-major sections [nblk][N] x element bytes: dx (and dmin, wext (16 halves), beta, gamma for Q4_K)
+                const int esz[6] = {0, 4, 4, 32, 4, 4};
+                for (int sc = 1; sc <= (blk == 256 ? 5 : 1); ++sc) {
+                    const size_t e = (size_t) esz[sc];
+                    Q2A_HIP(hipMemcpy2DAsync(dst + p.off[sc] + i * N * e, 3 * N * e, src + s.off[sc], N * e, N * e, nblk,
+                                             hipMemcpyDeviceToDevice, b->stream));
+                }
             }
         }
-    }
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    std::lock_guard<std::mutex> lk(d->mu);
+    };
     // the per-tensor images of Q, K and V (upload-time or lazy repacks) are not read again while the fused route is on:
     // released, so the expanded QKV weights are resident once (a graph that still needed one repacks it lazily; once any
     // graph has been captured on the device, the wgen bump keeps those that may hold their pointers from being replayed —
     // before that, nothing holds them and the capture schedule stays as it was)
-    for (size_t j = 0; j < d->wcache.size();) {
-        const packed_w & c = d->wcache[j];
-        bool own = false;
-        for (int i = 0; i < 3; ++i)
-            own |= c.raw == (const char *) w[i]->data && c.type == w[i]->type && c.N == N && c.K == K;
-        if (own) {
-            (void) hipFree(c.dev);
-            if (d->n_captured.load() > 0) ++d->wgen;
-            d->wcache[j] = d->wcache.back();
-            d->wcache.pop_back();
-        } else {
-            ++j;
+    auto evict_own = [&](q2a_device_ctx * d) {
+        for (size_t j = 0; j < d->wcache.size();) {
+            const packed_w & c = d->wcache[j];
+            bool own = false;
+            for (int i = 0; i < 3; ++i)
+                own |= c.raw == (const char *) w[i]->data && c.type == w[i]->type && c.N == N && c.K == K;
+            if (own) {
+                (void) hipFree(c.dev);
+                if (d->n_captured.load() > 0) ++d->wgen;
+                d->wcache[j] = d->wcache.back();
+                d->wcache.pop_back();
+            } else {
+                ++j;
+            }
         }
-    }
-    d->wcache.push_back(p);
-    return p;
+    };
+    return cache_get(b, key, build, evict_own);
 }
 
 // [bq | 0 | bv] as one f32 bias row (cached like the weights)
 const float * get_qkv_bias(q2a_backend_ctx * b, const ggml_tensor * bq, const ggml_tensor * bv, int N) {
-    const int TAG = -200;
     const char * lo = std::min((const char *) bq->data, (const char *) bv->data);
     const char * hi = std::max((const char *) bq->data + ggml_nbytes(bq), (const char *) bv->data + ggml_nbytes(bv));
-    q2a_device_ctx * d = dev_ctx(b->device);
-    {
-        std::lock_guard<std::mutex> lk(d->mu);
-        for (const packed_w & p : d->wcache)
-            if (p.raw == lo && p.raw_bytes == (size_t) (hi - lo) && p.type == TAG && p.N == 3 * N) return (const float *) p.dev;
-    }
-    packed_w p{};
-    p.raw = lo; p.raw_bytes = (size_t) (hi - lo); p.type = TAG; p.N = 3 * N; p.K = 1;
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    Q2A_HIP(hipMalloc(&p.dev, (size_t) 3 * N * 4));
-    Q2A_HIP(hipMemsetAsync(p.dev, 0, (size_t) 3 * N * 4, b->stream));
-    Q2A_HIP(hipMemcpyAsync(p.dev, bq->data, (size_t) N * 4, hipMemcpyDeviceToDevice, b->stream));
-    Q2A_HIP(hipMemcpyAsync((char *) p.dev + (size_t) 2 * N * 4, bv->data, (size_t) N * 4, hipMemcpyDeviceToDevice, b->stream));
-    Q2A_HIP(hipStreamSynchronize(b->stream));
-    std::lock_guard<std::mutex> lk(d->mu);
-    d->wcache.push_back(p);
-    return (const float *) p.dev;
+    const cache_key key{lo, (size_t) (hi - lo), TAG_QKV_BIAS, 3 * N, 1, true, false};
+    const packed_w row = cache_get(b, key, [&](packed_w & p) {
+        Q2A_HIP(hipMalloc(&p.dev, (size_t) 3 * N * 4));
+        Q2A_HIP(hipMemsetAsync(p.dev, 0, (size_t) 3 * N * 4, b->stream));
+        Q2A_HIP(hipMemcpyAsync(p.dev, bq->data, (size_t) N * 4, hipMemcpyDeviceToDevice, b->stream));
+        Q2A_HIP(hipMemcpyAsync((char *) p.dev + (size_t) 2 * N * 4, bv->data, (size_t) N * 4, hipMemcpyDeviceToDevice, b->stream));
+    });
+    return (const float *) row.dev;
 }
 
-// the operand buffer (zero-filled when it grows: V^T's columns t >= T are read as zero weights)
-char * qkv_buffer(q2a_backend_ctx * b, size_t bytes) {
-    if (bytes > b->qkv_bytes) {
-        abort_capture(b);
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        if (b->qkv_buf) Q2A_HIP(hipFree(b->qkv_buf));
-        b->qkv_buf = nullptr;
-        Q2A_HIP(hipMalloc((void **) &b->qkv_buf, bytes));
-        Q2A_HIP(hipMemsetAsync(b->qkv_buf, 0, bytes, b->stream));
-        Q2A_HIP(hipStreamSynchronize(b->stream));
-        b->qkv_bytes = bytes;
-        drop_graphs(b);
-        resume_discard(b);
-    }
-    return b->qkv_buf;
-}
-
-void run_qkv_fused(q2a_backend_ctx * b, const qkv_route & r, qkv_ops & ops) {
+qkv_ops run_qkv_fused(q2a_backend_ctx * b, const qkv_route & r) {
     const ggml_tensor * x = r.mm[0]->src[1];
     const int K = (int) x->ne[0], M = (int) x->ne[1], D = (int) r.mm[0]->src[0]->ne[1], H = D / 64, T = M;
-    const int TP = (T + 63) / 64 * 64;
     const ggml_tensor * const w[3] = {r.mm[0]->src[0], r.mm[1]->src[0], r.mm[2]->src[0]};
-    const int blk = w[0]->type == GGML_TYPE_Q4_K ? 256 : w[0]->type == GGML_TYPE_F16 ? 0 : 32;
+    const int blk = blk_of_type(w[0]->type);
     const packed_w pw = get_qkv_weight(b, w);
     const float * bias = get_qkv_bias(b, r.bq, r.bv, D);
-    const bool vlo = q2a_attention_wants_vlo();
-    const size_t hb = ((size_t) T * D * 2 + 255) & ~size_t(255);
-    const size_t vb1 = ((size_t) D * TP * 2 + 255) & ~size_t(255);
-    char * ob = qkv_buffer(b, 4 * hb + (vlo ? 2 : 1) * vb1);
-    ops = {(_Float16 *) ob, (_Float16 *) (ob + hb), (_Float16 *) (ob + 2 * hb), (_Float16 *) (ob + 3 * hb),
-           (_Float16 *) (ob + 4 * hb), vlo ? (_Float16 *) (ob + 4 * hb + vb1) : nullptr};
+    const attn_layout L = attn_layout_of(T, D);
+    const int TP = L.TP;
+    // the operand buffer (zero-filled when it grows: V^T's columns t >= T are read as zero weights)
+    char * ob = grow(b, &b->qkv_buf, &b->qkv_bytes, 4 * L.hb + L.vb(), true);
+    const qkv_ops ops = attn_operands(ob, L, (_Float16 *) (ob + 4 * L.hb));
     const act_operand ao = activation_operand(b, x, M, K, blk, 0);
     // (V hi / lo row-major: no pad columns; the attention clamps its key rows to T - 1)
     q2a_gemm_args a;
@@ -1667,20 +1618,7 @@ void run_qkv_fused(q2a_backend_ctx * b, const qkv_route & r, qkv_ops & ops) {
     // (x + b) * s then * log2 e in the unfused path; s = 2^-k makes one multiply by s * log2 e the same rounding
     a.qscale = r.qscale * Q2A_LOG2E;
     a.gelu_tab = gelu_table(b->device);
-    const char * base = (const char *) pw.dev;
-    a.W = (const q2a_half *) (base + pw.off[0]);
-    if (blk) {
-        a.nblk = K / blk;
-        a.dx = (const float *) (base + pw.off[1]);
-        a.dy = ao.dy; a.dy_ld = ao.MP;
-        if (blk == 256) {
-            a.dmin = (const float *) (base + pw.off[2]);
-            a.wext = (const q2a_half *) (base + pw.off[3]);
-            a.beta = (const float *) (base + pw.off[4]);
-            a.gamma = (const float *) (base + pw.off[5]);
-            a.aext = ao.aext;
-        }
-    }
+    set_packed_operand(a, pw, blk, ao);
     Q2A_HIP(q2a_launch_gemm(a, Q2A_EPI_QKV, blk, b->stream));
 #ifdef Q2A_DIAG_DUMP_ATTN   // diagnostic builds only: (acc + bias) * qscale of the same GEMM as f32 -> $Q2A_DUMP_ATTN.q
     static bool qdone = false;
@@ -1701,6 +1639,7 @@ void run_qkv_fused(q2a_backend_ctx * b, const qkv_route & r, qkv_ops & ops) {
         Q2A_HIP(hipFree(y));
     }
 #endif
+    return ops;
 }
 
 bool op_supported(const ggml_tensor * op) {
@@ -1787,525 +1726,584 @@ bool launch_rows(q2a_backend_ctx * b, int op_kind, const ggml_tensor * a, const 
     return true;
 }
 
-ggml_status run_nodes(q2a_backend_ctx * b, ggml_cgraph * g) {
-    static const bool no_fuse = [] { const char * v = getenv("GGML_Q2A_NO_FUSE"); return v && atoi(v); }();
-    b->stats = ggml_backend_q2a_stats{};
-    const int nn = ggml_graph_n_nodes(g);
+// ---- the per-cgraph plan: what run_nodes works out about a cgraph before it runs a node -----------------------------
+bool same_shape_rows(const ggml_tensor * x, const ggml_tensor * y) {
+    for (int k = 0; k < 4; ++k) if (x->ne[k] != y->ne[k]) return false;
+    return ggml_is_contiguous(x) && ggml_is_contiguous(y) && x->type == GGML_TYPE_F32 && y->type == GGML_TYPE_F32;
+}
+bool disjoint(const ggml_tensor * u, const ggml_tensor * v) {
+    return (const char *) u->data + ggml_nbytes(u) <= (const char *) v->data ||
+           (const char *) v->data + ggml_nbytes(v) <= (const char *) u->data;
+}
+
+struct graph_plan {
+    ggml_cgraph * g;
+    int nn;
+    bool no_fuse;   // GGML_Q2A_NO_FUSE=1: every node on its own kernel
+    bool no_qkv;    // GGML_Q2A_NO_FUSED_QKV=1: no fused Q|K|V routes
     // consumers per tensor within this graph: a node is folded into its producer's kernel only when it is the
     // producer's sole consumer (views count as consumers) and the producer is not a graph output
     std::unordered_map<const ggml_tensor *, int> uses;
-    if (!no_fuse) {
-        uses.reserve((size_t) nn * 2);
-        for (int j = 0; j < nn; ++j) {
-            const ggml_tensor * t = ggml_graph_node(g, j);
-            for (int k = 0; k < GGML_MAX_SRC; ++k) if (t->src[k]) uses[t->src[k]]++;
-        }
-    }
-    auto sole = [&](const ggml_tensor * producer, const ggml_tensor * consumer) {
-        if (no_fuse || (producer->flags & GGML_TENSOR_FLAG_OUTPUT)) return false;
-        auto it = uses.find(producer);
-        if (it == uses.end() || it->second != 1) return false;
-        for (int k = 0; k < GGML_MAX_SRC; ++k) if (consumer->src[k] == producer) return true;
-        return false;
-    };
-    auto node = [&](int j) -> ggml_tensor * { return j < nn ? ggml_graph_node(g, j) : nullptr; };
-    auto same_shape_rows = [](const ggml_tensor * x, const ggml_tensor * y) {
-        for (int k = 0; k < 4; ++k) if (x->ne[k] != y->ne[k]) return false;
-        return ggml_is_contiguous(x) && ggml_is_contiguous(y) && x->type == GGML_TYPE_F32 && y->type == GGML_TYPE_F32;
-    };
-    // the SCALE node fed by `prod` (directly or through one contiguous RESHAPE view) at node j, when every link is the
-    // sole consumer of the one before: its bytes are prod's bytes times the scale
-    auto scale_after = [&](ggml_tensor * prod, int j) -> ggml_tensor * {
-        ggml_tensor * t = node(j);
-        if (t && t->op == GGML_OP_RESHAPE && t->src[0] == prod && sole(prod, t)) {
-            prod = t;
-            t = node(j + 1);
-        }
-        if (!t || t->op != GGML_OP_SCALE || t->src[0] != prod || !sole(prod, t) || t->type != GGML_TYPE_F32 ||
-            !ggml_is_contiguous(t) || !ggml_is_contiguous(prod) || ggml_nelements(t) != ggml_nelements(prod) ||
-            ((uintptr_t) t->data & 15) != 0 || *(const float *) t->op_params == 0.0f)
-            return nullptr;
-        return t;
-    };
-    // V CONT nodes feeding a fused attention as its sole consumer: they produce the attention's V^T operand
-    std::unordered_map<const ggml_tensor *, int> vprep;
-    const ggml_tensor * vt_ready_for = nullptr;
     // f32 activations some F16-weight MUL_MAT converts to fp16: their producer also writes the fp16 copy
     std::unordered_map<const ggml_tensor *, int> want16;
+    // V CONT nodes feeding a fused attention as its sole consumer: they produce the attention's V^T operand
+    std::unordered_map<const ggml_tensor *, int> vprep;
+    std::vector<qkv_route> qkv_routes;
+    std::unordered_map<const ggml_tensor *, int> qkv_absorbed;     // nodes a route replaces (its MUL_MATs included) -> route
+
+    explicit graph_plan(ggml_cgraph * graph);
+
+    ggml_tensor * node(int j) const { return j < nn ? ggml_graph_node(g, j) : nullptr; }
+    int n_uses(const ggml_tensor * t) const { const auto it = uses.find(t); return it == uses.end() ? 0 : it->second; }
+    bool sole(const ggml_tensor * producer, const ggml_tensor * consumer) const {
+        if (no_fuse || (producer->flags & GGML_TENSOR_FLAG_OUTPUT) || n_uses(producer) != 1) return false;
+        for (int k = 0; k < GGML_MAX_SRC; ++k) if (consumer->src[k] == producer) return true;
+        return false;
+    }
+};
+
+// what a run of the cgraph changes as it goes
+struct run_state {
+    const ggml_tensor * vt_ready_for = nullptr;                        // the V CONT whose V^T is in vt_buf
+    std::vector<char> qkv_done;                                        // [route] its fused GEMM has run
+    std::unordered_map<const ggml_tensor *, qkv_ops> qkv_ready;        // KQ node -> operands written
+};
+
+// the SCALE node fed by `prod` (directly or through one contiguous RESHAPE view) at node j, when every link is the
+// sole consumer of the one before: its bytes are prod's bytes times the scale
+ggml_tensor * scale_after(const graph_plan & p, ggml_tensor * prod, int j) {
+    ggml_tensor * t = p.node(j);
+    if (t && t->op == GGML_OP_RESHAPE && t->src[0] == prod && p.sole(prod, t)) {
+        prod = t;
+        t = p.node(j + 1);
+    }
+    if (!t || t->op != GGML_OP_SCALE || t->src[0] != prod || !p.sole(prod, t) || t->type != GGML_TYPE_F32 ||
+        !ggml_is_contiguous(t) || !ggml_is_contiguous(prod) || ggml_nelements(t) != ggml_nelements(prod) ||
+        ((uintptr_t) t->data & 15) != 0 || *(const float *) t->op_params == 0.0f)
+        return nullptr;
+    return t;
+}
+
+// Q | K | V projections feeding a fused attention through exactly the reference's views (qwen2-whisper.cpp:
+// 2029-2089): K = PERMUTE(RESHAPE(MUL_MAT)), Q = PERMUTE(SCALE(RESHAPE(ADD(MUL_MAT, bq)))),
+// V = CONT(PERMUTE(RESHAPE(ADD(MUL_MAT, bv)))), every link its producer's sole consumer, the three MUL_MATs on one
+// activation with weights of one type and shape in a weights buffer: one GEMM (run_qkv_fused) then replaces
+// them, and the attention reads its operands from it
+bool match_qkv(const graph_plan & p, ggml_tensor * kq, ggml_tensor * kqv, qkv_route & r,
+               std::vector<const ggml_tensor *> & absorbed) {
+    // one link up a chain: t's source, when t is an `o` node whose sole consumer is `user` (null otherwise)
+    auto up = [&](ggml_tensor * t, ggml_op o, const ggml_tensor * user) -> ggml_tensor * {
+        return t && t->op == o && p.sole(t, user) ? t->src[0] : nullptr;
+    };
+    ggml_tensor * kp = kq->src[0];
+    ggml_tensor * kr = up(kp, GGML_OP_PERMUTE, kq);
+    ggml_tensor * km = up(kr, GGML_OP_RESHAPE, kp);
+    if (!up(km, GGML_OP_MUL_MAT, kr)) return false;
+    ggml_tensor * qp = kq->src[1];
+    ggml_tensor * qs = up(qp, GGML_OP_PERMUTE, kq);
+    ggml_tensor * qr = up(qs, GGML_OP_SCALE, qp);
+    ggml_tensor * qa = up(qr, GGML_OP_RESHAPE, qs);
+    ggml_tensor * qm = up(qa, GGML_OP_ADD, qr);
+    if (!up(qm, GGML_OP_MUL_MAT, qa)) return false;
+    ggml_tensor * vc = kqv->src[0];
+    ggml_tensor * vp = up(vc, GGML_OP_CONT, kqv);
+    ggml_tensor * vr = up(vp, GGML_OP_PERMUTE, vc);
+    ggml_tensor * va = up(vr, GGML_OP_RESHAPE, vp);
+    ggml_tensor * vm = up(va, GGML_OP_ADD, vr);
+    if (!up(vm, GGML_OP_MUL_MAT, va)) return false;
+    const ggml_tensor * x = qm->src[1];
+    const ggml_tensor * wq = qm->src[0];
+    if (km->src[1] != x || vm->src[1] != x) return false;
+    for (const ggml_tensor * m : {qm, km, vm})
+        if (!mm_fast_ok(m) || m->src[0]->type != wq->type || !ggml_are_same_shape(m->src[0], wq) ||
+            !is_weight_buffer(m->src[0]) || ((uintptr_t) m->data & 15) != 0)
+            return false;
+    const int64_t D = wq->ne[1], T = x->ne[1], H = D / 64;
+    // (any T: the fused GEMM writes V row-major, q2a_gemm_args.v_rows — the V^T epilogue's 4-t groups, which needed
+    // T % 4 == 0, are not used on this route)
+    if (wq->ne[0] != D || D % 64 != 0 || x->ne[2] != 1 || x->ne[3] != 1 || T * D >= (1ll << 31)) return false;
+    if (!row_vec_f32(qa->src[1], D) || !row_vec_f32(va->src[1], D) || !is_weight_buffer(qa->src[1]) ||
+        !is_weight_buffer(va->src[1]) || !same_shape_rows(qm, qa) || !same_shape_rows(vm, va))
+        return false;
+    float sc;
+    memcpy(&sc, qs->op_params, 4);
+    int ex;
+    if (!(sc > 0.0f) || frexpf(sc, &ex) != 0.5f || !ggml_is_contiguous(qs) || qs->type != GGML_TYPE_F32) return false;
+    // element (d, t, h) of the K / Q views and (t, d, h) of V's CONT source = row t, column 64 h + d of the
+    // projection (the only layout the epilogue writes)
+    auto hd = [&](const ggml_tensor * v, const ggml_tensor * base, int64_t n0, int64_t s0, int64_t s1) {
+        return v->data == base->data && v->ne[0] == n0 && v->ne[1] == (n0 == 64 ? T : 64) && v->ne[2] == H &&
+               (int64_t) v->nb[0] == s0 && (int64_t) v->nb[1] == s1 && (int64_t) v->nb[2] == 256;
+    };
+    if (!hd(kp, km, 64, 4, D * 4) || !hd(qp, qs, 64, 4, D * 4) || !hd(vp, va, T, D * 4, 4)) return false;
+    if (qr->data != qa->data) return false;
+    r = qkv_route{{qm, km, vm}, qa->src[1], va->src[1], sc, kq};
+    absorbed = {qm, km, vm, qa, qs, va, vc};
+    return true;
+}
+
+graph_plan::graph_plan(ggml_cgraph * graph) : g(graph), nn(ggml_graph_n_nodes(graph)) {
+    static const bool env_no_fuse = env_on("GGML_Q2A_NO_FUSE"), env_no_qkv = env_on("GGML_Q2A_NO_FUSED_QKV");
+    no_fuse = env_no_fuse; no_qkv = env_no_qkv;
+    if (no_fuse) return;
+    uses.reserve((size_t) nn * 2);
+    for (int j = 0; j < nn; ++j) {
+        const ggml_tensor * t = ggml_graph_node(g, j);
+        for (int k = 0; k < GGML_MAX_SRC; ++k) if (t->src[k]) uses[t->src[k]]++;
+        if (t->op == GGML_OP_MUL_MAT && t->src[0]->type == GGML_TYPE_F16 && mm_fast_ok(t)) want16[t->src[1]] = j;
+    }
+    for (int j = 0; j + 2 < nn; ++j) {
+        ggml_tensor * kqv = match_attention(g, j);
+        if (!kqv) continue;
+        ggml_tensor * V = kqv->src[0];
+        if (V->op == GGML_OP_CONT && sole(V, kqv) && V->src[0] && V->src[0]->type == GGML_TYPE_F32 &&
+            ggml_are_same_shape(V, V->src[0]) && V->ne[1] == 64)
+            vprep[V] = j;
+        qkv_route r;
+        std::vector<const ggml_tensor *> ab;
+        if (no_qkv || !match_qkv(*this, ggml_graph_node(g, j), kqv, r, ab)) continue;
+        const int id = (int) qkv_routes.size();
+        qkv_routes.push_back(r);
+        for (const ggml_tensor * t : ab) qkv_absorbed[t] = id;
+    }
+}
+
+// the fast MUL_MAT after node `from` that reads t, when it is t's only consumer (null otherwise)
+const ggml_tensor * sole_mm_consumer(const graph_plan & p, const ggml_tensor * t, int from) {
+    if (p.no_fuse) return nullptr;
+    for (int j = from + 1; j < p.nn; ++j) {
+        const ggml_tensor * n = ggml_graph_node(p.g, j);
+        if (n->op == GGML_OP_MUL_MAT && n->src[1] == t)
+            return p.sole(t, n) && mm_fast_ok(n) && !p.qkv_absorbed.count(n) && !match_attention(p.g, j) ? n : nullptr;
+    }
+    return nullptr;
+}
+
+// the epilogue chain that follows the fast MUL_MAT at node j: MUL_MAT -> ADD(bias row) [-> GELU | -> ADD(residual) |
+// -> [RESHAPE] -> SCALE] on the GEMM epilogue (qwen2-whisper.cpp:2029-2054, 2120-2154): same f32 operations, one
+// kernel, no [N][M] round trips
+mm_chain chain_of(const graph_plan & p, int j) {
+    ggml_tensor * op = ggml_graph_node(p.g, j);
+    mm_chain c{op, Q2A_EPI_STORE_F, nullptr, nullptr, 0.0f, j, 0};
+    ggml_tensor * n1 = p.node(j + 1), * n2 = p.node(j + 2);
+    if (p.no_fuse || !n1 || n1->op != GGML_OP_ADD || n1->src[0] != op || !p.sole(op, n1) ||
+        !row_vec_f32(n1->src[1], op->ne[0]) || !same_shape_rows(op, n1) || ((uintptr_t) n1->data & 15) != 0)
+        return c;
+    c.bias = (const float *) n1->src[1]->data;
+    c.out = n1; c.last = j + 1; c.nfused = 1;
+    if (n2 && n2->op == GGML_OP_UNARY && ggml_get_unary_op(n2) == GGML_UNARY_OP_GELU && n2->src[0] == n1 &&
+        p.sole(n1, n2) && same_shape_rows(n1, n2) && ((uintptr_t) n2->data & 15) == 0 && !mm_is_pipe8(op)) {
+        c.epi = Q2A_EPI_GELU_F; c.out = n2; c.last = j + 2; c.nfused = 2;
+    } else if (ggml_tensor * sc = scale_after(p, n1, j + 2)) {
+        c.oscale = *(const float *) sc->op_params; c.out = sc; c.nfused = 2;
+        c.last = j + 2;
+        while (ggml_graph_node(p.g, c.last) != sc) ++c.last;
+    } else if (n2 && n2->op == GGML_OP_ADD && p.sole(n1, n2) && same_shape_rows(n1, n2) && ((uintptr_t) n2->data & 15) == 0) {
+        const ggml_tensor * r = n2->src[0] == n1 ? n2->src[1] : n2->src[0];
+        if (r != n1 && same_shape_rows(n1, r) && ((uintptr_t) r->data & 15) == 0) {
+            c.epi = Q2A_EPI_RESID; c.resid = (const float *) r->data; c.out = n2; c.last = j + 2; c.nfused = 2;
+        }
+    }
+    return c;
+}
+
+// ---- node handlers: each runs node i, and whatever it folds into it, and returns the last node index it consumed -----
+
+// the first of a fused Q|K|V route's MUL_MATs in node order: the fused GEMM does everything the route replaces
+int run_qkv_node(q2a_backend_ctx * b, const graph_plan & p, run_state & rs, int i) {
+    const int route = p.qkv_absorbed.at(p.node(i));
+    rs.qkv_done[route] = 1;
+    b->stats.n_nodes++;
+    rs.qkv_ready[p.qkv_routes[route].kq] = run_qkv_fused(b, p.qkv_routes[route]);
+    b->stats.n_mul_mat_fast += 3;
+    b->stats.n_mm_grouped++;
+    b->stats.n_fused += 4;   // Q bias, Q scale, V bias, V CONT
+    return i;
+}
+
+// ADD / MUL, SCALE, GELU, SOFT_MAX, IM2COL, POOL_1D: one kernel each. False: not an op of this backend
+bool run_elementwise(q2a_backend_ctx * b, ggml_tensor * op) {
+    const ggml_tensor * s0 = op->src[0];
+    const ggml_tensor * s1 = op->src[1];
+    const int64_t n = ggml_nelements(op);
+    hipStream_t st = b->stream;
+    const int32_t * pp = (const int32_t *) op->op_params;
+    float sc;   // SCALE's and SOFT_MAX's scale
+    memcpy(&sc, op->op_params, 4);
+    switch (op->op) {
+        case GGML_OP_ADD: case GGML_OP_MUL:
+            if (!launch_rows(b, op->op == GGML_OP_ADD ? 0 : 1, s0, op, s1, 1.0f)) {
+                if (op->op == GGML_OP_ADD)
+                    hipLaunchKernelGGL(k_binary<0>, grid1(n), dim3(256), 0, st, tv(s0), tv(s1), tv(op), n);
+                else
+                    hipLaunchKernelGGL(k_binary<1>, grid1(n), dim3(256), 0, st, tv(s0), tv(s1), tv(op), n);
+            }
+            break;
+        case GGML_OP_SCALE:
+            if (!launch_rows(b, 2, s0, op, nullptr, sc))
+                hipLaunchKernelGGL(k_unary<0>, grid1(n), dim3(256), 0, st, tv(s0), tv(op), n, sc, (const uint16_t *) nullptr);
+            break;
+        case GGML_OP_UNARY:
+            if (!launch_rows(b, 3, s0, op, nullptr, 1.0f))
+                hipLaunchKernelGGL(k_unary<1>, grid1(n), dim3(256), 0, st, tv(s0), tv(op), n, 1.0f, gelu_table(b->device));
+            break;
+        case GGML_OP_SOFT_MAX:
+            hipLaunchKernelGGL(k_softmax, dim3((unsigned) ggml_nrows(op)), dim3(256), 0, st, tv(s0), tv(op), sc);
+            break;
+        case GGML_OP_IM2COL:   // (src0 the kernel: only its width is read; src1 the signal)
+            hipLaunchKernelGGL(k_im2col1d, grid1(n), dim3(256), 0, st, tv(s1), tv(op), (int) op->type, (int) s1->ne[1],
+                               (int) s1->ne[0], (int) s0->ne[0], (int) op->ne[1], pp[0], pp[2], pp[4], n);
+            break;
+        case GGML_OP_POOL_1D:
+            hipLaunchKernelGGL(k_pool1d_avg, grid1(n), dim3(256), 0, st, tv(s0), tv(op), (int) pp[1], n);
+            break;
+        default:
+            return false;
+    }
+    b->stats.n_other++;
+    return true;
+}
+
+// ---- NORM [-> MUL(weight row) -> ADD(bias row)] (qwen2-whisper.cpp:2002-2006, 2124-2128, 2176-2180)
+// The LayerNorm output `out` (the ADD at node i + 2) read only by fast MUL_MATs of one weight class (the Q|K|V
+// projections; fc1), with no other GEMM using the scratch before the last of them: the engine's fused LayerNorm can
+// then write their operand instead of the f32 rows. Returns that operand's block size (0 fp16 rows, 256 Q8_K, 32 Q8_0)
+// and in `extra` the scratch bytes the readers' GEMMs need past it, or -1
+int match_norm_operand(const graph_plan & p, int i, const ggml_tensor * s0, const ggml_tensor * out, size_t & extra) {
+    if (p.no_fuse || !ggml_is_contiguous(s0) || !ggml_is_contiguous(out) || (out->flags & GGML_TENSOR_FLAG_OUTPUT)) return -1;
+    const int D = (int) out->ne[0], M = (int) ggml_nrows(out);
+    const int readers = p.n_uses(out);
+    int blk = -1, found = 0, last = -1;
+    extra = 0;
+    for (int j = i + 3; j < p.nn && found < readers; ++j) {
+        const ggml_tensor * c = ggml_graph_node(p.g, j);
+        bool reads = false;
+        for (int k = 0; k < GGML_MAX_SRC; ++k) reads = reads || c->src[k] == out;
+        if (reads) {
+            if (c->op != GGML_OP_MUL_MAT || c->src[1] != out || c->src[0] == out || !mm_fast_ok(c) || match_attention(p.g, j))
+                return -1;
+            const int cb = blk_of_type(c->src[0]->type);
+            if (blk >= 0 && cb != blk) return -1;
+            blk = cb;
+            ++found;
+            last = j;
+            extra = std::max(extra, mm_part_bytes(Q2A_EPI_STORE_F, cb, M, (int) c->src[0]->ne[1], D, false));
+        } else if (c->op == GGML_OP_MUL_MAT && !p.qkv_absorbed.count(c)) {
+            return -1;   // another GEMM (scratch user) between the LayerNorm and its last reader
+        }
+    }
+    return found > 0 && found == readers && last > i && (blk == 0 || D % (blk == 256 ? 256 : 32) == 0) ? blk : -1;
+}
+
+// the engine's fused LayerNorm writing the readers' operand — fp16 rows into a shadow slot, or Q8_K / Q8_0 codes and
+// scales into the scratch — instead of the f32 rows (the same rows: k_norm_row sums like it; q2a_engine.hip run_block)
+void launch_norm_operand(q2a_backend_ctx * b, const ggml_tensor * s0, const ggml_tensor * out, const float * w,
+                         const float * bb, int blk, size_t extra) {
+    const int D = (int) out->ne[0], M = (int) ggml_nrows(out);
+    q2a_ln_args la{(const float *) s0->data, M, D, w, bb, blk == 0 ? 0 : blk == 256 ? 1 : 2, nullptr, nullptr, nullptr, 0};
+    if (blk == 0) {
+        la.outH = (q2a_half *) claim_a16(b, out);
+    } else {
+        const act_operand d = act_slots(b, M, D, blk, extra);
+        la.outH = (q2a_half *) d.A; la.dy = d.dy; la.aext = d.aext; la.dy_ld = d.MP;
+    }
+    Q2A_HIP(q2a_launch_layernorm(la, b->stream));
+    if (blk) { b->quant_src = out; b->quant_blk = blk; }
+}
+
+int run_norm_node(q2a_backend_ctx * b, const graph_plan & p, int i) {
+    ggml_tensor * op = p.node(i);
+    const ggml_tensor * s0 = op->src[0];
+    hipStream_t st = b->stream;
+    float eps;
+    memcpy(&eps, op->op_params, 4);
+    const unsigned rows = (unsigned) ggml_nrows(op);
+    if (op->ne[0] > 2048 || ggml_nrows(op) > (1ll << 31) - 1) {
+        hipLaunchKernelGGL(k_norm, dim3(rows), dim3(256), 0, st, tv(s0), tv(op), eps);
+        b->stats.n_other++;
+        return i;
+    }
+    ggml_tensor * n1 = p.node(i + 1), * n2 = p.node(i + 2);
+    const bool aff = n1 && n2 && n1->op == GGML_OP_MUL && n1->src[0] == op && p.sole(op, n1) &&
+        row_vec_f32(n1->src[1], op->ne[0]) && n2->op == GGML_OP_ADD && n2->src[0] == n1 && p.sole(n1, n2) &&
+        row_vec_f32(n2->src[1], op->ne[0]) && rows_f32(n2) && n1->type == GGML_TYPE_F32 &&
+        ggml_are_same_shape(op, n2);
+    ggml_tensor * out = aff ? n2 : op;
+    const bool v4 = op->ne[0] % 4 == 0 && aligned16(s0) && aligned16(out);
+    const float * w = aff ? (const float *) n1->src[1]->data : nullptr;
+    const float * bb = aff ? (const float *) n2->src[1]->data : nullptr;
+    size_t extra = 0;
+    const int blk = aff && v4 && eps == 1e-5f ? match_norm_operand(p, i, s0, out, extra) : -1;
+    if (blk >= 0) {
+        launch_norm_operand(b, s0, out, w, bb, blk, extra);
+    } else {
+        const dim3 grid((rows + 3) / 4);
+        _Float16 * yh = p.want16.count(out) && ggml_is_contiguous(out) ? claim_a16(b, out) : nullptr;
+        if (aff && v4) hipLaunchKernelGGL((k_norm_row<true, true>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
+        else if (aff) hipLaunchKernelGGL((k_norm_row<true, false>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
+        else if (v4) hipLaunchKernelGGL((k_norm_row<false, true>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
+        else hipLaunchKernelGGL((k_norm_row<false, false>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
+    }
+    if (aff) b->stats.n_fused += 2;
+    b->stats.n_other++;
+    return aff ? i + 2 : i;
+}
+
+// ---- CONT / DUP / CPY
+// The encoder's head and tail (qwen2-whisper.cpp:2004, 2160-2172) start with a CONT of contiguous f32 rows x [R][C]
+// swapped into [C][R] (TRANSPOSE, or PERMUTE 1,0,2,3); `next`, at index j, is the first node past it that executes or reads it
+struct swapped_cont { const ggml_tensor * x; ggml_tensor * next; int j; };
+bool match_swapped_cont(const graph_plan & p, int i, swapped_cont & m) {
+    const ggml_tensor * op = p.node(i);
+    const ggml_tensor * s0 = op->src[0];
+    if (op->op != GGML_OP_CONT || p.no_fuse || p.vprep.count(op) || op->type != GGML_TYPE_F32 || !s0 ||
+        s0->type != GGML_TYPE_F32 || !ggml_is_contiguous(op))
+        return false;
+    const ggml_tensor * x = s0->src[0];
+    const int32_t * ax = (const int32_t *) s0->op_params;
+    const bool swap01 = (s0->op == GGML_OP_TRANSPOSE ||
+                         (s0->op == GGML_OP_PERMUTE && ax[0] == 1 && ax[1] == 0 && ax[2] == 2 && ax[3] == 3)) &&
+                        x && x->type == GGML_TYPE_F32 && ggml_is_contiguous(x) && x->ne[2] == 1 && x->ne[3] == 1 &&
+                        s0->data == x->data && s0->ne[0] == x->ne[1] && s0->ne[1] == x->ne[0];
+    int j = i + 1;
+    while (p.node(j) && is_view_op(p.node(j)) && p.node(j)->src[0] != op) ++j;
+    m = {x, p.node(j), j};
+    return swap01 && m.next;
+}
+
+// CONT(TRANSPOSE(embd_conv)) read only by ADD(positional rows pe, ·): one tiled transpose writes the ADD
+const ggml_tensor * match_head_transpose(const graph_plan & p, const ggml_tensor * op, const swapped_cont & m) {
+    const ggml_tensor * nx = m.next;
+    if (nx->op != GGML_OP_ADD || !p.sole(op, nx) || nx->type != GGML_TYPE_F32 || !ggml_is_contiguous(nx) ||
+        !ggml_are_same_shape(nx, op))
+        return nullptr;
+    const ggml_tensor * pe = nx->src[0] == op ? nx->src[1] : nx->src[0];
+    const bool ok = pe != op && pe->type == GGML_TYPE_F32 && ggml_are_same_shape(pe, op) && pe->nb[0] == 4 &&
+                    pe->nb[1] == (size_t) pe->ne[0] * 4 && nx->src[1] == op && disjoint(nx, m.x) && disjoint(nx, pe);
+    return ok ? pe : nullptr;
+}
+int run_head_transpose(q2a_backend_ctx * b, const swapped_cont & m, const ggml_tensor * pe) {
+    // x [C rows][T] -> next [T rows][C]: R = C, C' = T
+    const int R = (int) m.x->ne[1], Cc = (int) m.x->ne[0];
+    hipLaunchKernelGGL(k_transpose_f32, dim3((unsigned) ((Cc + 63) / 64), (unsigned) ((R + 63) / 64)), dim3(256), 0,
+                       b->stream, (const float *) m.x->data, (float *) m.next->data, R, Cc, nullptr, nullptr,
+                       (const float *) pe->data);
+    b->stats.n_other++;
+    b->stats.n_fused += 1;
+    return m.j;
+}
+
+// CONT(PERMUTE(x)) read only by POOL_1D AVG whose PERMUTE -> CONT restores x's layout: one pass over x's rows,
+// written into that CONT (returned), or — when the allocator gave the CONT x's block (rows read and written by
+// different threads must not overlap) — into the first CONT's own block and copied over
+ggml_tensor * match_tail_pool(const graph_plan & p, const ggml_tensor * op, const swapped_cont & m) {
+    const ggml_tensor * x = m.x;
+    ggml_tensor * nx = m.next;
+    if (nx->op != GGML_OP_POOL_1D || nx->src[0] != op || !p.sole(op, nx)) return nullptr;
+    const int32_t * pp = (const int32_t *) nx->op_params;
+    ggml_tensor * p2 = p.node(m.j + 1), * c2 = p.node(m.j + 2);
+    if (!(pp[0] == GGML_OP_POOL_AVG && pp[1] == pp[2] && pp[3] == 0 && pp[1] >= 1 && nx->type == GGML_TYPE_F32 &&
+          p2 && c2 && p2->op == GGML_OP_PERMUTE && p2->src[0] == nx && p.sole(nx, p2) &&
+          ((const int32_t *) p2->op_params)[0] == 1 && ((const int32_t *) p2->op_params)[1] == 0 &&
+          c2->op == GGML_OP_CONT && c2->src[0] == p2 && p.sole(p2, c2) && c2->type == GGML_TYPE_F32 &&
+          ggml_is_contiguous(c2) && c2->ne[0] == x->ne[0] && c2->ne[1] == x->ne[1] / pp[1] &&
+          c2->ne[2] == 1 && c2->ne[3] == 1))
+        return nullptr;
+    return disjoint(c2, x) || (disjoint(op, x) && disjoint(op, c2)) ? c2 : nullptr;
+}
+int run_tail_pool(q2a_backend_ctx * b, const ggml_tensor * op, const swapped_cont & m, ggml_tensor * out) {
+    const int64_t n = ggml_nelements(out);
+    const bool direct = disjoint(out, m.x);
+    float * dst = (float *) (direct ? out->data : op->data);
+    hipLaunchKernelGGL(k_pool_rows_avg, grid1(n), dim3(256), 0, b->stream, (const float *) m.x->data, dst,
+                       (int) m.x->ne[0], (int) ((const int32_t *) m.next->op_params)[1], n);
+    if (!direct) Q2A_HIP(hipMemcpyAsync(out->data, dst, (size_t) n * 4, hipMemcpyDeviceToDevice, b->stream));
+    b->stats.n_other++;
+    b->stats.n_fused += 2;
+    return m.j + 2;
+}
+
+// V's CONT before a fused attention (qwen2-whisper.cpp:2081-2089): the V^T operand in vt_buf instead of the f32 copy
+void run_vt_tile(q2a_backend_ctx * b, const ggml_tensor * op) {
+    const int T = (int) op->ne[0], H = (int) op->ne[2];
+    const attn_layout L = attn_layout_of(T, (int64_t) H * 64);
+    _Float16 * vt = grow(b, &b->vt_buf, &b->vt_bytes, L.vb());
+    hipLaunchKernelGGL(k_vt_tile, dim3((unsigned) (L.TP / 64), (unsigned) H), dim3(256), 0, b->stream, tv(op->src[0]), vt,
+                       L.vtl(vt), T, L.TP);
+}
+
+int run_copy_node(q2a_backend_ctx * b, const graph_plan & p, run_state & rs, int i) {
+    ggml_tensor * op = p.node(i);
+    const ggml_tensor * s0 = op->src[0];
+    swapped_cont m;
+    if (match_swapped_cont(p, i, m)) {
+        if (const ggml_tensor * pe = match_head_transpose(p, op, m)) return run_head_transpose(b, m, pe);
+        if (ggml_tensor * out = match_tail_pool(p, op, m)) return run_tail_pool(b, op, m, out);
+    }
+    if (p.vprep.count(op) && !rs.vt_ready_for) {
+        // (one pending at a time: a second V before the first attention is copied normally)
+        run_vt_tile(b, op);
+        rs.vt_ready_for = op;
+    } else {
+        ggml_tensor * dst = op->op == GGML_OP_CPY ? op->src[1] : op;
+        const int64_t n = ggml_nelements(op);
+        if (n < (1ll << 31))
+            hipLaunchKernelGGL(k_copy<uint32_t>, grid1(n), dim3(256), 0, b->stream, tv(s0), (int) s0->type, tv(dst), (int) dst->type, n);
+        else
+            hipLaunchKernelGGL(k_copy<int64_t>, grid1(n), dim3(256), 0, b->stream, tv(s0), (int) s0->type, tv(dst), (int) dst->type, n);
+    }
+    b->stats.n_other++;
+    return i;
+}
+
+// ---- MUL_MAT
+// the CONT(PERMUTE(kqv, 0,2,1,3)) at nodes j, j + 1 (qwen2-whisper.cpp:2105-2107), whose [t][h*64+d] rows are
+// exactly the fused attention's output rows (null: something else follows)
+ggml_tensor * match_merged_output(const graph_plan & p, const ggml_tensor * kqv, int j) {
+    ggml_tensor * pm = p.node(j), * c = p.node(j + 1);
+    if (!(pm && c && pm->op == GGML_OP_PERMUTE && pm->src[0] == kqv && p.sole(kqv, pm) && c->op == GGML_OP_CONT &&
+          c->src[0] == pm && p.sole(pm, c)))
+        return nullptr;
+    const int32_t * ax = (const int32_t *) pm->op_params;
+    const bool ok = ax[0] == 0 && ax[1] == 2 && ax[2] == 1 && ax[3] == 3 && c->type == GGML_TYPE_F32 &&
+                    ggml_is_contiguous(c) && c->ne[0] == 64 * kqv->ne[2] && c->ne[1] == kqv->ne[1] &&
+                    c->ne[2] == 1 && c->ne[3] == 1 && ((uintptr_t) c->data & 15) == 0;
+    return ok ? c : nullptr;
+}
+
+// KQ -> SOFT_MAX -> KQV [-> PERMUTE -> CONT] at nodes i.. (match_attention gave kqv) as the fused attention
+int run_attention_node(q2a_backend_ctx * b, const graph_plan & p, run_state & rs, int i, ggml_tensor * kqv) {
+    ggml_tensor * kq = p.node(i);
+    ggml_tensor * merged = match_merged_output(p, kqv, i + 3);
+    const bool vt_ready = kqv->src[0] == rs.vt_ready_for;
+    const auto rd = rs.qkv_ready.find(kq);
+    // the merged rows feeding only an F16 O-projection: written as its fp16 operand directly
+    const ggml_tensor * o_mm = merged ? sole_mm_consumer(p, merged, i + 4) : nullptr;
+    _Float16 * out16 = o_mm && o_mm->src[0]->type == GGML_TYPE_F16 ? claim_a16(b, merged) : nullptr;
+    run_fused_attention(b, kq, kqv, vt_ready, merged, rd != rs.qkv_ready.end() ? &rd->second : nullptr, out16);
+    if (merged) b->stats.n_fused += 1;
+    if (vt_ready) rs.vt_ready_for = nullptr;
+    return merged ? i + 4 : i + 2;
+}
+
+// the conv graph's MUL_MAT -> RESHAPE -> ADD(bias [1][C]) -> GELU (ggml_conv_1d_ph, then qwen2-whisper.cpp's bias
+// add and GELU), every link its producer's sole consumer: one transpose writes the GELU node
+// (returns the GELU node, `last` its index; null: no such chain)
+ggml_tensor * match_conv_bias_gelu(const graph_plan & p, int i, int & last) {
+    if (p.no_fuse) return nullptr;
+    ggml_tensor * op = p.node(i);
+    const int64_t n = ggml_nelements(op);
+    int j = i + 1;
+    ggml_tensor * prod = op;
+    while (p.node(j) && (p.node(j)->op == GGML_OP_RESHAPE || p.node(j)->op == GGML_OP_VIEW) &&
+           p.node(j)->src[0] == prod && p.sole(prod, p.node(j)) && ggml_is_contiguous(p.node(j)) &&
+           p.node(j)->data == op->data && ggml_nelements(p.node(j)) == n)
+        prod = p.node(j++);
+    ggml_tensor * ad = p.node(j), * ge = p.node(j + 1);
+    const ggml_tensor * bs = ad ? ad->src[1] : nullptr;
+    if (!(ad && ge && ad->op == GGML_OP_ADD && ad->src[0] == prod && p.sole(prod, ad) && bs &&
+          bs->type == GGML_TYPE_F32 && ggml_is_contiguous(bs) && bs->ne[0] == 1 && bs->ne[1] == op->ne[1] &&
+          bs->ne[2] == 1 && bs->ne[3] == 1 && ad->type == GGML_TYPE_F32 && ggml_is_contiguous(ad) &&
+          ggml_nelements(ad) == n && ad->ne[0] == op->ne[0] && ad->ne[1] == op->ne[1] &&
+          ge->op == GGML_OP_UNARY && ggml_get_unary_op(ge) == GGML_UNARY_OP_GELU && ge->src[0] == ad &&
+          p.sole(ad, ge) && ge->type == GGML_TYPE_F32 && ggml_is_contiguous(ge) && ggml_are_same_shape(ad, ge)))
+        return nullptr;
+    last = j + 1;
+    return ge;
+}
+int run_conv_node(q2a_backend_ctx * b, const graph_plan & p, int i) {
+    int last = i;
+    ggml_tensor * gelu = match_conv_bias_gelu(p, i, last);
+    run_mm_conv_hilo(b, p.node(i), gelu, gelu ? (const float *) gelu->src[0]->src[1]->data : nullptr);
+    b->stats.n_mul_mat_conv++;
+    b->n_mul_mat_conv_total++;
+    if (gelu) b->stats.n_fused += 2;
+    return last;
+}
+
+// Two consecutive projections of the same activation with plain / bias / bias+scale epilogues (the K and Q
+// projections, qwen2-whisper.cpp:2029-2062) run as one grouped launch: twice the workgroups of either alone.
+// c1: the chain of the MUL_MAT at node i; m2, c2: the second MUL_MAT and its chain
+bool match_grouped_pair(const graph_plan & p, int i, const mm_chain & c1, ggml_tensor *& m2, mm_chain & c2) {
+    const ggml_tensor * op = p.node(i);
+    int j2 = c1.last + 1;   // the next node that executes (views in between are free)
+    while (p.node(j2) && is_view_op(p.node(j2))) ++j2;
+    m2 = p.node(j2);
+    if (!(c1.epi == Q2A_EPI_STORE_F && !p.no_fuse && m2 && m2->op == GGML_OP_MUL_MAT && m2->src[1] == op->src[1] &&
+          (op->src[0]->type == GGML_TYPE_F16 || op->src[0]->type == GGML_TYPE_Q4_K) &&
+          m2->src[0]->type == op->src[0]->type && mm_fast_ok(m2) &&
+          !match_attention(p.g, j2) && ggml_are_same_shape(m2->src[0], op->src[0]) && !mm_is_pipe8(op)))
+        return false;
+    c2 = chain_of(p, j2);
+    return c2.epi == Q2A_EPI_STORE_F;
+}
+
+// a fast MUL_MAT and its epilogue chain: grouped with the next projection, as fc1 writing fc2's operand
+// (run_fc1_for_fc2), or on its own
+int run_mm_fast_node(q2a_backend_ctx * b, const graph_plan & p, int i) {
+    ggml_tensor * op = p.node(i);
+    const mm_chain c1 = chain_of(p, i);
+    ggml_tensor * m2;
+    mm_chain c2;
+    if (match_grouped_pair(p, i, c1, m2, c2)) {
+        run_mm_fast(b, op, c1, nullptr, m2->src[0], &c2);
+        b->stats.n_fused += c1.nfused + c2.nfused;
+        b->stats.n_mul_mat_fast += 2;
+        b->stats.n_mm_grouped++;
+        return c2.last;
+    }
+    const bool gelu_rows = c1.epi == Q2A_EPI_GELU_F && ggml_is_contiguous(c1.out);
+    if (const ggml_tensor * fc2 = gelu_rows ? sole_mm_consumer(p, c1.out, c1.last) : nullptr) {
+        run_fc1_for_fc2(b, op, c1, fc2);
+    } else {
+        _Float16 * out16 = gelu_rows && p.want16.count(c1.out) ? claim_a16(b, c1.out) : nullptr;
+        run_mm_fast(b, op, c1, out16);
+    }
+    b->stats.n_fused += c1.nfused;
+    b->stats.n_mul_mat_fast++;
+    return c1.last;
+}
+
+int run_mul_mat_node(q2a_backend_ctx * b, const graph_plan & p, run_state & rs, int i) {
+    ggml_tensor * op = p.node(i);
+    if (ggml_tensor * kqv = match_attention(p.g, i)) return run_attention_node(b, p, rs, i, kqv);
+    if (mm_fast_ok(op)) return run_mm_fast_node(b, p, i);
+    if (conv_f64_diag(op)) { run_mm_conv_f64(b, op); b->stats.n_mul_mat_conv++; return i; }
+    if (conv_hilo_ok(op)) return run_conv_node(b, p, i);
+    run_mm_f32(b, op);
+    b->stats.n_mul_mat_f32++;
+    return i;
+}
+
+ggml_status run_nodes(q2a_backend_ctx * b, ggml_cgraph * g) {
+    b->stats = ggml_backend_q2a_stats{};
     b->a16_src[0] = b->a16_src[1] = nullptr;
     b->a16_last = 1;   // slot assignment deterministic per cgraph: a replayed capture sees the same slots as its run
     b->quant_src = nullptr;
-    if (!no_fuse) {
-        for (int j = 0; j < nn; ++j) {
-            const ggml_tensor * t = ggml_graph_node(g, j);
-            if (t->op == GGML_OP_MUL_MAT && t->src[0]->type == GGML_TYPE_F16 && mm_fast_ok(t)) want16[t->src[1]] = j;
-        }
-        for (int j = 0; j + 2 < nn; ++j) {
-            ggml_tensor * kqv = match_attention(g, j);
-            if (!kqv) continue;
-            ggml_tensor * V = kqv->src[0];
-            if (V->op == GGML_OP_CONT && sole(V, kqv) && V->src[0] && V->src[0]->type == GGML_TYPE_F32 &&
-                ggml_are_same_shape(V, V->src[0]) && V->ne[1] == 64)
-                vprep[V] = j;
-        }
-    }
-    // Q | K | V projections feeding a fused attention through exactly the reference's views (qwen2-whisper.cpp:
-    // 2029-2089): K = PERMUTE(RESHAPE(MUL_MAT)), Q = PERMUTE(SCALE(RESHAPE(ADD(MUL_MAT, bq)))),
-    // V = CONT(PERMUTE(RESHAPE(ADD(MUL_MAT, bv)))), every link its producer's sole consumer, the three MUL_MATs on one
-    // activation with weights of one type and shape in a weights buffer: one GEMM (run_qkv_fused) then replaces
-    // them, and the attention reads its operands from it
-    static const bool no_qkv = [] { const char * v = getenv("GGML_Q2A_NO_FUSED_QKV"); return v && atoi(v); }();
-    auto match_qkv = [&](ggml_tensor * kq, ggml_tensor * kqv, qkv_route & r, std::vector<const ggml_tensor *> & absorbed) {
-        auto is = [](const ggml_tensor * t, ggml_op o) { return t && t->op == o; };
-        ggml_tensor * kp = kq->src[0];
-        if (!is(kp, GGML_OP_PERMUTE) || !sole(kp, kq)) return false;
-        ggml_tensor * kr = kp->src[0];
-        if (!is(kr, GGML_OP_RESHAPE) || !sole(kr, kp)) return false;
-        ggml_tensor * km = kr->src[0];
-        if (!is(km, GGML_OP_MUL_MAT) || !sole(km, kr)) return false;
-        ggml_tensor * qp = kq->src[1];
-        if (!is(qp, GGML_OP_PERMUTE) || !sole(qp, kq)) return false;
-        ggml_tensor * qs = qp->src[0];
-        if (!is(qs, GGML_OP_SCALE) || !sole(qs, qp)) return false;
-        ggml_tensor * qr = qs->src[0];
-        if (!is(qr, GGML_OP_RESHAPE) || !sole(qr, qs)) return false;
-        ggml_tensor * qa = qr->src[0];
-        if (!is(qa, GGML_OP_ADD) || !sole(qa, qr)) return false;
-        ggml_tensor * qm = qa->src[0];
-        if (!is(qm, GGML_OP_MUL_MAT) || !sole(qm, qa)) return false;
-        ggml_tensor * vc = kqv->src[0];
-        if (!is(vc, GGML_OP_CONT) || !sole(vc, kqv)) return false;
-        ggml_tensor * vp = vc->src[0];
-        if (!is(vp, GGML_OP_PERMUTE) || !sole(vp, vc)) return false;
-        ggml_tensor * vr = vp->src[0];
-        if (!is(vr, GGML_OP_RESHAPE) || !sole(vr, vp)) return false;
-        ggml_tensor * va = vr->src[0];
-        if (!is(va, GGML_OP_ADD) || !sole(va, vr)) return false;
-        ggml_tensor * vm = va->src[0];
-        if (!is(vm, GGML_OP_MUL_MAT) || !sole(vm, va)) return false;
-        const ggml_tensor * x = qm->src[1];
-        const ggml_tensor * wq = qm->src[0];
-        if (km->src[1] != x || vm->src[1] != x) return false;
-        for (const ggml_tensor * m : {qm, km, vm})
-            if (!mm_fast_ok(m) || m->src[0]->type != wq->type || !ggml_are_same_shape(m->src[0], wq) ||
-                !is_weight_buffer(m->src[0]) || ((uintptr_t) m->data & 15) != 0)
-                return false;
-        const int64_t D = wq->ne[1], T = x->ne[1], H = D / 64;
-        // (any T: the fused GEMM writes V row-major, q2a_gemm_args.v_rows — the V^T epilogue's 4-t groups, which needed
-        // T % 4 == 0, are not used on this route)
-        if (wq->ne[0] != D || D % 64 != 0 || x->ne[2] != 1 || x->ne[3] != 1 || T * D >= (1ll << 31)) return false;
-        if (!row_vec_f32(qa->src[1], D) || !row_vec_f32(va->src[1], D) || !is_weight_buffer(qa->src[1]) ||
-            !is_weight_buffer(va->src[1]) || !same_shape_rows(qm, qa) || !same_shape_rows(vm, va))
-            return false;
-        float sc;
-        memcpy(&sc, qs->op_params, 4);
-        int ex;
-        if (!(sc > 0.0f) || frexpf(sc, &ex) != 0.5f || !ggml_is_contiguous(qs) || qs->type != GGML_TYPE_F32) return false;
-        // element (d, t, h) of the K / Q views and (t, d, h) of V's CONT source = row t, column 64 h + d of the
-        // projection (the only layout the epilogue writes)
-        auto hd = [&](const ggml_tensor * v, const ggml_tensor * base, int64_t n0, int64_t s0, int64_t s1) {
-            return v->data == base->data && v->ne[0] == n0 && v->ne[1] == (n0 == 64 ? T : 64) && v->ne[2] == H &&
-                   (int64_t) v->nb[0] == s0 && (int64_t) v->nb[1] == s1 && (int64_t) v->nb[2] == 256;
-        };
-        if (!hd(kp, km, 64, 4, D * 4) || !hd(qp, qs, 64, 4, D * 4) || !hd(vp, va, T, D * 4, 4)) return false;
-        if (qr->data != qa->data) return false;
-        r = qkv_route{{qm, km, vm}, qa->src[1], va->src[1], sc};
-        absorbed = {qm, km, vm, qa, qs, va, vc};
-        return true;
-    };
-    std::vector<qkv_route> qkv_routes;
-    std::vector<const ggml_tensor *> qkv_route_kq;                         // [route] its attention's KQ node
-    std::unordered_map<const ggml_tensor *, int> qkv_mm;                   // Q / K / V MUL_MAT -> route
-    std::unordered_map<const ggml_tensor *, int> qkv_absorbed;             // nodes a route replaces -> route
-    std::vector<char> qkv_done;
-    std::unordered_map<const ggml_tensor *, qkv_ops> qkv_ready;            // KQ node -> operands written
-    if (!no_fuse && !no_qkv) {
-        for (int j = 0; j + 2 < nn; ++j) {
-            ggml_tensor * kqv = match_attention(g, j);
-            if (!kqv) continue;
-            qkv_route r;
-            std::vector<const ggml_tensor *> ab;
-            if (!match_qkv(ggml_graph_node(g, j), kqv, r, ab)) continue;
-            const int id = (int) qkv_routes.size();
-            qkv_routes.push_back(r);
-            qkv_route_kq.push_back(ggml_graph_node(g, j));
-            for (int k = 0; k < 3; ++k) qkv_mm[r.mm[k]] = id;
-            for (const ggml_tensor * t : ab) qkv_absorbed[t] = id;
-        }
-        qkv_done.assign(qkv_routes.size(), 0);
-    }
-    // the fast MUL_MAT after node `from` that reads t, when it is t's only consumer (null otherwise)
-    auto sole_mm_consumer = [&](const ggml_tensor * t, int from) -> const ggml_tensor * {
-        if (no_fuse) return nullptr;
-        for (int j = from + 1; j < nn; ++j) {
-            const ggml_tensor * n = ggml_graph_node(g, j);
-            if (n->op == GGML_OP_MUL_MAT && n->src[1] == t)
-                return sole(t, n) && mm_fast_ok(n) && !qkv_mm.count(n) && !match_attention(g, j) ? n : nullptr;
-        }
-        return nullptr;
-    };
-    // the epilogue chain that follows the fast MUL_MAT at node j (see the MUL_MAT case)
-    auto chain_of = [&](int j) -> mm_chain {
-        ggml_tensor * op = ggml_graph_node(g, j);
-        mm_chain c{op, Q2A_EPI_STORE_F, nullptr, nullptr, 0.0f, j, 0};
-        ggml_tensor * n1 = node(j + 1), * n2 = node(j + 2);
-        if (no_fuse || !n1 || n1->op != GGML_OP_ADD || n1->src[0] != op || !sole(op, n1) ||
-            !row_vec_f32(n1->src[1], op->ne[0]) || !same_shape_rows(op, n1) || ((uintptr_t) n1->data & 15) != 0)
-            return c;
-        c.bias = (const float *) n1->src[1]->data;
-        c.out = n1; c.last = j + 1; c.nfused = 1;
-        if (n2 && n2->op == GGML_OP_UNARY && ggml_get_unary_op(n2) == GGML_UNARY_OP_GELU && n2->src[0] == n1 &&
-            sole(n1, n2) && same_shape_rows(n1, n2) && ((uintptr_t) n2->data & 15) == 0 && !mm_is_pipe8(op)) {
-            c.epi = Q2A_EPI_GELU_F; c.out = n2; c.last = j + 2; c.nfused = 2;
-        } else if (ggml_tensor * sc = scale_after(n1, j + 2)) {
-            c.oscale = *(const float *) sc->op_params; c.out = sc; c.nfused = 2;
-            c.last = j + 2;
-            while (ggml_graph_node(g, c.last) != sc) ++c.last;
-        } else if (n2 && n2->op == GGML_OP_ADD && sole(n1, n2) && same_shape_rows(n1, n2) && ((uintptr_t) n2->data & 15) == 0) {
-            const ggml_tensor * r = n2->src[0] == n1 ? n2->src[1] : n2->src[0];
-            if (r != n1 && same_shape_rows(n1, r) && ((uintptr_t) r->data & 15) == 0) {
-                c.epi = Q2A_EPI_RESID; c.resid = (const float *) r->data; c.out = n2; c.last = j + 2; c.nfused = 2;
-            }
-        }
-        return c;
-    };
-    for (int i = 0; i < nn; ++i) {
+    const graph_plan p(g);
+    run_state rs;
+    rs.qkv_done.assign(p.qkv_routes.size(), 0);
+    for (int i = 0; i < p.nn; ++i) {
         if (b->capture_aborted) return GGML_STATUS_SUCCESS;   // graph_compute re-runs the whole cgraph directly
-        ggml_tensor * op = ggml_graph_node(g, i);
-        if (ggml_is_empty(op) || op->op == GGML_OP_NONE || op->op == GGML_OP_RESHAPE || op->op == GGML_OP_VIEW ||
-            op->op == GGML_OP_PERMUTE || op->op == GGML_OP_TRANSPOSE)
-            continue;
-        if (!qkv_absorbed.empty()) {
-            const auto ab = qkv_absorbed.find(op);
-            if (ab != qkv_absorbed.end()) {
-                // the first of a route's MUL_MATs in node order runs the fused GEMM; everything else it replaces is done
-                if (qkv_mm.count(op) && !qkv_done[ab->second]) {
-                    qkv_done[ab->second] = 1;
-                    b->stats.n_nodes++;
-                    qkv_ops ops;
-                    run_qkv_fused(b, qkv_routes[ab->second], ops);
-                    qkv_ready[qkv_route_kq[ab->second]] = ops;
-                    b->stats.n_mul_mat_fast += 3;
-                    b->stats.n_mm_grouped++;
-                    b->stats.n_fused += 4;   // Q bias, Q scale, V bias, V CONT
-                    const hipError_t e = hipGetLastError();
-                    if (e != hipSuccess) {
-                        Q2A_LOG_ERROR("ggml-q2a: fused Q|K|V (%s) launch failed: %s\n", op->name, hipGetErrorString(e));
+        ggml_tensor * op = p.node(i);
+        if (is_view_op(op)) continue;
+        const auto ab = p.qkv_absorbed.find(op);
+        if (ab != p.qkv_absorbed.end()) {
+            // the first of a route's MUL_MATs in node order runs the fused GEMM; everything else it replaces is done
+            if (op->op != GGML_OP_MUL_MAT || rs.qkv_done[ab->second]) continue;
+            i = run_qkv_node(b, p, rs, i);
+        } else {
+            b->stats.n_nodes++;
+            switch (op->op) {
+                case GGML_OP_MUL_MAT: i = run_mul_mat_node(b, p, rs, i); break;
+                case GGML_OP_NORM: i = run_norm_node(b, p, i); break;
+                case GGML_OP_CONT: case GGML_OP_DUP: case GGML_OP_CPY: i = run_copy_node(b, p, rs, i); break;
+                default:
+                    if (!run_elementwise(b, op)) {
+                        Q2A_LOG_ERROR("ggml-q2a: unsupported op %s (%s)\n", ggml_op_desc(op), op->name);
                         return GGML_STATUS_FAILED;
                     }
-                }
-                continue;
             }
-        }
-        b->stats.n_nodes++;
-        const ggml_tensor * s0 = op->src[0];
-        const ggml_tensor * s1 = op->src[1];
-        const int64_t n = ggml_nelements(op);
-        hipStream_t st = b->stream;
-        switch (op->op) {
-            case GGML_OP_MUL_MAT: {
-                if (ggml_tensor * kqv = match_attention(g, i)) {
-                    ggml_tensor * merged = nullptr;
-                    ggml_tensor * p = node(i + 3), * c = node(i + 4);
-                    if (p && c && p->op == GGML_OP_PERMUTE && p->src[0] == kqv && sole(kqv, p) && c->op == GGML_OP_CONT &&
-                        c->src[0] == p && sole(p, c)) {
-                        const int32_t * ax = (const int32_t *) p->op_params;
-                        if (ax[0] == 0 && ax[1] == 2 && ax[2] == 1 && ax[3] == 3 && c->type == GGML_TYPE_F32 &&
-                            ggml_is_contiguous(c) && c->ne[0] == 64 * kqv->ne[2] && c->ne[1] == kqv->ne[1] &&
-                            c->ne[2] == 1 && c->ne[3] == 1 && ((uintptr_t) c->data & 15) == 0)
-                            merged = c;
-                    }
-                    const bool vt_ready = kqv->src[0] == vt_ready_for;
-                    const auto rd = qkv_ready.find(op);
-                    // the merged rows feeding only an F16 O-projection: written as its fp16 operand directly
-                    const ggml_tensor * o_mm = merged ? sole_mm_consumer(merged, i + 4) : nullptr;
-                    _Float16 * out16 = o_mm && o_mm->src[0]->type == GGML_TYPE_F16 ? claim_a16(b, merged) : nullptr;
-                    const int used = run_fused_attention(b, g, i, vt_ready, merged, rd != qkv_ready.end() ? &rd->second : nullptr,
-                                                         out16);
-                    if (merged) b->stats.n_fused += 1;
-                    if (vt_ready) vt_ready_for = nullptr;
-                    i += used - 1;
-                    break;
-                }
-                if (!mm_fast_ok(op) && conv_f64_diag(op)) { run_mm_conv_f64(b, op); b->stats.n_mul_mat_conv++; break; }
-                if (!mm_fast_ok(op) && conv_hilo_ok(op)) {
-                    // the conv graph's MUL_MAT -> RESHAPE -> ADD(bias [1][C]) -> GELU (ggml_conv_1d_ph, then
-                    // qwen2-whisper.cpp's bias add and GELU), every link its producer's sole consumer: one transpose
-                    // writes the GELU node
-                    int last = i;
-                    ggml_tensor * gout = nullptr;
-                    const float * cbias = nullptr;
-                    if (!no_fuse) {
-                        int j = i + 1;
-                        ggml_tensor * prod = op;
-                        while (node(j) && (node(j)->op == GGML_OP_RESHAPE || node(j)->op == GGML_OP_VIEW) &&
-                               node(j)->src[0] == prod && sole(prod, node(j)) && ggml_is_contiguous(node(j)) &&
-                               node(j)->data == op->data && ggml_nelements(node(j)) == n)
-                            prod = node(j++);
-                        ggml_tensor * ad = node(j), * ge = node(j + 1);
-                        const ggml_tensor * bs = ad ? ad->src[1] : nullptr;
-                        if (ad && ge && ad->op == GGML_OP_ADD && ad->src[0] == prod && sole(prod, ad) && bs &&
-                            bs->type == GGML_TYPE_F32 && ggml_is_contiguous(bs) && bs->ne[0] == 1 && bs->ne[1] == op->ne[1] &&
-                            bs->ne[2] == 1 && bs->ne[3] == 1 && ad->type == GGML_TYPE_F32 && ggml_is_contiguous(ad) &&
-                            ggml_nelements(ad) == n && ad->ne[0] == op->ne[0] && ad->ne[1] == op->ne[1] &&
-                            ge->op == GGML_OP_UNARY && ggml_get_unary_op(ge) == GGML_UNARY_OP_GELU && ge->src[0] == ad &&
-                            sole(ad, ge) && ge->type == GGML_TYPE_F32 && ggml_is_contiguous(ge) && ggml_are_same_shape(ad, ge)) {
-                            gout = ge;
-                            cbias = (const float *) bs->data;
-                            last = j + 1;
-                        }
-                    }
-                    run_mm_conv_hilo(b, op, gout, cbias);
-                    b->stats.n_mul_mat_conv++;
-                    b->n_mul_mat_conv_total++;
-                    if (gout) b->stats.n_fused += 2;
-                    i = last;
-                    break;
-                }
-                if (!mm_fast_ok(op)) { run_mm_f32(b, op); b->stats.n_mul_mat_f32++; break; }
-                // MUL_MAT -> ADD(bias row) [-> GELU | -> ADD(residual) | -> [RESHAPE] -> SCALE] on the GEMM epilogue
-                // (qwen2-whisper.cpp:2029-2054, 2120-2154): same f32 operations, one kernel, no [N][M] round trips
-                mm_chain c1 = chain_of(i);
-                // two consecutive projections of the same activation with plain / bias / bias+scale epilogues (the K
-                // and Q projections, :2029-2062) run as one grouped launch: twice the workgroups of either alone
-                int j2 = c1.last + 1;   // the next node that executes (views in between are free)
-                while (node(j2) && is_view_op(node(j2))) ++j2;
-                ggml_tensor * m2 = node(j2);
-                if (c1.epi == Q2A_EPI_STORE_F && !no_fuse && m2 && m2->op == GGML_OP_MUL_MAT && m2->src[1] == op->src[1] &&
-                    (op->src[0]->type == GGML_TYPE_F16 || op->src[0]->type == GGML_TYPE_Q4_K) &&
-                    m2->src[0]->type == op->src[0]->type && mm_fast_ok(m2) &&
-                    !match_attention(g, j2) && ggml_are_same_shape(m2->src[0], op->src[0]) && !mm_is_pipe8(op)) {
-                    const mm_chain c2 = chain_of(j2);
-                    if (c2.epi == Q2A_EPI_STORE_F) {
-                        mm_second sec{m2->src[0], c2.out, c2.bias, c2.oscale};
-                        run_mm_fast(b, op, c1.out, Q2A_EPI_STORE_F, c1.bias, nullptr, c1.oscale, nullptr, &sec);
-                        b->stats.n_fused += c1.nfused + c2.nfused;
-                        b->stats.n_mul_mat_fast += 2;
-                        b->stats.n_mm_grouped++;
-                        i = c2.last;
-                        break;
-                    }
-                }
-                if (c1.epi == Q2A_EPI_GELU_F && ggml_is_contiguous(c1.out)) {
-                    if (const ggml_tensor * f2 = sole_mm_consumer(c1.out, c1.last)) {
-                        run_fc1_for_fc2(b, op, c1, f2);
-                        b->stats.n_fused += c1.nfused;
-                        b->stats.n_mul_mat_fast++;
-                        i = c1.last;
-                        break;
-                    }
-                }
-                _Float16 * out16 = c1.epi == Q2A_EPI_GELU_F && want16.count(c1.out) && ggml_is_contiguous(c1.out)
-                                       ? claim_a16(b, c1.out) : nullptr;
-                run_mm_fast(b, op, c1.out, c1.epi, c1.bias, c1.resid, c1.oscale, out16);
-                b->stats.n_fused += c1.nfused;
-                b->stats.n_mul_mat_fast++;
-                i = c1.last;
-                break;
-            }
-            case GGML_OP_ADD: case GGML_OP_MUL:
-                if (!launch_rows(b, op->op == GGML_OP_ADD ? 0 : 1, s0, op, s1, 1.0f)) {
-                    if (op->op == GGML_OP_ADD)
-                        hipLaunchKernelGGL(k_binary<0>, grid1(n), dim3(256), 0, st, tv(s0), tv(s1), tv(op), n);
-                    else
-                        hipLaunchKernelGGL(k_binary<1>, grid1(n), dim3(256), 0, st, tv(s0), tv(s1), tv(op), n);
-                }
-                b->stats.n_other++;
-                break;
-            case GGML_OP_SCALE: {
-                float sc;
-                memcpy(&sc, op->op_params, 4);
-                if (!launch_rows(b, 2, s0, op, nullptr, sc))
-                    hipLaunchKernelGGL(k_unary<0>, grid1(n), dim3(256), 0, st, tv(s0), tv(op), n, sc, (const uint16_t *) nullptr);
-                b->stats.n_other++;
-                break;
-            }
-            case GGML_OP_UNARY:
-                if (!launch_rows(b, 3, s0, op, nullptr, 1.0f))
-                    hipLaunchKernelGGL(k_unary<1>, grid1(n), dim3(256), 0, st, tv(s0), tv(op), n, 1.0f, gelu_table(b->device));
-                b->stats.n_other++;
-                break;
-            case GGML_OP_NORM: {
-                float eps;
-                memcpy(&eps, op->op_params, 4);
-                const unsigned rows = (unsigned) ggml_nrows(op);
-                if (op->ne[0] > 2048 || ggml_nrows(op) > (1ll << 31) - 1) {
-                    hipLaunchKernelGGL(k_norm, dim3(rows), dim3(256), 0, st, tv(s0), tv(op), eps);
-                    b->stats.n_other++;
-                    break;
-                }
-                // NORM -> MUL(weight row) -> ADD(bias row) (qwen2-whisper.cpp:2002-2006, 2124-2128, 2176-2180)
-                ggml_tensor * n1 = node(i + 1), * n2 = node(i + 2);
-                const bool aff = n1 && n2 && n1->op == GGML_OP_MUL && n1->src[0] == op && sole(op, n1) &&
-                    row_vec_f32(n1->src[1], op->ne[0]) && n2->op == GGML_OP_ADD && n2->src[0] == n1 && sole(n1, n2) &&
-                    row_vec_f32(n2->src[1], op->ne[0]) && rows_f32(n2) && n1->type == GGML_TYPE_F32 &&
-                    ggml_are_same_shape(op, n2);
-                ggml_tensor * out = aff ? n2 : op;
-                const bool v4 = op->ne[0] % 4 == 0 && aligned16(s0) && aligned16(out);
-                const float * w = aff ? (const float *) n1->src[1]->data : nullptr;
-                const float * bb = aff ? (const float *) n2->src[1]->data : nullptr;
-                // rows read only by fast MUL_MATs of one weight class (the Q|K|V projections; fc1): the engine's fused
-                // LayerNorm writes their operand — fp16 rows, or Q8_K / Q8_0 codes and scales in the scratch —
-                // instead of the f32 rows (the same rows: k_norm_row sums like it; q2a_engine.hip run_block)
-                if (aff && v4 && eps == 1e-5f && !no_fuse && ggml_is_contiguous(s0) && ggml_is_contiguous(out) &&
-                    !(out->flags & GGML_TENSOR_FLAG_OUTPUT)) {
-                    const int D = (int) op->ne[0], M = (int) rows;
-                    int blk = -1, found = 0, last = -1;
-                    size_t extra = 0;
-                    bool ok = true;
-                    for (int j = i + 3; j < nn && ok; ++j) {
-                        const ggml_tensor * c = ggml_graph_node(g, j);
-                        bool reads = false;
-                        for (int k = 0; k < GGML_MAX_SRC; ++k) reads = reads || c->src[k] == out;
-                        if (reads) {
-                            if (c->op != GGML_OP_MUL_MAT || c->src[1] != out || c->src[0] == out || !mm_fast_ok(c) ||
-                                match_attention(g, j)) { ok = false; break; }
-                            const int cb = blk_of_type(c->src[0]->type);
-                            if (blk >= 0 && cb != blk) { ok = false; break; }
-                            blk = cb;
-                            ++found;
-                            last = j;
-                            extra = std::max(extra, mm_part_bytes(Q2A_EPI_STORE_F, cb, M, (int) c->src[0]->ne[1], D, false));
-                        } else if (found < (uses.count(out) ? uses[out] : 0) && c->op == GGML_OP_MUL_MAT && !qkv_absorbed.count(c)) {
-                            ok = false;   // another GEMM (scratch user) between the LayerNorm and its last reader
-                        }
-                        if (found == (uses.count(out) ? uses[out] : 0)) break;
-                    }
-                    if (ok && found > 0 && found == uses[out] && last > i && (blk == 0 || D % (blk == 256 ? 256 : 32) == 0)) {
-                        q2a_ln_args la{(const float *) s0->data, M, D, w, bb, blk == 0 ? 0 : blk == 256 ? 1 : 2, nullptr, nullptr, nullptr, 0};
-                        if (blk == 0) {
-                            la.outH = (q2a_half *) claim_a16(b, out);
-                        } else {
-                            const act_operand d = act_slots(b, M, D, blk, extra);
-                            la.outH = (q2a_half *) d.A; la.dy = d.dy; la.aext = d.aext; la.dy_ld = d.MP;
-                        }
-                        Q2A_HIP(q2a_launch_layernorm(la, st));
-                        if (blk) { b->quant_src = out; b->quant_blk = blk; }
-                        b->stats.n_fused += 2;
-                        b->stats.n_other++;
-                        i += 2;
-                        break;
-                    }
-                }
-                const dim3 grid((rows + 3) / 4);
-                _Float16 * yh = want16.count(out) && ggml_is_contiguous(out) ? claim_a16(b, out) : nullptr;
-                if (aff && v4) hipLaunchKernelGGL((k_norm_row<true, true>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
-                else if (aff) hipLaunchKernelGGL((k_norm_row<true, false>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
-                else if (v4) hipLaunchKernelGGL((k_norm_row<false, true>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
-                else hipLaunchKernelGGL((k_norm_row<false, false>), grid, dim3(256), 0, st, tv(s0), tv(out), eps, w, bb, (int) rows, yh);
-                if (aff) {
-                    b->stats.n_fused += 2;
-                    i += 2;
-                }
-                b->stats.n_other++;
-                break;
-            }
-            case GGML_OP_SOFT_MAX: {
-                float sc;
-                memcpy(&sc, op->op_params, 4);
-                hipLaunchKernelGGL(k_softmax, dim3((unsigned) ggml_nrows(op)), dim3(256), 0, st, tv(s0), tv(op), sc);
-                b->stats.n_other++;
-                break;
-            }
-            case GGML_OP_CONT: case GGML_OP_DUP: case GGML_OP_CPY: {
-                // the encoder's head and tail (qwen2-whisper.cpp:2004, 2160-2172): CONT(TRANSPOSE(embd_conv)) read only
-                // by ADD(positional rows, ·) -> one tiled transpose writing the ADD; CONT(PERMUTE(x)) read only by
-                // POOL_1D AVG whose PERMUTE -> CONT restores x's layout -> one pass over x's rows, written into that
-                // CONT, or — when the allocator gave the CONT x's block (rows read and written by different threads
-                // must not overlap) — into the first CONT's own block and copied over
-                if (op->op == GGML_OP_CONT && !no_fuse && !vprep.count(op) && op->type == GGML_TYPE_F32 && s0 &&
-                    s0->type == GGML_TYPE_F32 && ggml_is_contiguous(op)) {
-                    const ggml_tensor * x = s0->src[0];
-                    const bool swap01 = (s0->op == GGML_OP_TRANSPOSE ||
-                                         (s0->op == GGML_OP_PERMUTE && ((const int32_t *) s0->op_params)[0] == 1 &&
-                                          ((const int32_t *) s0->op_params)[1] == 0 && ((const int32_t *) s0->op_params)[2] == 2 &&
-                                          ((const int32_t *) s0->op_params)[3] == 3)) &&
-                                        x && x->type == GGML_TYPE_F32 && ggml_is_contiguous(x) && x->ne[2] == 1 && x->ne[3] == 1 &&
-                                        s0->data == x->data && s0->ne[0] == x->ne[1] && s0->ne[1] == x->ne[0];
-                    auto disjoint = [](const ggml_tensor * u, const ggml_tensor * v) {
-                        return (const char *) u->data + ggml_nbytes(u) <= (const char *) v->data ||
-                               (const char *) v->data + ggml_nbytes(v) <= (const char *) u->data;
-                    };
-                    int j = i + 1;
-                    while (node(j) && is_view_op(node(j)) && node(j)->src[0] != op) ++j;
-                    ggml_tensor * nx = node(j);
-                    if (swap01 && nx && nx->op == GGML_OP_ADD && sole(op, nx) && nx->type == GGML_TYPE_F32 &&
-                        ggml_is_contiguous(nx) && ggml_are_same_shape(nx, op)) {
-                        const ggml_tensor * pe = nx->src[0] == op ? nx->src[1] : nx->src[0];
-                        if (pe != op && pe->type == GGML_TYPE_F32 && ggml_are_same_shape(pe, op) && pe->nb[0] == 4 &&
-                            pe->nb[1] == (size_t) pe->ne[0] * 4 && nx->src[1] == op && disjoint(nx, x) && disjoint(nx, pe)) {
-                            // x [C rows][T] -> nx [T rows][C]: R = C, C' = T
-                            const int R = (int) x->ne[1], Cc = (int) x->ne[0];
-                            hipLaunchKernelGGL(k_transpose_f32, dim3((unsigned) ((Cc + 63) / 64), (unsigned) ((R + 63) / 64)), dim3(256), 0,
-                                               st, (const float *) x->data, (float *) nx->data, R, Cc, nullptr, nullptr,
-                                               (const float *) pe->data);
-                            b->stats.n_other++;
-                            b->stats.n_fused += 1;
-                            i = j;
-                            break;
-                        }
-                    }
-                    if (swap01 && nx && nx->op == GGML_OP_POOL_1D && nx->src[0] == op && sole(op, nx)) {
-                        const int32_t * pp = (const int32_t *) nx->op_params;
-                        ggml_tensor * p2 = node(j + 1), * c2 = node(j + 2);
-                        if (pp[0] == GGML_OP_POOL_AVG && pp[1] == pp[2] && pp[3] == 0 && pp[1] >= 1 && nx->type == GGML_TYPE_F32 &&
-                            p2 && c2 && p2->op == GGML_OP_PERMUTE && p2->src[0] == nx && sole(nx, p2) &&
-                            ((const int32_t *) p2->op_params)[0] == 1 && ((const int32_t *) p2->op_params)[1] == 0 &&
-                            c2->op == GGML_OP_CONT && c2->src[0] == p2 && sole(p2, c2) && c2->type == GGML_TYPE_F32 &&
-                            ggml_is_contiguous(c2) && c2->ne[0] == x->ne[0] && c2->ne[1] == x->ne[1] / pp[1] &&
-                            c2->ne[2] == 1 && c2->ne[3] == 1) {
-                            const bool direct = disjoint(c2, x);
-                            if (direct || (disjoint(op, x) && disjoint(op, c2))) {
-                                const int64_t nn2 = ggml_nelements(c2);
-                                float * dst = (float *) (direct ? c2->data : op->data);
-                                hipLaunchKernelGGL(k_pool_rows_avg, grid1(nn2), dim3(256), 0, st, (const float *) x->data, dst,
-                                                   (int) x->ne[0], (int) pp[1], nn2);
-                                if (!direct) Q2A_HIP(hipMemcpyAsync(c2->data, dst, (size_t) nn2 * 4, hipMemcpyDeviceToDevice, st));
-                                b->stats.n_other++;
-                                b->stats.n_fused += 2;
-                                i = j + 2;
-                                break;
-                            }
-                        }
-                    }
-                }
-                if (vprep.count(op) && !vt_ready_for) {   // V of a fused attention: its V^T operand instead of the f32 copy
-                    // (one pending at a time: a second V before the first attention is copied normally)
-                    const int T = (int) op->ne[0], H = (int) op->ne[2], TP = (T + 63) / 64 * 64;
-                    const size_t vb1 = ((size_t) H * 64 * TP * 2 + 255) & ~size_t(255);
-                    const bool vlo = q2a_attention_wants_vlo();   // (run_fused_attention finds the lo image at +vb1)
-                    _Float16 * vt = vt_buffer(b, vlo ? 2 * vb1 : vb1);
-                    hipLaunchKernelGGL(k_vt_tile, dim3((unsigned) (TP / 64), (unsigned) H), dim3(256), 0, st, tv(op->src[0]), vt,
-                                       vlo ? (_Float16 *) ((char *) vt + vb1) : nullptr, T, TP);
-                    vt_ready_for = op;
-                    b->stats.n_other++;
-                    break;
-                }
-                ggml_tensor * dst = op->op == GGML_OP_CPY ? op->src[1] : op;
-                if (n < (1ll << 31))
-                    hipLaunchKernelGGL(k_copy<uint32_t>, grid1(n), dim3(256), 0, st, tv(s0), (int) s0->type, tv(dst), (int) dst->type, n);
-                else
-                    hipLaunchKernelGGL(k_copy<int64_t>, grid1(n), dim3(256), 0, st, tv(s0), (int) s0->type, tv(dst), (int) dst->type, n);
-                b->stats.n_other++;
-                break;
-            }
-            case GGML_OP_IM2COL: {
-                const int32_t * pp = (const int32_t *) op->op_params;
-                const int IC = (int) s1->ne[1], IW = (int) s1->ne[0], KW = (int) s0->ne[0], OW = (int) op->ne[1];
-                hipLaunchKernelGGL(k_im2col1d, grid1(n), dim3(256), 0, st, tv(s1), tv(op), (int) op->type, IC, IW, KW, OW,
-                                   pp[0], pp[2], pp[4], n);
-                b->stats.n_other++;
-                break;
-            }
-            case GGML_OP_POOL_1D: {
-                const int32_t * pp = (const int32_t *) op->op_params;
-                hipLaunchKernelGGL(k_pool1d_avg, grid1(n), dim3(256), 0, st, tv(s0), tv(op), (int) pp[1], n);
-                b->stats.n_other++;
-                break;
-            }
-            default:
-                Q2A_LOG_ERROR("ggml-q2a: unsupported op %s (%s)\n", ggml_op_desc(op), op->name);
-                return GGML_STATUS_FAILED;
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
@@ -2340,7 +2338,7 @@ uint64_t graph_signature(ggml_cgraph * g, uint64_t wgen) {
 ggml_status graph_compute(ggml_backend_t backend, ggml_cgraph * g) {
     q2a_backend_ctx * b = (q2a_backend_ctx *) backend->context;
     Q2A_HIP(hipSetDevice(b->device));
-    static const bool no_graph = [] { const char * v = getenv("GGML_Q2A_NO_GRAPH"); return v && atoi(v); }();
+    static const bool no_graph = env_on("GGML_Q2A_NO_GRAPH");
     if (no_graph) return run_nodes(b, g);
     constexpr size_t max_graphs = 8;
     q2a_device_ctx * d = dev_ctx(b->device);
@@ -2411,11 +2409,8 @@ void be_free(ggml_backend_t be) {
     q2a_backend_ctx * b = (q2a_backend_ctx *) be->context;
     (void) hipSetDevice(b->device);
     (void) hipStreamSynchronize(b->stream);
-    if (b->scratch) (void) hipFree(b->scratch);
-    if (b->vt_buf) (void) hipFree(b->vt_buf);
-    if (b->qkv_buf) (void) hipFree(b->qkv_buf);
-    if (b->pre16) (void) hipFree(b->pre16);
-    for (int k = 0; k < 2; ++k) if (b->a16[k]) (void) hipFree(b->a16[k]);
+    for (void * q : {b->scratch, (void *) b->vt_buf, (void *) b->qkv_buf, (void *) b->pre16, (void *) b->a16[0], (void *) b->a16[1]})
+        if (q) (void) hipFree(q);
     for (auto & e : b->graphs) if (e.exec) (void) hipGraphExecDestroy(e.exec);
     (void) hipStreamDestroy(b->stream);
     delete b;
