@@ -128,6 +128,37 @@ int q2a_encode_device_ex(q2a_engine * e, const float * pcm_dev, int64_t pcm_stri
 int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                        int n_clips, int offset_ms, float * out_host, int32_t * status);
 
+/* ---- clips shorter than 30 s: padding-aware encode ----------------------------------------------------------
+ * The entry points above follow the reference: every clip is a full 30 s window and every query attends to all
+ * n_audio_ctx keys, padding included (the reference's graph has no mask). Qwen2-Audio itself masks the padded key
+ * positions in every encoder layer and keeps only the valid output frames; the entry points below do that.
+ *
+ * q2a_valid_lengths: the valid encoder positions (enc_len) and output vectors (out_len) of a clip of n_samples samples
+ * encoded from offset_ms. Pure host arithmetic (also exported from libq2a_host.so):
+ *   n_len_org = 1 + (n_samples - 200) / 160                        (the mel frames the reference computes)
+ *   frames    = clamp(n_len_org - offset_ms / 10, 1, 2 * n_audio_ctx)
+ *   enc_len   = (frames - 1) / 2 + 1                                (conv2, stride 2)
+ *   out_len   = enc_len / 2                                         (AvgPool1d(2))
+ * Either output pointer may be NULL. Q2A_ERR_ARG for a negative argument or n_audio_ctx = 0. */
+int q2a_valid_lengths(int n_samples, int offset_ms, int n_audio_ctx, int32_t * enc_len, int32_t * out_len);
+
+/* q2a_encode_device_ex with per-clip key lengths: in every encoder block clip c's queries attend to keys
+ * 0 .. key_len[c]-1 only (rows past it of K and V are never read).
+ *   offsets_ms  host array [n_clips], or NULL (0 for every clip)
+ *   key_len     host array [n_clips], 1 <= key_len[c] <= n_audio_ctx (else Q2A_ERR_ARG, before anything is launched),
+ *               or NULL: q2a_valid_lengths' enc_len of each clip
+ *   out_len     host array [n_clips], may be NULL: key_len[c] / 2 valid output vectors, 0 for a skipped clip
+ *   out_dev     [n_clips][n_out][n_audio_state] f32: rows >= out_len[c] of clip c are written as zeros (a skipped
+ *               clip's rows are all zeros)
+ * Everything else is as in q2a_encode_device_ex (same front end, GEMMs and LayerNorms over all n_audio_ctx rows: the
+ * padded rows are computed and ignored). Reference activation contract only: Q2A_ERR_UNSUPPORTED for Q2A_ACT_BF16. */
+int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream);
+/* Same with host buffers in and out (like q2a_encode_host_ex; synchronous). */
+int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                           const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status);
+
 /* log-mel of one clip (whisper_pcm_to_mel semantics): writes [n_mels][n_len] into mel_out (capacity
  * mel_cap floats) and *n_len. Runs the same kernels as the encoder on the engine's device. */
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len);
@@ -201,6 +232,11 @@ int q2a_test_fc1_path(q2a_engine * e, int path);
 /* Attention only: q,k,v [n_clips*T][D] f32 (q already scaled), out [n_clips*T][D] f32. */
 int q2a_test_attention(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                        float * out_dev, void * stream);
+/* q2a_test_attention / q2a_test_block with per-clip key lengths (host array [n_clips], 1 <= key_len[c] <= n_audio_ctx,
+ * uploaded by the call): the key-length instantiation of the attention kernel. Reference activation contract only. */
+int q2a_test_attention_len(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
+                           const int32_t * key_len, float * out_dev, void * stream);
+int q2a_test_block_len(q2a_engine * e, int layer, float * x_dev, int n_clips, const int32_t * key_len, void * stream);
 
 /* ---- downstream consumer: the Qwen2-Audio multi-modal projector ------------------------
  * audio_features = Linear(d_model -> text hidden size, bias)(embd_enc) — transformers' Qwen2AudioMultiModalProjector

@@ -13,13 +13,16 @@
 // Kernels (the schedules measured and not adopted live in diag/attn_variants.hip, built only into diag libraries):
 //   k_attn_t       reference contract: one 256-thread workgroup = 4 waves x 32 queries of one (clip, head) (x 16 when
 //                  that grid would leave CUs idle), K/V tiles of 32 keys by LDS-DMA into three LDS stages,
-//                  software-pipelined, 16x16x32 MFMAs
+//                  software-pipelined, 16x16x32 MFMAs; with per-clip key lengths (q2a_attn_args.key_len, the padded
+//                  encode) its KL instantiation, which never reads K / V rows past a clip's length
 //   k_attn_pp<BF>  bf16-activation contract (BF = true): 8-wave ping-pong, one 512-thread workgroup = 256 queries
 // The S accumulator feeds the P.V MFMA as its B operand with no data movement (K rows permuted so a lane's scores are
 // the keys of its P.V fragment; cdna_hip_programming.md §3 "An accumulator tile as the next MFMA's operand").
 #include "q2a_internal.h"
 
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 
 namespace {
 
@@ -152,9 +155,14 @@ __device__ __forceinline__ float sum_lane32(float x) {
 // NQB = 16-query blocks per wave: 2 (128 queries per workgroup) or 1 (64, for grids too small to fill the chip — one
 // clip). A block's arithmetic does not depend on its wave-mates (the lazy re-base is decided per block), so both forms
 // give every query the same bits.
-template <bool VR, int NQB>
+// KL: per-clip key lengths (q2a_attn_args.key_len): the clip's queries attend to keys 0 .. Tk-1, Tk = key_len[clip]
+// (uniform per workgroup) — the tile count, the DMA row clamp and the mask take Tk where the other form takes T, so
+// rows >= Tk of K and V are never read; a workgroup whose queries all lie at or past Tk stores zeros and leaves. The
+// Q-row clamp and the store guard keep T. Its own instantiation: the !KL forms compile as before.
+template <bool VR, int NQB, bool KL = false>
 __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
     static_assert(NQB == 1 || NQB == 2, "16 or 32 queries per wave");
+    static_assert(!KL || VR, "key lengths: row-major V only (the V^T image's columns are not clamped)");
     constexpr int QWG = 64 * NQB;   // queries per workgroup
     constexpr int KROW = 128, VROW = 64;
     constexpr int KIMG = KS * KROW, VIMG = 64 * VROW;
@@ -171,6 +179,26 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
     const int q0 = qt * QWG + wave * 16 * NQB;
     const int64_t rowbase = (int64_t) clip * T;
     const int c16 = lane & 15, g = lane >> 4;
+    int Tk = T;   // keys of this clip
+    if constexpr (KL) {
+        Tk = min(max(p.key_len[clip], 1), T);   // (the callers check 1 <= key_len <= T; the DMA clamp relies on it)
+        if (qt * QWG >= Tk) {   // every query of the workgroup lies in the padding: zeros, before the first barrier
+#pragma unroll
+            for (int qb = 0; qb < NQB; ++qb) {
+                const int q = q0 + 16 * qb + c16;
+                if (q < T) {
+                    const int64_t orow = (rowbase + q) * D + h * 64;
+#pragma unroll
+                    for (int db = 0; db < 4; ++db) {
+                        const int d = 16 * db + 4 * g;
+                        if (p.outH) *(half4 *) (p.outH + orow + d) = half4{(_Float16) 0.f, (_Float16) 0.f, (_Float16) 0.f, (_Float16) 0.f};
+                        else *(float4 *) (p.outF + orow + d) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+                }
+            }
+            return;
+        }
+    }
 
     // Q fragments (B operand): query 16qb + c16, d = 32ds + 8g .. +7
     half8 qh[NQB][2], ql[NQB][2];
@@ -205,7 +233,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
     const int vrow_d = 16 * wave + (lane >> 2), vg = (lane & 3) ^ vswz(vrow_d);
     const int vrg = (lane & 7) ^ vrswz(krow_d);
     auto dma_tile = [&](char * st, int t) {   // (k_attn_s's DMA)
-        const int key = min(t * KS + krow_d, T - 1);
+        const int key = min(t * KS + krow_d, Tk - 1);
         const uint32_t ko = (uint32_t) (key * D + kg * 8) * 2u;
         const uint32_t vo = VR ? (uint32_t) (key * D + vrg * 8) * 2u : (uint32_t) (vrow_d * p.TP + t * KS + vg * 8) * 2u;
         __builtin_amdgcn_global_load_lds((const void *) (khb + ko), (lds_ptr_t) (st + wave * 1024), 16, 0, 0);
@@ -223,7 +251,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
         m_run[qb] = 0.f;
         l_run[qb] = 0.f;
     }
-    const int ntiles = (T + KS - 1) / KS;
+    const int ntiles = (Tk + KS - 1) / KS;
     // LDS byte offsets: K row of (kb, i = c16), chunk 4ds + g (swizzled); V^T row c16 (+16db), granule g (swizzled)
     uint32_t kofs[2][2], vofs;
 #pragma unroll
@@ -331,7 +359,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
             }
         }
     };
-    auto mask = [&](sc_t & sv, int t) {   // keys >= T (last tile only): key of (kb, r) in lane group g is 8g + 4kb + r
+    auto mask = [&](sc_t & sv, int t) {   // keys >= Tk (last tile only): key of (kb, r) in lane group g is 8g + 4kb + r
         if (t == ntiles - 1) {
 #pragma unroll
             for (int qb = 0; qb < NQB; ++qb)
@@ -339,7 +367,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (t * KS + 8 * g + 4 * kb + r >= T) sv[qb][kb][r] = -1e30f;
+                        if (t * KS + 8 * g + 4 * kb + r >= Tk) sv[qb][kb][r] = -1e30f;
         }
     };
     // re-base query block qb to the tile's max over its 32 keys (4 lane groups): first tile m' := that max
@@ -424,7 +452,8 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) sn[qb][kb] = init[qb][kb];
         // region A: QK^T(t+1) beside the P split / sums of tile t. (After the last tile it reads a stage holding an
-        // older tile; those scores are never used.)
+        // older tile — or, with one or two tiles, one never filled; those scores are never used: sn and the ex that
+        // region B derives from it are read by the next iteration only, and there is none.)
         qk(sK, sn, &ex, ls);
         // rare: re-base from tile t's scores (K(t) in place), decided per 16-query block (a block whose lanes all stay
         // under PLIM keeps its reference point and its exponentials)
@@ -757,8 +786,10 @@ bool q2a_attention_wants_vlo() { return true; }
 #ifndef Q2A_ATTN_LAUNCH
 #define Q2A_ATTN_LAUNCH q2a_launch_attention
 #endif
-hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
+namespace {
+hipError_t launch_attention(const q2a_attn_args & a, hipStream_t s) {
     if (a.D != a.H * 64 || a.TP < ((a.T + KT - 1) / KT) * KT) return hipErrorInvalidValue;
+    if (a.key_len && (a.bf16 || !a.v_rows)) return hipErrorInvalidValue;   // key lengths: k_attn_t<true, *, true> only
     if (a.bf16) {
         // bf16 contract: the 8-wave ping-pong kernel (33 -> 30 ms/step at 64 clips against the 4-wave form)
         if (!a.outH) return hipErrorInvalidValue;
@@ -770,7 +801,10 @@ hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
         const int n2 = ((a.T + 127) / 128) * a.H * a.n_clips;
         const bool narrow = n2 < q2a_cu_count();
         const dim3 grid(narrow ? ((a.T + 63) / 64) * a.H * a.n_clips : n2);
-        if (a.v_rows) {
+        if (a.key_len) {   // (the grid stays a function of T and n_clips: short clips' tail workgroups leave at once)
+            if (narrow) hipLaunchKernelGGL((k_attn_t<true, 1, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_attn_t<true, 2, true>), grid, dim3(256), 0, s, a);
+        } else if (a.v_rows) {
             if (narrow) hipLaunchKernelGGL((k_attn_t<true, 1>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((k_attn_t<true, 2>), grid, dim3(256), 0, s, a);
         } else {
@@ -780,3 +814,19 @@ hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
     }
     return hipGetLastError();
 }
+}  // namespace
+
+// Reads the fields up to v_rows only and runs without key lengths: key_len was appended to q2a_attn_args later, and a
+// caller compiled against the struct as it was before (the ggml plugin's object, which is also linked into programs
+// built apart from this library) hands over an object that ends at v_rows. Key lengths go through
+// q2a_launch_attention_len.
+hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
+    q2a_attn_args b;
+    memcpy(&b, &a, offsetof(q2a_attn_args, key_len));
+    b.key_len = nullptr;
+    return launch_attention(b, s);
+}
+
+// The launcher with per-clip key lengths: key_len != NULL selects k_attn_t<true, NQB, true> (hipErrorInvalidValue with
+// the bf16 contract or the V^T layout), NULL is q2a_launch_attention
+hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s) { return launch_attention(a, s); }

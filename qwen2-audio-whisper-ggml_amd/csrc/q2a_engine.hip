@@ -736,7 +736,7 @@ struct q2a_engine {
     hipStream_t copy_stream = nullptr;
     host_buf hb[2];
     float * out_stage = nullptr;     // unused (outputs are written straight to the user buffer)
-    int32_t * meta = nullptr;        // device: nsamp | seek | clip_ok | clip_max
+    int32_t * meta = nullptr;        // device: nsamp | seek | clip_ok | clip_max | key_len (rows of the call's B)
     int32_t * meta_host = nullptr;   // pinned
     hipEvent_t meta_evt = nullptr;   // last async upload out of meta_host (host rewrites wait on it)
     float * mel = nullptr;
@@ -880,7 +880,7 @@ int reserve(q2a_engine * e, int B) {
     const bool quant = e->blk != 0;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_meta = take((size_t) B * 4 * 4);
+    const size_t o_meta = take((size_t) B * 5 * 4);
     const size_t o_mel = take((size_t) B * d.M * d.TM * 4);
     const size_t o_xc1 = take((size_t) B * (d.TM + 2) * 3 * d.M * 2);
     const size_t o_y1 = take((size_t) B * (d.TM + 1) * d.D * 2 * (e->f32 ? 2 : 1));
@@ -920,7 +920,7 @@ int reserve(q2a_engine * e, int B) {
         return Q2A_ERR_OOM;
     }
     HIP_TRY(hipMemsetAsync(ws, 0, off, e->stream));   // zero pad rows (xc1 rows 0/last, y1 row 0, V^T tail)
-    HIP_TRY(hipHostMalloc((void **) &e->meta_host, (size_t) B * 4 * 4, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **) &e->meta_host, (size_t) B * 5 * 4, hipHostMallocDefault));
     uint8_t * b = (uint8_t *) ws;
     e->ws = ws; e->ws_bytes = off; e->cap_clips = B;
     e->meta = (int32_t *) (b + o_meta);
@@ -1006,8 +1006,9 @@ int ln_mode(const q2a_engine * e) { return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 
         }                                                                             \
     } while (0)
 
-// one pre-LN encoder block on X [B*T][D] (qwen2-whisper.cpp:2014-2155)
-int run_block(q2a_engine * e, int l, int B, hipStream_t s) {
+// one pre-LN encoder block on X [B*T][D] (qwen2-whisper.cpp:2014-2155); key_len: device [B] per-clip key lengths of
+// the attention (the padded entry points), NULL = all T keys
+int run_block(q2a_engine * e, int l, int B, hipStream_t s, const int32_t * key_len = nullptr) {
     const dims & d = e->d;
     const int M = B * d.T;
     const int mode = ln_mode(e);
@@ -1032,8 +1033,10 @@ int run_block(q2a_engine * e, int l, int B, hipStream_t s) {
         q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, B, d.T, d.D, d.H, e->TP, nullptr, nullptr, e->bf16 ? 1 : 0};
         at.vtl = e->vtl;
         at.v_rows = e->bf16 ? 0 : 1;
+        at.key_len = key_len;
         if (mode == 0 || mode == 4) at.outH = e->actD; else at.outF = e->attF;
-        PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention(at, s));
+        if (key_len) PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_len(at, s));
+        else PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention(at, s));
         if (mode == 3) {
             const int64_t n = (int64_t) M * d.D;
             PLAUNCH(e, s, Q2A_PROF_QUANT, launch_split3(e->attF, e->actD, d.D, n, s));
@@ -1155,7 +1158,7 @@ int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int m
 
 // per-clip metadata (host): whisper_encoder_output_with_state's seek / too-short logic (:2356-2365)
 int prepare_meta(q2a_engine * e, const int32_t * n_samples, int B, int offset_ms, const int32_t * offs, int32_t * status, int & max_frames,
-                 int64_t max_valid, hipStream_t s) {
+                 int64_t max_valid, hipStream_t s, const int32_t * key_len = nullptr) {
     int32_t * mh = e->meta_host;
     HIP_TRY(hipEventSynchronize(e->meta_evt));   // the previous call's upload out of mh may still be queued
     max_frames = 0;
@@ -1172,8 +1175,82 @@ int prepare_meta(q2a_engine * e, const int32_t * n_samples, int B, int offset_ms
         if (status) status[c] = ok ? Q2A_CLIP_ENCODED : Q2A_CLIP_SKIPPED;
         max_frames = std::max(max_frames, (int) (((int64_t) mh[c] + 480000) / 160));
     }
-    HIP_TRY(hipMemcpyAsync(e->meta, mh, (size_t) B * 3 * 4, hipMemcpyHostToDevice, s));
+    // key lengths (the padded entry points): the fifth row, in the same upload (the clip_max row between is
+    // device-written: run_frontend resets it after this copy, on the same stream)
+    if (key_len)
+        for (int c = 0; c < B; ++c) { mh[3 * B + c] = (int32_t) 0x80808080u; mh[4 * B + c] = key_len[c]; }
+    HIP_TRY(hipMemcpyAsync(e->meta, mh, (size_t) B * (key_len ? 5 : 3) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(e->meta_evt, s));
+    return Q2A_OK;
+}
+
+// key lengths of a test hook into the metadata's fifth row (host array, checked; the meta_evt handshake as prepare_meta)
+int upload_key_len(q2a_engine * e, const int32_t * key_len, int B, hipStream_t s) {
+    if (e->bf16) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    for (int c = 0; c < B; ++c)
+        if (key_len[c] < 1 || key_len[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, key_len[c], e->d.T); return Q2A_ERR_ARG; }
+    HIP_TRY(hipEventSynchronize(e->meta_evt));
+    memcpy(e->meta_host + 4 * B, key_len, (size_t) B * 4);
+    HIP_TRY(hipMemcpyAsync(e->meta + 4 * B, e->meta_host + 4 * B, (size_t) B * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->meta_evt, s));
+    return Q2A_OK;
+}
+
+// out [B][TO][D]: rows >= key_len[c] / 2 of clip c (every row of a clip that was not encoded) := 0
+__global__ void k_zero_tail_rows(float * out, const int32_t * key_len, const int32_t * clip_ok, int TO, int D) {
+    const int c = blockIdx.y;
+    const int n4 = TO * D / 4, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    const int valid = clip_ok[c] ? key_len[c] / 2 : 0;
+    if (i * 4 / D >= valid) ((float4 *) (out + (int64_t) c * TO * D))[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+hipError_t launch_zero_tail_rows(float * out, const int32_t * key_len, const int32_t * clip_ok, int B, int TO, int D, hipStream_t s) {
+    if (D % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_zero_tail_rows, dim3((unsigned) ((TO * D / 4 + 255) / 256), (unsigned) B), dim3(256), 0, s, out, key_len, clip_ok, TO, D);
+    return hipGetLastError();
+}
+
+// the per-clip key lengths of a padded encode: the caller's (checked), or q2a_valid_lengths' enc_len
+int padded_key_lens(q2a_engine * e, const int32_t * n_samples, const int32_t * offs, const int32_t * key_len, int B,
+                    std::vector<int32_t> & kl) {
+    kl.resize(B);
+    for (int c = 0; c < B; ++c) {
+        if (key_len) {
+            kl[c] = key_len[c];
+            if (kl[c] < 1 || kl[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, kl[c], e->d.T); return Q2A_ERR_ARG; }
+        } else if (q2a_valid_lengths(n_samples[c], offs ? offs[c] : 0, e->d.T, &kl[c], nullptr) != Q2A_OK) {
+            set_err("clip %d: bad n_samples %d or offset", c, n_samples[c]);
+            return Q2A_ERR_ARG;
+        }
+    }
+    return Q2A_OK;
+}
+
+// encode_impl with per-clip key lengths kl (host [B], checked by padded_key_lens): the attention of every block masks
+// keys >= kl[c], output rows >= kl[c] / 2 are zeros. Everything else runs over all B*T rows as in encode_impl.
+int encode_padded_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t * n_samples, int B, const int32_t * offs,
+                       const int32_t * kl, float * out, int32_t * out_len, int32_t * status, hipStream_t s) {
+    if (B <= 0 || !pcm || !n_samples || !out || !kl) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = reserve(e, B);
+    if (rc) return rc;
+    std::vector<int32_t> st_local;
+    if (!status) { st_local.resize(B); status = st_local.data(); }
+    int max_frames = 0;
+    rc = prepare_meta(e, n_samples, B, 0, offs, status, max_frames, stride > 0 ? stride : -1, s, kl);
+    if (rc) return rc;
+    if (out_len) for (int c = 0; c < B; ++c) out_len[c] = status[c] == Q2A_CLIP_ENCODED ? kl[c] / 2 : 0;
+    rc = run_frontend(e, pcm, stride, B, max_frames, s);
+    if (rc) return rc;
+    const int32_t * kl_dev = e->meta + 4 * B;
+    for (int l = 0; l < e->d.L; ++l) {
+        rc = run_block(e, l, B, s, kl_dev);
+        if (rc) return rc;
+    }
+    q2a_pool_args pa{e->X, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, e->meta + 2 * B};
+    PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
+    PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(out, kl_dev, e->meta + 2 * B, B, e->d.TO, e->d.D, s));
     return Q2A_OK;
 }
 
@@ -1393,8 +1470,11 @@ int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n
     return q2a_encode_host_ex(e, pcm, n_samples, nullptr, n_clips, offset_ms, out_host, status);
 }
 
-int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
-                       int n_clips, int offset_ms, float * out_host, int32_t * status) {
+// q2a_encode_host_ex, and with kl (host [n_clips] key lengths, already checked) q2a_encode_host_padded: every clip's
+// output is then copied back (rows past its valid length, and a skipped clip's rows, are zeros)
+static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                            int n_clips, int offset_ms, float * out_host, int32_t * status, const int32_t * kl,
+                            int32_t * out_len) {
     if (!e || !pcm || !n_samples || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     for (int c = 0; c < n_clips; ++c)   // (checked before any copy: a negative count would be a huge memcpy)
         if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) {
@@ -1426,7 +1506,7 @@ int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t 
         q2a_engine::host_buf & b = e->hb[k & 1];
         if (hipEventSynchronize(b.d2h) != hipSuccess) return Q2A_ERR_HIP;
         for (int c = 0; c < n; ++c) {
-            if (st[c0 + c] == Q2A_CLIP_ENCODED)
+            if (st[c0 + c] == Q2A_CLIP_ENCODED || (kl && st[c0 + c] == Q2A_CLIP_SKIPPED))
                 memcpy(out_host + (c0 + c) * per_out, b.pin_out + c * per_out, per_out * 4);
             pub[c0 + c] = st[c0 + c];
         }
@@ -1448,8 +1528,12 @@ int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t 
             rc = Q2A_ERR_HIP;
             break;
         }
-        rc = encode_impl(e, b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr, b.d_out,
-                         st.data() + c0, s);
+        if (kl)
+            rc = encode_padded_impl(e, b.d_in, maxn, n_samples + c0, n, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, b.d_out,
+                                    out_len ? out_len + c0 : nullptr, st.data() + c0, s);
+        else
+            rc = encode_impl(e, b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr, b.d_out,
+                             st.data() + c0, s);
         if (rc) break;
         if (hipEventRecord(b.comp, s) != hipSuccess || hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||
             hipMemcpyAsync(b.pin_out, b.d_out, (size_t) n * per_out * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
@@ -1466,6 +1550,32 @@ int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t 
     if (rc == Q2A_ERR_HIP && g_err.empty()) set_err("host-path copy failed");
     if (status) for (int c = 0; c < n_clips; ++c) status[c] = pub[c];
     return rc;
+}
+
+int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                       int n_clips, int offset_ms, float * out_host, int32_t * status) {
+    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, offset_ms, out_host, status, nullptr, nullptr);
+}
+
+int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    std::vector<int32_t> kl;
+    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    return encode_padded_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms, kl.data(), out_dev, out_len, status,
+                              call_stream(stream));
+}
+
+int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                           const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
+    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    std::vector<int32_t> kl;
+    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -1585,18 +1695,27 @@ int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M
     return Q2A_OK;
 }
 
-int q2a_test_block(q2a_engine * e, int layer, float * x, int n_clips, void * stream) {
-    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0) return Q2A_ERR_ARG;
+static int test_block_impl(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, bool with_len, void * stream) {
+    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0 || (with_len && !key_len)) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
     if (rc) return rc;
+    if (with_len && (rc = upload_key_len(e, key_len, n_clips, s))) return rc;
     const size_t bytes = (size_t) n_clips * e->d.T * e->d.D * 4;
     HIP_TRY(hipMemcpyAsync(e->X, x, bytes, hipMemcpyDeviceToDevice, s));
-    rc = run_block(e, layer, n_clips, s);
+    rc = run_block(e, layer, n_clips, s, with_len ? e->meta + 4 * n_clips : nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(x, e->X, bytes, hipMemcpyDeviceToDevice, s));
     return Q2A_OK;
+}
+
+int q2a_test_block(q2a_engine * e, int layer, float * x, int n_clips, void * stream) {
+    return test_block_impl(e, layer, x, n_clips, nullptr, false, stream);
+}
+
+int q2a_test_block_len(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
+    return test_block_impl(e, layer, x, n_clips, key_len, true, stream);
 }
 
 int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void * const * taps, void * stream) {
@@ -1646,13 +1765,14 @@ int q2a_test_fc1_path(q2a_engine * e, int path) {
     return Q2A_OK;
 }
 
-int q2a_test_attention(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips, float * out,
-                       void * stream) {
-    if (!e || n_clips <= 0) return Q2A_ERR_ARG;
+static int test_attention_impl(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
+                               const int32_t * key_len, bool with_len, float * out, void * stream) {
+    if (!e || n_clips <= 0 || (with_len && !key_len)) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
     if (rc) return rc;
+    if (with_len && (rc = upload_key_len(e, key_len, n_clips, s))) return rc;
     const dims & d = e->d;
     const int64_t n = (int64_t) n_clips * d.T * d.D;
     const dim3 g((unsigned) ((n + 255) / 256)), b(256);
@@ -1663,8 +1783,20 @@ int q2a_test_attention(q2a_engine * e, const float * q, const float * k, const f
     q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, n_clips, d.T, d.D, d.H, e->TP, nullptr, out};
     at.vtl = e->vtl;
     at.v_rows = 1;
-    LAUNCH(q2a_launch_attention(at, s));
+    at.key_len = with_len ? e->meta + 4 * n_clips : nullptr;
+    if (with_len) LAUNCH(q2a_launch_attention_len(at, s));
+    else LAUNCH(q2a_launch_attention(at, s));
     return Q2A_OK;
+}
+
+int q2a_test_attention(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips, float * out,
+                       void * stream) {
+    return test_attention_impl(e, q, k, v, n_clips, nullptr, false, out, stream);
+}
+
+int q2a_test_attention_len(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
+                           const int32_t * key_len, float * out, void * stream) {
+    return test_attention_impl(e, q, k, v, n_clips, key_len, true, out, stream);
 }
 
 // ---- downstream consumer: the Qwen2-Audio multi-modal projector ---------------------------

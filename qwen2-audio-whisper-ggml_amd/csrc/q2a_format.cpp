@@ -2,6 +2,7 @@
 // Compiled with -ffp-contract=off: the quantizers must round exactly like the reference build (the
 // reference's shipped Debug build forms no FMAs), so that quantized bytes are identical.
 #include "q2a_format.h"
+#include "q2a_encoder.h"
 
 #include <algorithm>
 #include <cmath>
@@ -99,6 +100,18 @@ extern "C" void q2a_synth_clip(float * out, int64_t n, int c) {
                          0.05 * q2a_gauss(seed, 0, (uint64_t) t);
         out[t] = (float) v;
     }
+}
+
+// valid encoder positions / output vectors of a clip (include/q2a_encoder.h). Here so that libq2a.so and
+// libq2a_host.so both export it.
+extern "C" int q2a_valid_lengths(int n_samples, int offset_ms, int n_audio_ctx, int32_t * enc_len, int32_t * out_len) {
+    if (n_samples < 0 || offset_ms < 0 || n_audio_ctx <= 0) return Q2A_ERR_ARG;
+    const int n_len_org = 1 + (n_samples + 200 - 400) / 160;   // as prepare_meta (q2a_engine.hip), C truncation
+    const int frames = std::min(std::max(n_len_org - offset_ms / 10, 1), 2 * n_audio_ctx);
+    const int el = (frames - 1) / 2 + 1;   // conv2: kernel 3, stride 2, padding 1
+    if (enc_len) *enc_len = el;
+    if (out_len) *out_len = el / 2;        // AvgPool1d(2, 2)
+    return Q2A_OK;
 }
 
 static double hz_to_mel_slaney(double f) {

@@ -139,12 +139,18 @@ struct q2a_attn_args {
     const q2a_half * vtl;   // V^T lo image (v - fp16(v)) when q2a_attention_wants_vlo(), else unused
     int v_rows;             // reference contract: 1 = vt / vtl hold V hi / lo row-major [clips*T][D] (the K layout; the
                             //   kernel reads its P.V operand by transposing LDS reads), 0 = V^T [clip][head][64][TP]
+    const int32_t * key_len;   // device [n_clips]: clip c attends to keys 0 .. key_len[c]-1 only (1 <= key_len[c] <= T; rows
+                               //   past it of K and V are never read). NULL = every clip attends to all T keys. Reference
+                               //   contract with v_rows only; read by q2a_launch_attention_len alone. Stays the last field
 };
 // Reference contract (bf16 == 0): qh/ql hold Q * Q2A_LOG2E (after the 1/sqrt(dh) scale), split hi/lo — the kernel
 // works in log2 units (P = exp2(S' - m')); every producer (QKV epilogue qscale, ggml backend prep, test entry) folds it.
 // bf16 contract: qh holds Q scaled by 1/sqrt(dh) only.
 constexpr float Q2A_LOG2E = 1.4426950408889634f;
+// q2a_launch_attention reads the fields up to v_rows only (key_len was appended later: an object compiled against the
+// struct before that still calls it) and never masks; q2a_launch_attention_len honours key_len (NULL: the same launch)
 hipError_t q2a_launch_attention(const q2a_attn_args & a, hipStream_t s);
+hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s);
 // true when this build's reference-contract attention reads a V^T lo image (the QKV epilogue must then write it)
 bool q2a_attention_wants_vlo();
 

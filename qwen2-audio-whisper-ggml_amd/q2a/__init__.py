@@ -24,6 +24,8 @@ EXPORTS = (
     "q2a_pack_model_compact", "q2a_blob_device_size", "q2a_expand_blob",
     "q2a_device_count", "q2a_group_open", "q2a_group_close", "q2a_group_size", "q2a_group_engine", "q2a_group_split",
     "q2a_group_encode_host", "q2a_group_setup_times", "q2a_group_open_with", "q2a_whisper_context_engine",
+    "q2a_valid_lengths", "q2a_encode_device_padded", "q2a_encode_host_padded", "q2a_test_attention_len",
+    "q2a_test_block_len",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -106,6 +108,13 @@ def lib() -> C.CDLL:
             L.q2a_group_encode_host.argtypes = [vp, C.POINTER(vp), i32p, i32p, C.c_int, C.c_int, vp, i32p]
             L.q2a_group_setup_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        # padding-aware encode (optional like the hooks above: an earlier diagnostic library still loads)
+        for name, at in (("q2a_encode_device_padded", [vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, vp, i32p, i32p, vp]),
+                         ("q2a_encode_host_padded", [vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, i32p, i32p]),
+                         ("q2a_test_attention_len", [vp, vp, vp, vp, C.c_int, i32p, vp, vp]),
+                         ("q2a_test_block_len", [vp, C.c_int, vp, C.c_int, i32p, vp])):
+            if hasattr(L, name):
+                getattr(L, name).argtypes = at
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -117,7 +126,9 @@ def lib() -> C.CDLL:
 
 def _check(rc):
     if rc != 0:
-        raise Q2AError(f"q2a error {rc}: {lib().q2a_last_error().decode()}")
+        err = Q2AError(f"q2a error {rc}: {lib().q2a_last_error().decode()}")
+        err.rc = rc   # the q2a_status code (include/q2a_encoder.h)
+        raise err
 
 
 class Engine:
@@ -191,6 +202,48 @@ class Engine:
         _check(rc)
         return out, st
 
+    def encode_device_padded(self, pcm_ptr: int, pcm_stride: int, n_samples, out_ptr: int, offsets_ms=None, key_len=None,
+                             stream: int | None = None):
+        """q2a_encode_device_padded: per-clip key lengths in every block's attention (key_len=None: valid_lengths'
+        enc_len of each clip), output rows >= out_len written as zeros. Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        n = len(ns)
+        offs = None if offsets_ms is None else np.ascontiguousarray(offsets_ms, dtype=np.int32)
+        kl = None if key_len is None else np.ascontiguousarray(key_len, dtype=np.int32)
+        if (offs is not None and len(offs) != n) or (kl is not None and len(kl) != n):
+            raise ValueError(f"offsets_ms / key_len need {n} entries")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        _check(lib().q2a_encode_device_padded(self.h, C.c_void_p(pcm_ptr), C.c_int64(pcm_stride), ns.ctypes.data_as(i32p),
+                                              offs.ctypes.data_as(i32p) if offs is not None else None,
+                                              kl.ctypes.data_as(i32p) if kl is not None else None, n,
+                                              C.c_void_p(out_ptr), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
+                                              C.c_void_p(stream) if stream else None))
+        return ol, st
+
+    def encode_host_padded(self, clips, offsets_ms=None, key_len=None, out: np.ndarray | None = None,
+                           return_status: bool = False):
+        """q2a_encode_host_padded over host PCM clips -> (out, out_len) (with return_status: (out, out_len, status))."""
+        i32p = C.POINTER(C.c_int32)
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(clips)
+        if out is None:
+            out = np.zeros((n,) + self.out_shape, dtype=np.float32)
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
+        ns = np.array([len(c) for c in clips], dtype=np.int32)
+        offs = None if offsets_ms is None else np.ascontiguousarray(offsets_ms, dtype=np.int32)
+        kl = None if key_len is None else np.ascontiguousarray(key_len, dtype=np.int32)
+        if (offs is not None and len(offs) != n) or (kl is not None and len(kl) != n):
+            raise ValueError(f"offsets_ms / key_len need {n} entries")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        _check(lib().q2a_encode_host_padded(self.h, ptrs, ns.ctypes.data_as(i32p),
+                                            offs.ctypes.data_as(i32p) if offs is not None else None,
+                                            kl.ctypes.data_as(i32p) if kl is not None else None, n,
+                                            C.c_void_p(out.ctypes.data), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p)))
+        return (out, ol, st) if return_status else (out, ol)
+
     def pcm_to_mel(self, pcm: np.ndarray) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         n_len = (len(pcm) + 480000) // 160
@@ -230,6 +283,41 @@ class Engine:
     def test_attention(self, q_ptr, k_ptr, v_ptr, n_clips, out_ptr, stream=None):
         _check(lib().q2a_test_attention(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
                                         C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
+
+    # the same two with per-clip key lengths (host list, uploaded by the call)
+    def test_attention_len(self, q_ptr, k_ptr, v_ptr, n_clips, key_len, out_ptr, stream=None):
+        kl = np.ascontiguousarray(key_len, dtype=np.int32)
+        assert len(kl) == n_clips
+        _check(lib().q2a_test_attention_len(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
+                                            kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out_ptr),
+                                            C.c_void_p(stream) if stream else None))
+
+    def test_block_len(self, layer, x_ptr, n_clips, key_len, stream=None):
+        kl = np.ascontiguousarray(key_len, dtype=np.int32)
+        assert len(kl) == n_clips
+        _check(lib().q2a_test_block_len(self.h, layer, C.c_void_p(x_ptr), n_clips,
+                                        kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream) if stream else None))
+
+
+_host_lib = None
+
+
+def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
+    """(enc_len, out_len): the valid encoder positions and output vectors of a clip of n_samples samples encoded from
+    offset_ms (q2a_valid_lengths). Host arithmetic through lib/libq2a_host.so: needs no GPU."""
+    global _host_lib
+    if _host_lib is None:
+        if not os.path.exists(HOST_LIB_PATH):
+            raise Q2AError(f"{HOST_LIB_PATH} not built; run `make -C {PKG_DIR} host`")
+        _host_lib = C.CDLL(HOST_LIB_PATH)
+        _host_lib.q2a_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    a, b = C.c_int32(), C.c_int32()
+    rc = _host_lib.q2a_valid_lengths(n_samples, offset_ms, n_audio_ctx, C.byref(a), C.byref(b))
+    if rc != 0:
+        err = Q2AError(f"q2a error {rc}: invalid arguments to q2a_valid_lengths")
+        err.rc = rc
+        raise err
+    return a.value, b.value
 
 
 def group_split(n_clips: int, n_devices: int) -> list[range]:
