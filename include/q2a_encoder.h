@@ -229,7 +229,13 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
  * quantizer, 1 GELU in the fc1 epilogue + quantizer, 2 GELU + Q8_K fused into the fc1 epilogue. All three give
  * identical codes (tests/test_gpu_parity.py::test_deferred_gelu_equals_epilogue_gelu); a test hook, not a tuning knob. */
 int q2a_test_fc1_path(q2a_engine * e, int path);
-/* Attention only: q,k,v [n_clips*T][D] f32 (q already scaled), out [n_clips*T][D] f32. */
+/* Attention only: q,k,v [n_clips*T][D] f32 (q already scaled), out [n_clips*T][D] f32.
+ * Every operand enters the kernel as an fp16 pair hi = fp16(x), lo = fp16(x - hi) (q after the log2 e factor), which
+ * carries 22 bits only while x - hi stays above fp16's 2^-24 spacing. Against float64 the F32-class bar (2e-5 max-rel,
+ * 5e-6 rel-L2) was measured to hold with q, k and v elements of typical magnitude 2^-4 .. 2^4 and to end at typical
+ * magnitude 2^-8 (v: rel-L2 4.5e-6; q or k: up to 1.7e-5); at 2^-12 the result is that of a one-term fp16 kernel
+ * (7e-5 .. 2.6e-4). The window belongs to each operand by itself, whatever the scores: Q*2^-8 with K*2^8 leaves it.
+ * Nothing rescales the operands (tests/test_gpu_attention_edges.py::test_scale_window). */
 int q2a_test_attention(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                        float * out_dev, void * stream);
 /* q2a_test_attention / q2a_test_block with per-clip key lengths (host array [n_clips], 1 <= key_len[c] <= n_audio_ctx,
