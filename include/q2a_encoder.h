@@ -159,6 +159,36 @@ int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_
 int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                            const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status);
 
+/* ---- variable-length encode: the encoder blocks run on the valid rows only --------------------------------------
+ * The padded entry points above still run every GEMM, LayerNorm and quantizer over all n_audio_ctx rows of every clip.
+ * The entry points below pack the valid rows of all clips into one [M_tot][n_audio_state] residual stream after the
+ * front end (which still runs over full windows), run the n_audio_layer blocks on those M_tot rows, and pool, normalise
+ * and scatter them into the same [n_clips][n_out][n_audio_state] output. They return the padded entry points' bytes:
+ * rows are independent everywhere but in the attention, every GEMM configuration sums K in the same order, and the
+ * attention's 16-query blocks are carried along whole (below).
+ *
+ * q2a_varlen_rows: the rows clip c occupies in the packed stream, and where they start (host arithmetic; also exported
+ * from libq2a_host.so):
+ *   seg_rows[c]    = key_len[c] == 0 ? 0 : min(round_up(key_len[c], 16), n_audio_ctx)
+ *   row_start[0]   = 0, row_start[c+1] = row_start[c] + seg_rows[c]         (row_start has n_clips + 1 entries)
+ * key_len[c] in 0 .. n_audio_ctx (0: a clip that is not encoded). Returns M_tot = row_start[n_clips], < 0
+ * (Q2A_ERR_ARG) on error. 16: the attention kernel decides its lazy re-base per block of 16 queries, so the rows
+ * between a clip's length and the end of its last partly valid block (the front end's output for the padding, carried
+ * through the layers) travel with the clip — at most 15 rows, computed as queries, never read as keys.
+ *
+ * Not covered: the whisper_* API, q2a_group_*, the ggml backend and the bf16 activation contract
+ * (Q2A_ERR_UNSUPPORTED); the output is not packed; the front end is not restricted to the valid frames. */
+int64_t q2a_varlen_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * row_start);
+
+/* q2a_encode_device_padded / q2a_encode_host_padded on the packed rows: the same arguments, checks, out_len, status
+ * and output bytes (a batch of skipped clips only: zeros, Q2A_OK, no block is launched). The engine keeps a second
+ * residual buffer from the first such call on (counted in q2a_info.workspace_bytes). */
+int q2a_encode_device_varlen(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream);
+int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                           const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status);
+
 /* log-mel of one clip (whisper_pcm_to_mel semantics): writes [n_mels][n_len] into mel_out (capacity
  * mel_cap floats) and *n_len. Runs the same kernels as the encoder on the engine's device. */
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len);
@@ -243,6 +273,11 @@ int q2a_test_attention(q2a_engine * e, const float * q_dev, const float * k_dev,
 int q2a_test_attention_len(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                            const int32_t * key_len, float * out_dev, void * stream);
 int q2a_test_block_len(q2a_engine * e, int layer, float * x_dev, int n_clips, const int32_t * key_len, void * stream);
+/* The same two on packed rows (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx): q, k, v, out and x are
+ * [M_tot][D]; the packed instantiation of the attention kernel. Rows behind M_tot are not touched. */
+int q2a_test_attention_varlen(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
+                              const int32_t * key_len, float * out_dev, void * stream);
+int q2a_test_block_varlen(q2a_engine * e, int layer, float * x_dev, int n_clips, const int32_t * key_len, void * stream);
 
 /* ---- downstream consumer: the Qwen2-Audio multi-modal projector ------------------------
  * audio_features = Linear(d_model -> text hidden size, bias)(embd_enc) — transformers' Qwen2AudioMultiModalProjector

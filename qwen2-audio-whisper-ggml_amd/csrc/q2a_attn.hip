@@ -13,8 +13,8 @@
 // Kernels (the schedules measured and not adopted live in diag/attn_variants.hip, built only into diag libraries):
 //   k_attn_t       reference contract: one 256-thread workgroup = 4 waves x 32 queries of one (clip, head) (x 16 when
 //                  that grid would leave CUs idle), K/V tiles of 32 keys by LDS-DMA into three LDS stages,
-//                  software-pipelined, 16x16x32 MFMAs; with per-clip key lengths (q2a_attn_args.key_len, the padded
-//                  encode) its KL instantiation, which never reads K / V rows past a clip's length
+//                  software-pipelined, 16x16x32 MFMAs; KL: per-clip key lengths (the padded encode), never reads K / V
+//                  rows past a clip's length; PK: KL on the packed rows of the variable-length encode (row_start)
 //   k_attn_pp<BF>  bf16-activation contract (BF = true): 8-wave ping-pong, one 512-thread workgroup = 256 queries
 // The S accumulator feeds the P.V MFMA as its B operand with no data movement (K rows permuted so a lane's scores are
 // the keys of its P.V fragment; cdna_hip_programming.md §3 "An accumulator tile as the next MFMA's operand").
@@ -159,10 +159,12 @@ __device__ __forceinline__ float sum_lane32(float x) {
 // (uniform per workgroup) — the tile count, the DMA row clamp and the mask take Tk where the other form takes T, so
 // rows >= Tk of K and V are never read; a workgroup whose queries all lie at or past Tk stores zeros and leaves. The
 // Q-row clamp and the store guard keep T. Its own instantiation: the !KL forms compile as before.
-template <bool VR, int NQB, bool KL = false>
+// PK (with KL): the packed rows of the variable-length encode, described at q2a_launch_attention_varlen below.
+template <bool VR, int NQB, bool KL = false, bool PK = false>
 __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
     static_assert(NQB == 1 || NQB == 2, "16 or 32 queries per wave");
     static_assert(!KL || VR, "key lengths: row-major V only (the V^T image's columns are not clamped)");
+    static_assert(!PK || KL, "the packed layout carries key lengths");
     constexpr int QWG = 64 * NQB;   // queries per workgroup
     constexpr int KROW = 128, VROW = 64;
     constexpr int KIMG = KS * KROW, VIMG = 64 * VROW;
@@ -171,18 +173,25 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
     __shared__ __attribute__((aligned(16))) char ldsB[STAGE];
     __shared__ __attribute__((aligned(16))) char ldsC[STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int T = p.T, D = p.D;
-    const int nq = (T + QWG - 1) / QWG, total = (int) gridDim.x;
+    const int D = p.D;
+    int T = p.T;   // rows of this clip (PK: its segment's, below)
+    const int nq = ((PK ? p.r_max : T) + QWG - 1) / QWG, total = (int) gridDim.x;
     const int L = (int) blockIdx.x;
     const int w = (total & 7) ? L : (L & 7) * (total >> 3) + (L >> 3);   // XCD-contiguous work order: the q-tiles of one (clip, head) on one XCD
     const int qt = w % nq, h = (w / nq) % p.H, clip = w / (nq * p.H);
     const int q0 = qt * QWG + wave * 16 * NQB;
-    const int64_t rowbase = (int64_t) clip * T;
+    int64_t rowbase = (int64_t) clip * T;
+    if constexpr (PK) {
+        const int r0 = p.row_start[clip];
+        rowbase = r0;
+        T = p.row_start[clip + 1] - r0;
+        if (qt * QWG >= T) return;   // no such rows (a clip with no rows at all: every workgroup of it)
+    }
     const int c16 = lane & 15, g = lane >> 4;
     int Tk = T;   // keys of this clip
     if constexpr (KL) {
         Tk = min(max(p.key_len[clip], 1), T);   // (the callers check 1 <= key_len <= T; the DMA clamp relies on it)
-        if (qt * QWG >= Tk) {   // every query of the workgroup lies in the padding: zeros, before the first barrier
+        if (!PK && qt * QWG >= Tk) {   // every query of the workgroup lies in the padding: zeros, before the first barrier
 #pragma unroll
             for (int qb = 0; qb < NQB; ++qb) {
                 const int q = q0 + 16 * qb + c16;
@@ -824,9 +833,39 @@ hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
     q2a_attn_args b;
     memcpy(&b, &a, offsetof(q2a_attn_args, key_len));
     b.key_len = nullptr;
+    b.row_start = nullptr;
+    b.r_max = 0;
     return launch_attention(b, s);
 }
 
 // The launcher with per-clip key lengths: key_len != NULL selects k_attn_t<true, NQB, true> (hipErrorInvalidValue with
-// the bf16 contract or the V^T layout), NULL is q2a_launch_attention
-hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s) { return launch_attention(a, s); }
+// the bf16 contract or the V^T layout), NULL is q2a_launch_attention. Reads the fields up to key_len only: the packed
+// fields behind it were appended later still.
+hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s) {
+    q2a_attn_args b;
+    memcpy(&b, &a, offsetof(q2a_attn_args, row_start));
+    b.row_start = nullptr;
+    b.r_max = 0;
+    return launch_attention(b, s);
+}
+
+// k_attn_t's PK flag (with KL): the packed layout of the variable-length encode (q2a_attn_args.row_start). Clip c owns rows
+// row_start[c] .. row_start[c+1]-1 of q / k / v / out: R rows, its key length rounded up to the 16-query block (or the
+// whole window), so the rows between Tk and R are the ones the KL form's last partly valid block computes — as queries
+// they can trigger that block's re-base, as keys they are never read. rowbase and R replace clip * T and T in the
+// Q-row clamp and the store guard; the query tiles per (clip, head) come from r_max, the call's longest segment. A
+// workgroup whose first query is >= R has no rows: it leaves before the first barrier and stores nothing. Everything
+// a query's bits depend on is the KL form's. Its own instantiation again.
+// The packed launcher (the variable-length encode): k_attn_t<true, NQB, true, true> over ceil(r_max / QWG) query tiles
+// per (clip, head) — the grid follows the call's longest segment, not the window — in the XCD-contiguous order of the
+// other forms; the 64-query form when the 128-query grid would leave CUs idle (the same bits).
+hipError_t q2a_launch_attention_varlen(const q2a_attn_args & a, hipStream_t s) {
+    if (a.D != a.H * 64 || a.bf16 || !a.v_rows || !a.vtl || !a.key_len || !a.row_start) return hipErrorInvalidValue;
+    if (a.n_clips <= 0 || a.r_max <= 0 || a.r_max > a.T) return hipErrorInvalidValue;
+    const int n2 = ((a.r_max + 127) / 128) * a.H * a.n_clips;
+    if (n2 < q2a_cu_count())
+        hipLaunchKernelGGL((k_attn_t<true, 1, true, true>), dim3(((a.r_max + 63) / 64) * a.H * a.n_clips), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_attn_t<true, 2, true, true>), dim3(n2), dim3(256), 0, s, a);
+    return hipGetLastError();
+}

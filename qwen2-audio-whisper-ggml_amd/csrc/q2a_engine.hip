@@ -736,13 +736,16 @@ struct q2a_engine {
     hipStream_t copy_stream = nullptr;
     host_buf hb[2];
     float * out_stage = nullptr;     // unused (outputs are written straight to the user buffer)
-    int32_t * meta = nullptr;        // device: nsamp | seek | clip_ok | clip_max | key_len (rows of the call's B)
+    int32_t * meta = nullptr;        // device: nsamp | seek | clip_ok | clip_max | key_len (rows of the call's B) |
+                                     //   row_start (B + 1 entries: the packed layout of the variable-length encode)
     int32_t * meta_host = nullptr;   // pinned
     hipEvent_t meta_evt = nullptr;   // last async upload out of meta_host (host rewrites wait on it)
     float * mel = nullptr;
     q2a_half * xc1 = nullptr;
     q2a_half * y1 = nullptr;
     float * X = nullptr;
+    float * Xp = nullptr;            // packed residual stream of the variable-length encode, [xp_clips * T][D]: its own
+    int xp_clips = 0;                //   allocation, made by the first such call (ensure_packed)
     q2a_half * actD = nullptr;
     q2a_half * actF = nullptr;
     float * dyD = nullptr;
@@ -817,8 +820,9 @@ int engine_adopt_header(q2a_engine * e) {
 void free_ws(q2a_engine * e) {
     if (e->ws) (void) hipFree(e->ws);
     if (e->meta_host) (void) hipHostFree(e->meta_host);
-    e->ws = nullptr; e->meta_host = nullptr;
-    e->cap_clips = 0; e->ws_bytes = 0;
+    if (e->Xp) (void) hipFree(e->Xp);
+    e->ws = nullptr; e->meta_host = nullptr; e->Xp = nullptr;
+    e->cap_clips = 0; e->ws_bytes = 0; e->xp_clips = 0;
 }
 
 void free_host_bufs(q2a_engine * e) {
@@ -880,7 +884,7 @@ int reserve(q2a_engine * e, int B) {
     const bool quant = e->blk != 0;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_meta = take((size_t) B * 5 * 4);
+    const size_t o_meta = take(((size_t) B * 6 + 1) * 4);
     const size_t o_mel = take((size_t) B * d.M * d.TM * 4);
     const size_t o_xc1 = take((size_t) B * (d.TM + 2) * 3 * d.M * 2);
     const size_t o_y1 = take((size_t) B * (d.TM + 1) * d.D * 2 * (e->f32 ? 2 : 1));
@@ -920,7 +924,7 @@ int reserve(q2a_engine * e, int B) {
         return Q2A_ERR_OOM;
     }
     HIP_TRY(hipMemsetAsync(ws, 0, off, e->stream));   // zero pad rows (xc1 rows 0/last, y1 row 0, V^T tail)
-    HIP_TRY(hipHostMalloc((void **) &e->meta_host, (size_t) B * 5 * 4, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **) &e->meta_host, ((size_t) B * 6 + 1) * 4, hipHostMallocDefault));
     uint8_t * b = (uint8_t *) ws;
     e->ws = ws; e->ws_bytes = off; e->cap_clips = B;
     e->meta = (int32_t *) (b + o_meta);
@@ -1006,17 +1010,27 @@ int ln_mode(const q2a_engine * e) { return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 
         }                                                                             \
     } while (0)
 
-// one pre-LN encoder block on X [B*T][D] (qwen2-whisper.cpp:2014-2155); key_len: device [B] per-clip key lengths of
-// the attention (the padded entry points), NULL = all T keys
-int run_block(q2a_engine * e, int l, int B, hipStream_t s, const int32_t * key_len = nullptr) {
+// the packed residual stream of a variable-length encode (q2a_varlen_rows): clip c's rows are row_start[c] ..
+// row_start[c+1]-1 of X [M_tot][D]
+struct packed_rows {
+    const int32_t * row_start;   // device [B + 1]
+    int r_max;                   // the longest segment (host)
+    float * X;                   // [M_tot][D]
+};
+
+// one pre-LN encoder block on M rows of D (qwen2-whisper.cpp:2014-2155): X [B*T][D] (M = B * T), or with pk the packed
+// rows pk->X [M][D] of B clips. key_len: device [B] per-clip key lengths of the attention (the padded and the
+// variable-length entry points), NULL = all T keys. Everything but the attention is a function of M alone (rows are
+// independent); dy_ld stays the workspace's stride.
+int run_block(q2a_engine * e, int l, int B, int M, hipStream_t s, const int32_t * key_len = nullptr, const packed_rows * pk = nullptr) {
     const dims & d = e->d;
-    const int M = B * d.T;
+    float * X = pk ? pk->X : e->X;
     const int mode = ln_mode(e);
     auto tap = [&](int i, const q2a_half * src, int K) -> hipError_t {
         if (!e->taps[i]) return hipSuccess;
         return hipMemcpyAsync(e->taps[i], src, (size_t) M * K * e->kx * 2, hipMemcpyDeviceToDevice, s);
     };
-    q2a_ln_args ln{e->X, M, d.D, e->lv<const float *>(l, L_LN1W), e->lv<const float *>(l, L_LN1B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
+    q2a_ln_args ln{X, M, d.D, e->lv<const float *>(l, L_LN1W), e->lv<const float *>(l, L_LN1B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
     PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln, s));
     LAUNCH(tap(0, e->actD, d.D));
     {
@@ -1034,8 +1048,14 @@ int run_block(q2a_engine * e, int l, int B, hipStream_t s, const int32_t * key_l
         at.vtl = e->vtl;
         at.v_rows = e->bf16 ? 0 : 1;
         at.key_len = key_len;
+        at.row_start = nullptr;
+        at.r_max = 0;
         if (mode == 0 || mode == 4) at.outH = e->actD; else at.outF = e->attF;
-        if (key_len) PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_len(at, s));
+        if (pk) {
+            at.row_start = pk->row_start;
+            at.r_max = pk->r_max;
+            PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_varlen(at, s));
+        } else if (key_len) PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_len(at, s));
         else PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention(at, s));
         if (mode == 3) {
             const int64_t n = (int64_t) M * d.D;
@@ -1049,11 +1069,11 @@ int run_block(q2a_engine * e, int l, int B, hipStream_t s, const int32_t * key_l
     {
         q2a_gemm_args a = gemm_base(e, l, 1, e->actD, M);
         a.bias = e->lv<const float *>(l, L_BO);
-        a.outF = e->X; a.ldo = d.D;
+        a.outF = X; a.ldo = d.D;
         a.part = e->part; a.split_stride = (int64_t) M * d.D;
         PLAUNCH(e, s, Q2A_PROF_GEMM_O, q2a_launch_gemm(a, Q2A_EPI_RESID, e->gblk, s));
     }
-    q2a_ln_args ln2{e->X, M, d.D, e->lv<const float *>(l, L_LN2W), e->lv<const float *>(l, L_LN2B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
+    q2a_ln_args ln2{X, M, d.D, e->lv<const float *>(l, L_LN2W), e->lv<const float *>(l, L_LN2B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
     PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln2, s));
     LAUNCH(tap(2, e->actD, d.D));
     {
@@ -1091,7 +1111,7 @@ int run_block(q2a_engine * e, int l, int B, hipStream_t s, const int32_t * key_l
     {
         q2a_gemm_args a = gemm_base(e, l, 3, e->actF, M);
         a.bias = e->lv<const float *>(l, L_B2);
-        a.outF = e->X; a.ldo = d.D;
+        a.outF = X; a.ldo = d.D;
         a.part = e->part; a.split_stride = (int64_t) M * d.D;
         PLAUNCH(e, s, Q2A_PROF_GEMM_FC2, q2a_launch_gemm(a, Q2A_EPI_RESID, e->gblk, s));
     }
@@ -1156,9 +1176,28 @@ int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int m
     return Q2A_OK;
 }
 
+// the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
+// clip_ok entry is 0 (clip_ok NULL: every clip has rows). row_start: B + 1 entries
+struct packed_layout {
+    int m_tot;   // rows of the packed stream (0: no clip is encoded)
+    int r_max;   // the longest segment
+};
+int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_t * clip_ok, int B, int32_t * row_start,
+                     packed_layout & pl) {
+    std::vector<int32_t> kl(key_len, key_len + B);
+    if (clip_ok)
+        for (int c = 0; c < B; ++c) if (!clip_ok[c]) kl[c] = 0;
+    const int64_t m = q2a_varlen_rows(kl.data(), B, e->d.T, row_start);
+    if (m < 0) { set_err("key lengths outside 0..%d", e->d.T); return Q2A_ERR_ARG; }
+    pl.m_tot = (int) m;
+    pl.r_max = 0;
+    for (int c = 0; c < B; ++c) pl.r_max = std::max(pl.r_max, row_start[c + 1] - row_start[c]);
+    return Q2A_OK;
+}
+
 // per-clip metadata (host): whisper_encoder_output_with_state's seek / too-short logic (:2356-2365)
 int prepare_meta(q2a_engine * e, const int32_t * n_samples, int B, int offset_ms, const int32_t * offs, int32_t * status, int & max_frames,
-                 int64_t max_valid, hipStream_t s, const int32_t * key_len = nullptr) {
+                 int64_t max_valid, hipStream_t s, const int32_t * key_len = nullptr, packed_layout * pl = nullptr) {
     int32_t * mh = e->meta_host;
     HIP_TRY(hipEventSynchronize(e->meta_evt));   // the previous call's upload out of mh may still be queued
     max_frames = 0;
@@ -1179,7 +1218,12 @@ int prepare_meta(q2a_engine * e, const int32_t * n_samples, int B, int offset_ms
     // device-written: run_frontend resets it after this copy, on the same stream)
     if (key_len)
         for (int c = 0; c < B; ++c) { mh[3 * B + c] = (int32_t) 0x80808080u; mh[4 * B + c] = key_len[c]; }
-    HIP_TRY(hipMemcpyAsync(e->meta, mh, (size_t) B * (key_len ? 5 : 3) * 4, hipMemcpyHostToDevice, s));
+    // the packed layout (the variable-length entry points): row_start behind the key lengths, still the same upload. A
+    // clip that is not encoded has no rows
+    if (pl) {
+        if (int rc = packed_layout_of(e, key_len, mh + 2 * B, B, mh + 5 * B, *pl)) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(e->meta, mh, (pl ? (size_t) B * 6 + 1 : (size_t) B * (key_len ? 5 : 3)) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(e->meta_evt, s));
     return Q2A_OK;
 }
@@ -1245,12 +1289,95 @@ int encode_padded_impl(q2a_engine * e, const float * pcm, int64_t stride, const 
     if (rc) return rc;
     const int32_t * kl_dev = e->meta + 4 * B;
     for (int l = 0; l < e->d.L; ++l) {
-        rc = run_block(e, l, B, s, kl_dev);
+        rc = run_block(e, l, B, B * e->d.T, s, kl_dev);
         if (rc) return rc;
     }
     q2a_pool_args pa{e->X, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, e->meta + 2 * B};
     PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
     PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(out, kl_dev, e->meta + 2 * B, B, e->d.TO, e->d.D, s));
+    return Q2A_OK;
+}
+
+// ---- variable-length encode: the blocks run on the valid rows only ------------------------------
+// key lengths and their packed layout of a test hook into the metadata's fifth and sixth rows (one copy; checks and
+// handshake as upload_key_len). Every clip has rows.
+int upload_varlen(q2a_engine * e, const int32_t * key_len, int B, hipStream_t s, packed_layout & pl) {
+    if (e->bf16) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    for (int c = 0; c < B; ++c)
+        if (key_len[c] < 1 || key_len[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, key_len[c], e->d.T); return Q2A_ERR_ARG; }
+    HIP_TRY(hipEventSynchronize(e->meta_evt));
+    memcpy(e->meta_host + 4 * B, key_len, (size_t) B * 4);
+    if (int rc = packed_layout_of(e, key_len, nullptr, B, e->meta_host + 5 * B, pl)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->meta + 4 * B, e->meta_host + 4 * B, ((size_t) B * 2 + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->meta_evt, s));
+    return Q2A_OK;
+}
+
+// the packed residual buffer, for as many clips as the workspace holds (its own allocation: engines that never run a
+// variable-length encode do not pay for it)
+int ensure_packed(q2a_engine * e) {
+    if (e->Xp && e->xp_clips >= e->cap_clips) return Q2A_OK;
+    HIP_TRY(hipDeviceSynchronize());   // earlier calls may still read the old buffer, on any stream
+    if (e->Xp) { (void) hipFree(e->Xp); e->Xp = nullptr; e->xp_clips = 0; }
+    const size_t bytes = (size_t) e->cap_clips * e->d.T * e->d.D * 4;
+    if (hipMalloc((void **) &e->Xp, bytes) != hipSuccess) {
+        (void) hipGetLastError();
+        e->Xp = nullptr;
+        set_err("packed residual allocation of %.2f GB for %d clips failed", bytes / 1e9, e->cap_clips);
+        return Q2A_ERR_OOM;
+    }
+    e->xp_clips = e->cap_clips;
+    return Q2A_OK;
+}
+
+// rows 0 .. seg_rows[c]-1 of clip c's window X [B][T][D] -> packed rows row_start[c] .. of Xp (whole rows, float4)
+__global__ void k_gather_rows(const float * X, float * Xp, const int32_t * row_start, int T, int D) {
+    const int c = blockIdx.y;
+    const int r0 = row_start[c], n4 = (row_start[c + 1] - r0) * (D / 4);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    ((float4 *) (Xp + (int64_t) r0 * D))[i] = ((const float4 *) (X + (int64_t) c * T * D))[i];
+}
+hipError_t launch_gather_rows(const float * X, float * Xp, const int32_t * row_start, int B, int T, int D, int r_max, hipStream_t s) {
+    if (D % 4 || r_max <= 0 || r_max > T) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_gather_rows, dim3((unsigned) (((int64_t) r_max * (D / 4) + 255) / 256), (unsigned) B), dim3(256), 0, s,
+                       X, Xp, row_start, T, D);
+    return hipGetLastError();
+}
+
+// encode_padded_impl on the packed rows: after the front end (full windows, unchanged) the valid rows of every clip
+// (each rounded up to the attention's 16-query block) are gathered into one [M_tot][D] stream, the blocks run on those
+// M_tot rows, and the pool + final LayerNorm reads them back into out [B][TO][D], zeros past each clip's valid length.
+// Row for row the padded encode's operations: the same bytes.
+int encode_varlen_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t * n_samples, int B, const int32_t * offs,
+                       const int32_t * kl, float * out, int32_t * out_len, int32_t * status, hipStream_t s) {
+    if (B <= 0 || !pcm || !n_samples || !out || !kl) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = reserve(e, B);
+    if (rc) return rc;
+    if ((rc = ensure_packed(e))) return rc;
+    std::vector<int32_t> st_local;
+    if (!status) { st_local.resize(B); status = st_local.data(); }
+    int max_frames = 0;
+    packed_layout pl{0, 0};
+    rc = prepare_meta(e, n_samples, B, 0, offs, status, max_frames, stride > 0 ? stride : -1, s, kl, &pl);
+    if (rc) return rc;
+    if (out_len) for (int c = 0; c < B; ++c) out_len[c] = status[c] == Q2A_CLIP_ENCODED ? kl[c] / 2 : 0;
+    const int32_t * kl_dev = e->meta + 4 * B;
+    const int32_t * rs_dev = e->meta + 5 * B;
+    if (pl.m_tot > 0) {   // (every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros)
+        rc = run_frontend(e, pcm, stride, B, max_frames, s);
+        if (rc) return rc;
+        PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, rs_dev, B, e->d.T, e->d.D, pl.r_max, s));
+        const packed_rows pk{rs_dev, pl.r_max, e->Xp};
+        for (int l = 0; l < e->d.L; ++l) {
+            rc = run_block(e, l, B, pl.m_tot, s, kl_dev, &pk);
+            if (rc) return rc;
+        }
+    }
+    q2a_pool_varlen_args pa{e->Xp, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, kl_dev, rs_dev};
+    PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
     return Q2A_OK;
 }
 
@@ -1267,7 +1394,7 @@ int encode_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t
     rc = run_frontend(e, pcm, stride, B, max_frames, s);
     if (rc) return rc;
     for (int l = 0; l < e->d.L; ++l) {
-        rc = run_block(e, l, B, s);
+        rc = run_block(e, l, B, B * e->d.T, s);
         if (rc) return rc;
     }
     q2a_pool_args pa{e->X, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, e->meta + 2 * B};
@@ -1437,7 +1564,7 @@ int q2a_get_info(const q2a_engine * e, q2a_info * info) {
     if (!e || !info) return Q2A_ERR_ARG;
     info->n_audio_ctx = e->d.T; info->n_audio_state = e->d.D; info->n_audio_head = e->d.H;
     info->n_audio_layer = e->d.L; info->n_mels = e->d.M; info->wtype = e->wtype; info->n_out = e->d.TO;
-    info->device = e->device; info->weight_bytes = e->blob_size; info->workspace_bytes = (int64_t) e->ws_bytes;
+    info->device = e->device; info->weight_bytes = e->blob_size; info->workspace_bytes = (int64_t) e->ws_bytes + (int64_t) e->xp_clips * e->d.T * e->d.D * 4;
     info->act = e->bf16 ? Q2A_ACT_BF16 : Q2A_ACT_REFERENCE;
     info->reserved = 0;
     return Q2A_OK;
@@ -1471,10 +1598,11 @@ int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n
 }
 
 // q2a_encode_host_ex, and with kl (host [n_clips] key lengths, already checked) q2a_encode_host_padded: every clip's
-// output is then copied back (rows past its valid length, and a skipped clip's rows, are zeros)
+// output is then copied back (rows past its valid length, and a skipped clip's rows, are zeros); varlen:
+// q2a_encode_host_varlen (each chunk of clips packed on its own)
 static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                             int n_clips, int offset_ms, float * out_host, int32_t * status, const int32_t * kl,
-                            int32_t * out_len) {
+                            int32_t * out_len, bool varlen = false) {
     if (!e || !pcm || !n_samples || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     for (int c = 0; c < n_clips; ++c)   // (checked before any copy: a negative count would be a huge memcpy)
         if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) {
@@ -1528,7 +1656,10 @@ static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int
             rc = Q2A_ERR_HIP;
             break;
         }
-        if (kl)
+        if (kl && varlen)
+            rc = encode_varlen_impl(e, b.d_in, maxn, n_samples + c0, n, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, b.d_out,
+                                    out_len ? out_len + c0 : nullptr, st.data() + c0, s);
+        else if (kl)
             rc = encode_padded_impl(e, b.d_in, maxn, n_samples + c0, n, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, b.d_out,
                                     out_len ? out_len + c0 : nullptr, st.data() + c0, s);
         else
@@ -1576,6 +1707,27 @@ int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int3
     std::vector<int32_t> kl;
     if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
     return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
+}
+
+int q2a_encode_device_varlen(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    std::vector<int32_t> kl;
+    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    return encode_varlen_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms, kl.data(), out_dev, out_len, status,
+                              call_stream(stream));
+}
+
+int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
+                           const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
+    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    std::vector<int32_t> kl;
+    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len, true);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -1704,7 +1856,7 @@ static int test_block_impl(q2a_engine * e, int layer, float * x, int n_clips, co
     if (with_len && (rc = upload_key_len(e, key_len, n_clips, s))) return rc;
     const size_t bytes = (size_t) n_clips * e->d.T * e->d.D * 4;
     HIP_TRY(hipMemcpyAsync(e->X, x, bytes, hipMemcpyDeviceToDevice, s));
-    rc = run_block(e, layer, n_clips, s, with_len ? e->meta + 4 * n_clips : nullptr);
+    rc = run_block(e, layer, n_clips, n_clips * e->d.T, s, with_len ? e->meta + 4 * n_clips : nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(x, e->X, bytes, hipMemcpyDeviceToDevice, s));
     return Q2A_OK;
@@ -1716,6 +1868,25 @@ int q2a_test_block(q2a_engine * e, int layer, float * x, int n_clips, void * str
 
 int q2a_test_block_len(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
     return test_block_impl(e, layer, x, n_clips, key_len, true, stream);
+}
+
+// one block on packed rows x [M_tot][D] (q2a_varlen_rows over key_len): the variable-length encode's block
+int q2a_test_block_varlen(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
+    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0 || !key_len || !x) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    int rc = reserve(e, n_clips);
+    if (rc) return rc;
+    packed_layout pl{0, 0};
+    if ((rc = upload_varlen(e, key_len, n_clips, s, pl))) return rc;
+    if ((rc = ensure_packed(e))) return rc;
+    const size_t bytes = (size_t) pl.m_tot * e->d.D * 4;
+    HIP_TRY(hipMemcpyAsync(e->Xp, x, bytes, hipMemcpyDeviceToDevice, s));
+    const packed_rows pk{e->meta + 5 * n_clips, pl.r_max, e->Xp};
+    rc = run_block(e, layer, n_clips, pl.m_tot, s, e->meta + 4 * n_clips, &pk);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(x, e->Xp, bytes, hipMemcpyDeviceToDevice, s));
+    return Q2A_OK;
 }
 
 int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void * const * taps, void * stream) {
@@ -1797,6 +1968,33 @@ int q2a_test_attention(q2a_engine * e, const float * q, const float * k, const f
 int q2a_test_attention_len(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
                            const int32_t * key_len, float * out, void * stream) {
     return test_attention_impl(e, q, k, v, n_clips, key_len, true, out, stream);
+}
+
+// attention only on packed rows: q, k, v, out [M_tot][D] (q2a_varlen_rows over key_len)
+int q2a_test_attention_varlen(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
+                              const int32_t * key_len, float * out, void * stream) {
+    if (!e || n_clips <= 0 || !key_len || !q || !k || !v || !out) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    int rc = reserve(e, n_clips);
+    if (rc) return rc;
+    packed_layout pl{0, 0};
+    if ((rc = upload_varlen(e, key_len, n_clips, s, pl))) return rc;
+    const dims & d = e->d;
+    const int64_t n = (int64_t) pl.m_tot * d.D;
+    const dim3 g((unsigned) ((n + 255) / 256)), b(256);
+    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, q, e->qh, e->ql, n, Q2A_LOG2E);
+    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, k, e->kh, e->kl, n, 1.0f);
+    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, v, e->vt, e->vtl, n, 1.0f);
+    LAUNCH(hipGetLastError());
+    q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, n_clips, d.T, d.D, d.H, e->TP, nullptr, out};
+    at.vtl = e->vtl;
+    at.v_rows = 1;
+    at.key_len = e->meta + 4 * n_clips;
+    at.row_start = e->meta + 5 * n_clips;
+    at.r_max = pl.r_max;
+    LAUNCH(q2a_launch_attention_varlen(at, s));
+    return Q2A_OK;
 }
 
 // ---- downstream consumer: the Qwen2-Audio multi-modal projector ---------------------------

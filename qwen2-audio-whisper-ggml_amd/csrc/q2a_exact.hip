@@ -535,16 +535,11 @@ __global__ __launch_bounds__(GQ_THREADS) void k_gelu_quant_q8k_h16(const q2a_hal
 }
 
 // AvgPool1d(k=2,s=2) over time (ggml.c:15077-15125: drow = 0; += a; += b; /= 2) + final LayerNorm -> f32
-__global__ __launch_bounds__(256) void k_pool_ln(const q2a_pool_args p) {
-    const int lane = threadIdx.x & 63;
-    const int TO = p.T / 2;
-    const int orow = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (orow >= p.n_clips * TO) return;
-    const int c = orow / TO, t = orow % TO;
-    if (!p.clip_ok[c]) return;
-    const float4 * a4 = (const float4 *) (p.X + ((int64_t) c * p.T + 2 * t) * p.D);
-    const float4 * b4 = (const float4 *) (p.X + ((int64_t) c * p.T + 2 * t + 1) * p.D);
-    const int nch = p.D / 4;
+// One output row by one wave: rows a4 / b4 of D floats pooled, normalised (lng, lnb) -> o4. Shared by the full-window
+// and the packed kernel, so both run the same operations in the same order.
+__device__ __forceinline__ void pool_ln_row(const float4 * a4, const float4 * b4, float4 * o4, int D, const float * lng,
+                                            const float * lnb, int lane) {
+    const int nch = D / 4;
     constexpr int MAXC = 8;
     float4 v[MAXC], bv[MAXC];
     // the rows' loads at clamped chunk indices (always readable) before any arithmetic: under the `ch < nch` branches
@@ -567,7 +562,7 @@ __global__ __launch_bounds__(256) void k_pool_ln(const q2a_pool_args p) {
         }
     }
     s = wave_sum_d(s);
-    const float mean = (float) (s / p.D);
+    const float mean = (float) (s / D);
     double s2 = 0.0;
 #pragma unroll
     for (int u = 0; u < MAXC; ++u) {
@@ -579,13 +574,12 @@ __global__ __launch_bounds__(256) void k_pool_ln(const q2a_pool_args p) {
         }
     }
     s2 = wave_sum_d(s2);
-    const float scale = 1.0f / sqrtf((float) (s2 / p.D) + 1e-5f);
-    float4 * o4 = (float4 *) (p.out + ((int64_t) c * TO + t) * p.D);
+    const float scale = 1.0f / sqrtf((float) (s2 / D) + 1e-5f);
     // affine operands likewise (clamped, all in flight), then the stores
 #pragma unroll
     for (int u = 0; u < MAXC; ++u) {
         const int ch = min(lane + 64 * u, nch - 1);
-        const float4 gg = ((const float4 *) p.g)[ch], bb = ((const float4 *) p.b)[ch];
+        const float4 gg = ((const float4 *) lng)[ch], bb = ((const float4 *) lnb)[ch];
         float4 y;
         y.x = (v[u].x * scale) * gg.x + bb.x;
         y.y = (v[u].y * scale) * gg.y + bb.y;
@@ -598,6 +592,37 @@ __global__ __launch_bounds__(256) void k_pool_ln(const q2a_pool_args p) {
         const int ch = lane + 64 * u;
         if (ch < nch) o4[ch] = v[u];
     }
+}
+
+__global__ __launch_bounds__(256) void k_pool_ln(const q2a_pool_args p) {
+    const int lane = threadIdx.x & 63;
+    const int TO = p.T / 2;
+    const int orow = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (orow >= p.n_clips * TO) return;
+    const int c = orow / TO, t = orow % TO;
+    if (!p.clip_ok[c]) return;
+    const float4 * a4 = (const float4 *) (p.X + ((int64_t) c * p.T + 2 * t) * p.D);
+    const float4 * b4 = (const float4 *) (p.X + ((int64_t) c * p.T + 2 * t + 1) * p.D);
+    pool_ln_row(a4, b4, (float4 *) (p.out + ((int64_t) c * TO + t) * p.D), p.D, p.g, p.b, lane);
+}
+
+// k_pool_ln from a packed residual stream: clip c's rows start at row_start[c]; output rows >= key_len[c] / 2 (every
+// row of a clip with no packed rows) are zeros
+__global__ __launch_bounds__(256) void k_pool_ln_varlen(const q2a_pool_varlen_args p) {
+    const int lane = threadIdx.x & 63;
+    const int TO = p.T / 2;
+    const int orow = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (orow >= p.n_clips * TO) return;
+    const int c = orow / TO, t = orow % TO;
+    const int r0 = p.row_start[c], R = p.row_start[c + 1] - r0;
+    float4 * o4 = (float4 *) (p.out + ((int64_t) c * TO + t) * p.D);
+    if (2 * t + 1 >= min(p.key_len[c], R)) {   // t >= key_len / 2
+        for (int ch = lane; ch < p.D / 4; ch += 64) o4[ch] = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float4 * a4 = (const float4 *) (p.X + ((int64_t) r0 + 2 * t) * p.D);
+    const float4 * b4 = (const float4 *) (p.X + ((int64_t) r0 + 2 * t + 1) * p.D);
+    pool_ln_row(a4, b4, o4, p.D, p.g, p.b, lane);
 }
 
 }  // namespace
@@ -693,5 +718,11 @@ hipError_t q2a_launch_quant_act(const q2a_quant_args & a, hipStream_t s) {
 hipError_t q2a_launch_pool_ln(const q2a_pool_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pool_ln, dim3((a.n_clips * (a.T / 2) + 3) / 4), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t s) {
+    if (a.D % 4 != 0 || a.D > 2048 || !a.key_len || !a.row_start) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_ln_varlen, dim3((a.n_clips * (a.T / 2) + 3) / 4), dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -141,7 +141,12 @@ struct q2a_attn_args {
                             //   kernel reads its P.V operand by transposing LDS reads), 0 = V^T [clip][head][64][TP]
     const int32_t * key_len;   // device [n_clips]: clip c attends to keys 0 .. key_len[c]-1 only (1 <= key_len[c] <= T; rows
                                //   past it of K and V are never read). NULL = every clip attends to all T keys. Reference
-                               //   contract with v_rows only; read by q2a_launch_attention_len alone. Stays the last field
+                               //   contract with v_rows only; read by q2a_launch_attention_len (and _varlen) alone
+    // the packed (variable-length) form, read by q2a_launch_attention_varlen alone; appended behind key_len, the last
+    // field q2a_launch_attention_len reads. New fields go behind these.
+    const int32_t * row_start;   // device [n_clips + 1]: clip c's rows of q / k / v / out are row_start[c] .. row_start[c+1]-1
+                                 //   of one packed [M_tot][D] array (q2a_varlen_rows; 0 rows: no workgroup does anything)
+    int r_max;                   // the call's longest segment max_c(row_start[c+1] - row_start[c]): the grid's extent
 };
 // Reference contract (bf16 == 0): qh/ql hold Q * Q2A_LOG2E (after the 1/sqrt(dh) scale), split hi/lo — the kernel
 // works in log2 units (P = exp2(S' - m')); every producer (QKV epilogue qscale, ggml backend prep, test entry) folds it.
@@ -151,6 +156,9 @@ constexpr float Q2A_LOG2E = 1.4426950408889634f;
 // struct before that still calls it) and never masks; q2a_launch_attention_len honours key_len (NULL: the same launch)
 hipError_t q2a_launch_attention(const q2a_attn_args & a, hipStream_t s);
 hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s);
+// the packed form (k_attn_t<true, NQB, true, true>): key_len and row_start set, r_max >= 1; T is the window length the
+// segments were cut from (key_len[c] <= T). The grid covers ceil(r_max / 128 or 64) query tiles per (clip, head)
+hipError_t q2a_launch_attention_varlen(const q2a_attn_args & a, hipStream_t s);
 // true when this build's reference-contract attention reads a V^T lo image (the QKV epilogue must then write it)
 bool q2a_attention_wants_vlo();
 
@@ -233,3 +241,16 @@ struct q2a_pool_args {
     const int32_t * clip_ok;   // [clips] 1 = write output, 0 = leave untouched (reference early return)
 };
 hipError_t q2a_launch_pool_ln(const q2a_pool_args & a, hipStream_t s);
+// The same from a packed residual stream (q2a_varlen_rows): output row t < key_len[c] / 2 of clip c pools packed rows
+// row_start[c] + 2t, + 1 with k_pool_ln's operations in its order; every other row of out (rows past the valid length,
+// every row of a clip with no packed rows) is written as zeros, so the call writes the whole [clips][T/2][D] buffer.
+struct q2a_pool_varlen_args {
+    const float * X;             // [M_tot][D] packed
+    int n_clips, T, D;
+    const float * g;
+    const float * b;
+    float * out;
+    const int32_t * key_len;     // device [clips]
+    const int32_t * row_start;   // device [clips + 1]
+};
+hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t s);

@@ -26,6 +26,8 @@ EXPORTS = (
     "q2a_group_encode_host", "q2a_group_setup_times", "q2a_group_open_with", "q2a_whisper_context_engine",
     "q2a_valid_lengths", "q2a_encode_device_padded", "q2a_encode_host_padded", "q2a_test_attention_len",
     "q2a_test_block_len",
+    "q2a_varlen_rows", "q2a_encode_device_varlen", "q2a_encode_host_varlen", "q2a_test_attention_varlen",
+    "q2a_test_block_varlen",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -112,9 +114,17 @@ def lib() -> C.CDLL:
         for name, at in (("q2a_encode_device_padded", [vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, vp, i32p, i32p, vp]),
                          ("q2a_encode_host_padded", [vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, i32p, i32p]),
                          ("q2a_test_attention_len", [vp, vp, vp, vp, C.c_int, i32p, vp, vp]),
-                         ("q2a_test_block_len", [vp, C.c_int, vp, C.c_int, i32p, vp])):
+                         ("q2a_test_block_len", [vp, C.c_int, vp, C.c_int, i32p, vp]),
+                         # the variable-length family: the padded family's argument lists
+                         ("q2a_encode_device_varlen", [vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, vp, i32p, i32p, vp]),
+                         ("q2a_encode_host_varlen", [vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, i32p, i32p]),
+                         ("q2a_test_attention_varlen", [vp, vp, vp, vp, C.c_int, i32p, vp, vp]),
+                         ("q2a_test_block_varlen", [vp, C.c_int, vp, C.c_int, i32p, vp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = at
+        if hasattr(L, "q2a_varlen_rows"):
+            L.q2a_varlen_rows.restype = C.c_int64
+            L.q2a_varlen_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -203,7 +213,7 @@ class Engine:
         return out, st
 
     def encode_device_padded(self, pcm_ptr: int, pcm_stride: int, n_samples, out_ptr: int, offsets_ms=None, key_len=None,
-                             stream: int | None = None):
+                             stream: int | None = None, _fn: str = "q2a_encode_device_padded"):
         """q2a_encode_device_padded: per-clip key lengths in every block's attention (key_len=None: valid_lengths'
         enc_len of each clip), output rows >= out_len written as zeros. Returns (out_len, status)."""
         i32p = C.POINTER(C.c_int32)
@@ -215,15 +225,22 @@ class Engine:
             raise ValueError(f"offsets_ms / key_len need {n} entries")
         st = np.full(n, -1, dtype=np.int32)
         ol = np.zeros(n, dtype=np.int32)
-        _check(lib().q2a_encode_device_padded(self.h, C.c_void_p(pcm_ptr), C.c_int64(pcm_stride), ns.ctypes.data_as(i32p),
-                                              offs.ctypes.data_as(i32p) if offs is not None else None,
-                                              kl.ctypes.data_as(i32p) if kl is not None else None, n,
-                                              C.c_void_p(out_ptr), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
-                                              C.c_void_p(stream) if stream else None))
+        _check(getattr(lib(), _fn)(self.h, C.c_void_p(pcm_ptr), C.c_int64(pcm_stride), ns.ctypes.data_as(i32p),
+                                   offs.ctypes.data_as(i32p) if offs is not None else None,
+                                   kl.ctypes.data_as(i32p) if kl is not None else None, n,
+                                   C.c_void_p(out_ptr), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
+                                   C.c_void_p(stream) if stream else None))
         return ol, st
 
+    def encode_device_varlen(self, pcm_ptr: int, pcm_stride: int, n_samples, out_ptr: int, offsets_ms=None, key_len=None,
+                             stream: int | None = None):
+        """q2a_encode_device_varlen: encode_device_padded's arguments, results and output bytes, with the encoder
+        blocks run on the clips' valid rows only (packed per varlen_rows). Returns (out_len, status)."""
+        return self.encode_device_padded(pcm_ptr, pcm_stride, n_samples, out_ptr, offsets_ms=offsets_ms, key_len=key_len,
+                                         stream=stream, _fn="q2a_encode_device_varlen")
+
     def encode_host_padded(self, clips, offsets_ms=None, key_len=None, out: np.ndarray | None = None,
-                           return_status: bool = False):
+                           return_status: bool = False, _fn: str = "q2a_encode_host_padded"):
         """q2a_encode_host_padded over host PCM clips -> (out, out_len) (with return_status: (out, out_len, status))."""
         i32p = C.POINTER(C.c_int32)
         clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
@@ -238,11 +255,17 @@ class Engine:
             raise ValueError(f"offsets_ms / key_len need {n} entries")
         st = np.full(n, -1, dtype=np.int32)
         ol = np.zeros(n, dtype=np.int32)
-        _check(lib().q2a_encode_host_padded(self.h, ptrs, ns.ctypes.data_as(i32p),
-                                            offs.ctypes.data_as(i32p) if offs is not None else None,
-                                            kl.ctypes.data_as(i32p) if kl is not None else None, n,
-                                            C.c_void_p(out.ctypes.data), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p)))
+        _check(getattr(lib(), _fn)(self.h, ptrs, ns.ctypes.data_as(i32p),
+                                   offs.ctypes.data_as(i32p) if offs is not None else None,
+                                   kl.ctypes.data_as(i32p) if kl is not None else None, n,
+                                   C.c_void_p(out.ctypes.data), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p)))
         return (out, ol, st) if return_status else (out, ol)
+
+    def encode_host_varlen(self, clips, offsets_ms=None, key_len=None, out: np.ndarray | None = None,
+                           return_status: bool = False):
+        """q2a_encode_host_varlen: encode_host_padded's arguments, results and output bytes on the packed rows."""
+        return self.encode_host_padded(clips, offsets_ms=offsets_ms, key_len=key_len, out=out, return_status=return_status,
+                                       _fn="q2a_encode_host_varlen")
 
     def pcm_to_mel(self, pcm: np.ndarray) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
@@ -298,21 +321,57 @@ class Engine:
         _check(lib().q2a_test_block_len(self.h, layer, C.c_void_p(x_ptr), n_clips,
                                         kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream) if stream else None))
 
+    # the same two on packed rows (varlen_rows over key_len): q, k, v, out and x are [M_tot][D]
+    def test_attention_varlen(self, q_ptr, k_ptr, v_ptr, n_clips, key_len, out_ptr, stream=None):
+        kl = np.ascontiguousarray(key_len, dtype=np.int32)
+        assert len(kl) == n_clips
+        _check(lib().q2a_test_attention_varlen(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
+                                               kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out_ptr),
+                                               C.c_void_p(stream) if stream else None))
+
+    def test_block_varlen(self, layer, x_ptr, n_clips, key_len, stream=None):
+        kl = np.ascontiguousarray(key_len, dtype=np.int32)
+        assert len(kl) == n_clips
+        _check(lib().q2a_test_block_varlen(self.h, layer, C.c_void_p(x_ptr), n_clips,
+                                           kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream) if stream else None))
+
 
 _host_lib = None
 
 
-def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
-    """(enc_len, out_len): the valid encoder positions and output vectors of a clip of n_samples samples encoded from
-    offset_ms (q2a_valid_lengths). Host arithmetic through lib/libq2a_host.so: needs no GPU."""
+def _host() -> C.CDLL:
+    """lib/libq2a_host.so: host arithmetic, needs no GPU."""
     global _host_lib
     if _host_lib is None:
         if not os.path.exists(HOST_LIB_PATH):
             raise Q2AError(f"{HOST_LIB_PATH} not built; run `make -C {PKG_DIR} host`")
         _host_lib = C.CDLL(HOST_LIB_PATH)
         _host_lib.q2a_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        _host_lib.q2a_varlen_rows.restype = C.c_int64
+        _host_lib.q2a_varlen_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    return _host_lib
+
+
+def varlen_rows(key_len, n_audio_ctx: int = 1500) -> tuple[int, np.ndarray]:
+    """(M_tot, row_start): the packed layout of the variable-length encode (q2a_varlen_rows) — clip c occupies rows
+    row_start[c] .. row_start[c+1]-1 (its key length rounded up to 16, inside the window; none for key length 0) of
+    M_tot = row_start[-1] rows. Host arithmetic through lib/libq2a_host.so: needs no GPU."""
+    kl = np.ascontiguousarray(key_len, dtype=np.int32)
+    rs = np.zeros(len(kl) + 1, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    m = _host().q2a_varlen_rows(kl.ctypes.data_as(i32p), len(kl), n_audio_ctx, rs.ctypes.data_as(i32p))
+    if m < 0:
+        err = Q2AError(f"q2a error {m}: invalid arguments to q2a_varlen_rows")
+        err.rc = int(m)
+        raise err
+    return int(m), rs
+
+
+def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
+    """(enc_len, out_len): the valid encoder positions and output vectors of a clip of n_samples samples encoded from
+    offset_ms (q2a_valid_lengths). Host arithmetic through lib/libq2a_host.so: needs no GPU."""
     a, b = C.c_int32(), C.c_int32()
-    rc = _host_lib.q2a_valid_lengths(n_samples, offset_ms, n_audio_ctx, C.byref(a), C.byref(b))
+    rc = _host().q2a_valid_lengths(n_samples, offset_ms, n_audio_ctx, C.byref(a), C.byref(b))
     if rc != 0:
         err = Q2AError(f"q2a error {rc}: invalid arguments to q2a_valid_lengths")
         err.rc = rc
