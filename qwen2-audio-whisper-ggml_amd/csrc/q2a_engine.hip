@@ -723,7 +723,6 @@ struct q2a_engine {
 
     // workspace (capacity)
     int cap_clips = 0;
-    int64_t cap_samples = 0;
     void * ws = nullptr;
     size_t ws_bytes = 0;
     // host API (q2a_encode_host*): a copy stream and two sets of pinned + device staging buffers, so the PCIe copies
@@ -735,10 +734,8 @@ struct q2a_engine {
     };
     hipStream_t copy_stream = nullptr;
     host_buf hb[2];
-    float * out_stage = nullptr;     // unused (outputs are written straight to the user buffer)
-    int32_t * meta = nullptr;        // device: nsamp | seek | clip_ok | clip_max | key_len (rows of the call's B) |
-                                     //   row_start (B + 1 entries: the packed layout of the variable-length encode)
-    int32_t * meta_host = nullptr;   // pinned
+    int32_t * meta = nullptr;        // device: the per-clip metadata of a call, addressed through meta_rows
+    int32_t * meta_host = nullptr;   // pinned, the same layout: written and uploaded by upload_meta alone
     hipEvent_t meta_evt = nullptr;   // last async upload out of meta_host (host rewrites wait on it)
     float * mel = nullptr;
     q2a_half * xc1 = nullptr;
@@ -792,6 +789,30 @@ namespace {
 // outputs read on stream 0 need no extra synchronisation. (Round 5 ran it on the handle's own stream between two
 // cross-stream events: 0.2 ms per encode at one clip, diag/null_stream_ab.py, profiles/r06e_null_stream.jsonl.)
 inline hipStream_t call_stream(const void * stream) { return (hipStream_t) stream; }
+
+// The per-clip metadata of a call, on the device (e->meta) and pinned on the host (e->meta_host): five rows of the
+// call's B entries, then row_start with B + 1 entries (the packed layout of the variable-length encode). clip_max is
+// written on the device (the mel kernel's running maximum); every other row comes from the host through upload_meta.
+constexpr size_t meta_words(int B) { return (size_t) B * 6 + 1; }
+struct meta_rows {
+    int32_t *nsamp, *seek, *clip_ok, *clip_max, *key_len, *row_start, *end;
+    meta_rows(int32_t * p, int B)
+        : nsamp(p), seek(p + B), clip_ok(p + 2 * B), clip_max(p + 3 * B), key_len(p + 4 * B), row_start(p + 5 * B),
+          end(p + meta_words(B)) {}
+};
+
+// The one writer of meta_host. It waits until the previous upload has left the pinned buffer (a queued copy may still
+// read it), lets `fill` write the host rows first .. last (a failing `fill` uploads nothing), copies exactly those words
+// to the same rows of e->meta on s, and records the event the next writer waits on.
+template <class Fill>
+int upload_meta(q2a_engine * e, int B, int32_t * meta_rows::*first, int32_t * meta_rows::*last, hipStream_t s, Fill fill) {
+    const meta_rows host(e->meta_host, B), dev(e->meta, B);
+    HIP_TRY(hipEventSynchronize(e->meta_evt));
+    if (int rc = fill(host)) return rc;
+    HIP_TRY(hipMemcpyAsync(dev.*first, host.*first, (size_t) (host.*last - host.*first) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->meta_evt, s));
+    return Q2A_OK;
+}
 
 int engine_init(q2a_engine * e, int device) {
     int n = 0;
@@ -884,7 +905,7 @@ int reserve(q2a_engine * e, int B) {
     const bool quant = e->blk != 0;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_meta = take(((size_t) B * 6 + 1) * 4);
+    const size_t o_meta = take(meta_words(B) * 4);
     const size_t o_mel = take((size_t) B * d.M * d.TM * 4);
     const size_t o_xc1 = take((size_t) B * (d.TM + 2) * 3 * d.M * 2);
     const size_t o_y1 = take((size_t) B * (d.TM + 1) * d.D * 2 * (e->f32 ? 2 : 1));
@@ -924,7 +945,7 @@ int reserve(q2a_engine * e, int B) {
         return Q2A_ERR_OOM;
     }
     HIP_TRY(hipMemsetAsync(ws, 0, off, e->stream));   // zero pad rows (xc1 rows 0/last, y1 row 0, V^T tail)
-    HIP_TRY(hipHostMalloc((void **) &e->meta_host, ((size_t) B * 6 + 1) * 4, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void **) &e->meta_host, meta_words(B) * 4, hipHostMallocDefault));
     uint8_t * b = (uint8_t *) ws;
     e->ws = ws; e->ws_bytes = off; e->cap_clips = B;
     e->meta = (int32_t *) (b + o_meta);
@@ -1010,21 +1031,30 @@ int ln_mode(const q2a_engine * e) { return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 
         }                                                                             \
     } while (0)
 
-// the packed residual stream of a variable-length encode (q2a_varlen_rows): clip c's rows are row_start[c] ..
-// row_start[c+1]-1 of X [M_tot][D]
-struct packed_rows {
-    const int32_t * row_start;   // device [B + 1]
-    int r_max;                   // the longest segment (host)
-    float * X;                   // [M_tot][D]
+// the residual rows an encoder block runs on: the windows X [B*T][D] (M = B * T), or with row_start the packed stream
+// of a variable-length encode (q2a_varlen_rows), X [M][D] with clip c's rows row_start[c] .. row_start[c+1]-1
+struct block_rows {
+    int B, M;
+    float * X;
+    const int32_t * key_len;     // device [B]: per-clip key lengths of the attention, NULL = all T keys
+    const int32_t * row_start;   // device [B + 1], NULL = windows
+    int r_max;                   // the longest packed segment (host)
 };
 
-// one pre-LN encoder block on M rows of D (qwen2-whisper.cpp:2014-2155): X [B*T][D] (M = B * T), or with pk the packed
-// rows pk->X [M][D] of B clips. key_len: device [B] per-clip key lengths of the attention (the padded and the
-// variable-length entry points), NULL = all T keys. Everything but the attention is a function of M alone (rows are
-// independent); dy_ld stays the workspace's stride.
-int run_block(q2a_engine * e, int l, int B, int M, hipStream_t s, const int32_t * key_len = nullptr, const packed_rows * pk = nullptr) {
+// the attention of `rows`: packed rows take the packed kernel, key lengths alone the key-length one, neither the plain one
+hipError_t launch_attention(q2a_attn_args & at, const block_rows & rows, hipStream_t s) {
+    at.key_len = rows.key_len;
+    at.row_start = rows.row_start;
+    at.r_max = rows.r_max;
+    return rows.row_start ? q2a_launch_attention_varlen(at, s) : rows.key_len ? q2a_launch_attention_len(at, s) : q2a_launch_attention(at, s);
+}
+
+// one pre-LN encoder block on the M rows of `rows` (qwen2-whisper.cpp:2014-2155). Everything but the attention is a
+// function of M alone (rows are independent); dy_ld stays the workspace's stride.
+int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
     const dims & d = e->d;
-    float * X = pk ? pk->X : e->X;
+    const int M = rows.M;
+    float * X = rows.X;
     const int mode = ln_mode(e);
     auto tap = [&](int i, const q2a_half * src, int K) -> hipError_t {
         if (!e->taps[i]) return hipSuccess;
@@ -1044,19 +1074,11 @@ int run_block(q2a_engine * e, int l, int B, int M, hipStream_t s, const int32_t 
         PLAUNCH(e, s, Q2A_PROF_GEMM_QKV, q2a_launch_gemm(a, Q2A_EPI_QKV, e->gblk, s));
     }
     {
-        q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, B, d.T, d.D, d.H, e->TP, nullptr, nullptr, e->bf16 ? 1 : 0};
+        q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, rows.B, d.T, d.D, d.H, e->TP, nullptr, nullptr, e->bf16 ? 1 : 0};
         at.vtl = e->vtl;
         at.v_rows = e->bf16 ? 0 : 1;
-        at.key_len = key_len;
-        at.row_start = nullptr;
-        at.r_max = 0;
         if (mode == 0 || mode == 4) at.outH = e->actD; else at.outF = e->attF;
-        if (pk) {
-            at.row_start = pk->row_start;
-            at.r_max = pk->r_max;
-            PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_varlen(at, s));
-        } else if (key_len) PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention_len(at, s));
-        else PLAUNCH(e, s, Q2A_PROF_ATTN, q2a_launch_attention(at, s));
+        PLAUNCH(e, s, Q2A_PROF_ATTN, launch_attention(at, rows, s));
         if (mode == 3) {
             const int64_t n = (int64_t) M * d.D;
             PLAUNCH(e, s, Q2A_PROF_QUANT, launch_split3(e->attF, e->actD, d.D, n, s));
@@ -1130,20 +1152,25 @@ int ensure_frange(q2a_engine * e, hipStream_t s) {
     return Q2A_OK;
 }
 
+// the mel kernel's arguments for the B clips described by the device rows `dev` (after ensure_frange)
+q2a_mel_args mel_args(const q2a_engine * e, const float * pcm, int64_t stride, const meta_rows & dev, int B, int max_frames) {
+    const dims & d = e->d;
+    q2a_mel_args ma;
+    ma.pcm = pcm; ma.pcm_stride = stride; ma.n_samples = dev.nsamp; ma.seek = dev.seek; ma.n_clips = B;
+    ma.n_mel = d.M; ma.n_bins = 201; ma.n_frames_win = d.TM; ma.max_frames = max_frames;
+    ma.filters = e->g<const float *>(G_FILT); ma.tab = e->g<const float *>(G_TAB);
+    ma.frange = e->frange;
+    ma.mel = e->mel; ma.clip_max = dev.clip_max; ma.xc1 = e->xc1; ma.xc_f32 = e->f32 ? 1 : 0;
+    return ma;
+}
+
 // mel + conv frontend: PCM -> X [B*T][D] (conv graph qwen2-whisper.cpp:1892-1952 + pe add :2005)
 int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int max_frames, hipStream_t s) {
     const dims & d = e->d;
-    int32_t * nsamp = e->meta;
-    int32_t * seek = e->meta + B;
-    int32_t * cmax = e->meta + 3 * B;
-    LAUNCH(hipMemsetAsync(cmax, 0x80, (size_t) B * 4, s));
-    q2a_mel_args ma;
-    ma.pcm = pcm; ma.pcm_stride = stride; ma.n_samples = nsamp; ma.seek = seek; ma.n_clips = B;
-    ma.n_mel = d.M; ma.n_bins = 201; ma.n_frames_win = d.TM; ma.max_frames = max_frames;
-    ma.filters = e->g<const float *>(G_FILT); ma.tab = e->g<const float *>(G_TAB);
+    const meta_rows dev(e->meta, B);
+    LAUNCH(hipMemsetAsync(dev.clip_max, 0x80, (size_t) B * 4, s));
     if (int rc = ensure_frange(e, s)) return rc;
-    ma.frange = e->frange;
-    ma.mel = e->mel; ma.clip_max = cmax; ma.xc1 = e->xc1; ma.xc_f32 = e->f32 ? 1 : 0;
+    const q2a_mel_args ma = mel_args(e, pcm, stride, dev, B, max_frames);
     PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel(ma, s));
     const int P1 = 3, P2 = e->f32 ? 2 : 1;   // operand parts per mel row / per conv1 output row
     // both convs sum each 64-deep K-step's MFMA partial in f64 (Q2A_BLK_EXACT): within rounding of the exact dot
@@ -1176,68 +1203,91 @@ int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int m
     return Q2A_OK;
 }
 
-// the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
-// clip_ok entry is 0 (clip_ok NULL: every clip has rows). row_start: B + 1 entries
-struct packed_layout {
-    int m_tot;   // rows of the packed stream (0: no clip is encoded)
-    int r_max;   // the longest segment
+// the three encode families: q2a_encode_device / _host (all T keys), the padded entry points (per-clip key lengths in
+// the attention, the blocks on all B*T rows) and the variable-length ones (the blocks on the packed valid rows)
+enum encode_kind { ENC_PLAIN, ENC_PADDED, ENC_PACKED };
+
+// the arguments of one encode: B clips in device memory, host arrays of B entries
+struct encode_call {
+    const float * pcm;
+    int64_t stride;             // 0: every clip reads the same PCM
+    const int32_t * n_samples;
+    int B;
+    int offset_ms;
+    const int32_t * offs;       // per-clip offsets, NULL = offset_ms for every clip
+    const int32_t * kl;         // key lengths, checked by padded_key_lens (ENC_PADDED, ENC_PACKED)
+    float * out;                // device [B][TO][D]
+    int32_t * out_len;          // NULL, or the clips' valid output rows (ENC_PADDED, ENC_PACKED)
+    int32_t * status;           // NULL, or Q2A_CLIP_* per clip
 };
-int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_t * clip_ok, int B, int32_t * row_start,
-                     packed_layout & pl) {
+
+// the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
+// clip_ok entry is 0 (clip_ok NULL: every clip has rows). Writes row_start (rows.B + 1 entries), rows.M (0: no clip is
+// encoded) and rows.r_max
+int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_t * clip_ok, int32_t * row_start, block_rows & rows) {
+    const int B = rows.B;
     std::vector<int32_t> kl(key_len, key_len + B);
     if (clip_ok)
         for (int c = 0; c < B; ++c) if (!clip_ok[c]) kl[c] = 0;
     const int64_t m = q2a_varlen_rows(kl.data(), B, e->d.T, row_start);
     if (m < 0) { set_err("key lengths outside 0..%d", e->d.T); return Q2A_ERR_ARG; }
-    pl.m_tot = (int) m;
-    pl.r_max = 0;
-    for (int c = 0; c < B; ++c) pl.r_max = std::max(pl.r_max, row_start[c + 1] - row_start[c]);
+    rows.M = (int) m;
+    rows.r_max = 0;
+    for (int c = 0; c < B; ++c) rows.r_max = std::max(rows.r_max, row_start[c + 1] - row_start[c]);
     return Q2A_OK;
 }
 
-// per-clip metadata (host): whisper_encoder_output_with_state's seek / too-short logic (:2356-2365)
-int prepare_meta(q2a_engine * e, const int32_t * n_samples, int B, int offset_ms, const int32_t * offs, int32_t * status, int & max_frames,
-                 int64_t max_valid, hipStream_t s, const int32_t * key_len = nullptr, packed_layout * pl = nullptr) {
-    int32_t * mh = e->meta_host;
-    HIP_TRY(hipEventSynchronize(e->meta_evt));   // the previous call's upload out of mh may still be queued
+// per-clip metadata (host): whisper_encoder_output_with_state's seek / too-short logic (:2356-2365), uploaded in one
+// copy with what the kind adds: 3 B words (plain), 5 B with the key lengths (padded), 6 B + 1 with their packed layout
+// (packed). `rows` receives what the blocks of the call run on.
+int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s, int & max_frames, block_rows & rows) {
+    const int B = c.B;
+    const int64_t max_valid = c.stride > 0 ? c.stride : -1;   // stride 0: shared PCM
+    const meta_rows dev(e->meta, B);
+    rows = block_rows{B, B * e->d.T, e->X, kind == ENC_PLAIN ? nullptr : dev.key_len, nullptr, 0};
     max_frames = 0;
-    for (int c = 0; c < B; ++c) {
-        const int seek = (offs ? offs[c] : offset_ms) / 10;
-        if (seek < 0) { set_err("clip %d: negative offset", c); return Q2A_ERR_ARG; }
-        const int n = n_samples[c];
-        if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", c, n); return Q2A_ERR_ARG; }
-        const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
-        const bool ok = n > 200 && (e->force_encode || !(n_len_org < seek + 100));
-        mh[c] = ok ? n : 0;
-        mh[B + c] = seek;
-        mh[2 * B + c] = ok ? 1 : 0;
-        if (status) status[c] = ok ? Q2A_CLIP_ENCODED : Q2A_CLIP_SKIPPED;
-        max_frames = std::max(max_frames, (int) (((int64_t) mh[c] + 480000) / 160));
-    }
-    // key lengths (the padded entry points): the fifth row, in the same upload (the clip_max row between is
-    // device-written: run_frontend resets it after this copy, on the same stream)
-    if (key_len)
-        for (int c = 0; c < B; ++c) { mh[3 * B + c] = (int32_t) 0x80808080u; mh[4 * B + c] = key_len[c]; }
-    // the packed layout (the variable-length entry points): row_start behind the key lengths, still the same upload. A
-    // clip that is not encoded has no rows
-    if (pl) {
-        if (int rc = packed_layout_of(e, key_len, mh + 2 * B, B, mh + 5 * B, *pl)) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(e->meta, mh, (pl ? (size_t) B * 6 + 1 : (size_t) B * (key_len ? 5 : 3)) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->meta_evt, s));
-    return Q2A_OK;
+    const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start : &meta_rows::end;
+    return upload_meta(e, B, &meta_rows::nsamp, last, s, [&](const meta_rows & mh) -> int {
+        for (int i = 0; i < B; ++i) {
+            const int seek = (c.offs ? c.offs[i] : c.offset_ms) / 10;
+            if (seek < 0) { set_err("clip %d: negative offset", i); return Q2A_ERR_ARG; }
+            const int n = c.n_samples[i];
+            if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", i, n); return Q2A_ERR_ARG; }
+            const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
+            const bool ok = n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+            mh.nsamp[i] = ok ? n : 0;
+            mh.seek[i] = seek;
+            mh.clip_ok[i] = ok ? 1 : 0;
+            if (c.status) c.status[i] = ok ? Q2A_CLIP_ENCODED : Q2A_CLIP_SKIPPED;
+            max_frames = std::max(max_frames, (int) (((int64_t) mh.nsamp[i] + 480000) / 160));
+            // the clip_max row lies between clip_ok and the key lengths, inside the copy: it is device-written, and
+            // run_frontend resets it after this copy on the same stream, to the value uploaded here
+            if (kind != ENC_PLAIN) { mh.clip_max[i] = (int32_t) 0x80808080u; mh.key_len[i] = c.kl[i]; }
+        }
+        if (kind != ENC_PACKED) return Q2A_OK;
+        rows.X = e->Xp;
+        rows.row_start = dev.row_start;
+        return packed_layout_of(e, mh.key_len, mh.clip_ok, mh.row_start, rows);   // a clip that is not encoded has no rows
+    });
 }
 
-// key lengths of a test hook into the metadata's fifth row (host array, checked; the meta_evt handshake as prepare_meta)
-int upload_key_len(q2a_engine * e, const int32_t * key_len, int B, hipStream_t s) {
+// the rows of a test hook: the windows, for ENC_PADDED with key lengths (host array, checked) uploaded into the key_len
+// row, for ENC_PACKED with their packed layout behind them in the same copy (every clip has rows; rows.X is left to the
+// caller, the attention hook has no residual stream)
+int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, hipStream_t s, block_rows & rows) {
+    const meta_rows dev(e->meta, B);
+    rows = block_rows{B, B * e->d.T, e->X, nullptr, nullptr, 0};
+    if (kind == ENC_PLAIN) return Q2A_OK;
     if (e->bf16) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     for (int c = 0; c < B; ++c)
         if (key_len[c] < 1 || key_len[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, key_len[c], e->d.T); return Q2A_ERR_ARG; }
-    HIP_TRY(hipEventSynchronize(e->meta_evt));
-    memcpy(e->meta_host + 4 * B, key_len, (size_t) B * 4);
-    HIP_TRY(hipMemcpyAsync(e->meta + 4 * B, e->meta_host + 4 * B, (size_t) B * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->meta_evt, s));
-    return Q2A_OK;
+    const bool packed = kind == ENC_PACKED;
+    rows.key_len = dev.key_len;
+    if (packed) { rows.X = nullptr; rows.row_start = dev.row_start; }
+    return upload_meta(e, B, &meta_rows::key_len, packed ? &meta_rows::end : &meta_rows::row_start, s, [&](const meta_rows & mh) -> int {
+        memcpy(mh.key_len, key_len, (size_t) B * 4);
+        return packed ? packed_layout_of(e, key_len, nullptr, mh.row_start, rows) : Q2A_OK;
+    });
 }
 
 // out [B][TO][D]: rows >= key_len[c] / 2 of clip c (every row of a clip that was not encoded) := 0
@@ -1270,49 +1320,7 @@ int padded_key_lens(q2a_engine * e, const int32_t * n_samples, const int32_t * o
     return Q2A_OK;
 }
 
-// encode_impl with per-clip key lengths kl (host [B], checked by padded_key_lens): the attention of every block masks
-// keys >= kl[c], output rows >= kl[c] / 2 are zeros. Everything else runs over all B*T rows as in encode_impl.
-int encode_padded_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t * n_samples, int B, const int32_t * offs,
-                       const int32_t * kl, float * out, int32_t * out_len, int32_t * status, hipStream_t s) {
-    if (B <= 0 || !pcm || !n_samples || !out || !kl) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = reserve(e, B);
-    if (rc) return rc;
-    std::vector<int32_t> st_local;
-    if (!status) { st_local.resize(B); status = st_local.data(); }
-    int max_frames = 0;
-    rc = prepare_meta(e, n_samples, B, 0, offs, status, max_frames, stride > 0 ? stride : -1, s, kl);
-    if (rc) return rc;
-    if (out_len) for (int c = 0; c < B; ++c) out_len[c] = status[c] == Q2A_CLIP_ENCODED ? kl[c] / 2 : 0;
-    rc = run_frontend(e, pcm, stride, B, max_frames, s);
-    if (rc) return rc;
-    const int32_t * kl_dev = e->meta + 4 * B;
-    for (int l = 0; l < e->d.L; ++l) {
-        rc = run_block(e, l, B, B * e->d.T, s, kl_dev);
-        if (rc) return rc;
-    }
-    q2a_pool_args pa{e->X, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, e->meta + 2 * B};
-    PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
-    PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(out, kl_dev, e->meta + 2 * B, B, e->d.TO, e->d.D, s));
-    return Q2A_OK;
-}
-
 // ---- variable-length encode: the blocks run on the valid rows only ------------------------------
-// key lengths and their packed layout of a test hook into the metadata's fifth and sixth rows (one copy; checks and
-// handshake as upload_key_len). Every clip has rows.
-int upload_varlen(q2a_engine * e, const int32_t * key_len, int B, hipStream_t s, packed_layout & pl) {
-    if (e->bf16) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
-    for (int c = 0; c < B; ++c)
-        if (key_len[c] < 1 || key_len[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, key_len[c], e->d.T); return Q2A_ERR_ARG; }
-    HIP_TRY(hipEventSynchronize(e->meta_evt));
-    memcpy(e->meta_host + 4 * B, key_len, (size_t) B * 4);
-    if (int rc = packed_layout_of(e, key_len, nullptr, B, e->meta_host + 5 * B, pl)) return rc;
-    HIP_TRY(hipMemcpyAsync(e->meta + 4 * B, e->meta_host + 4 * B, ((size_t) B * 2 + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->meta_evt, s));
-    return Q2A_OK;
-}
-
 // the packed residual buffer, for as many clips as the workspace holds (its own allocation: engines that never run a
 // variable-length encode do not pay for it)
 int ensure_packed(q2a_engine * e) {
@@ -1345,60 +1353,53 @@ hipError_t launch_gather_rows(const float * X, float * Xp, const int32_t * row_s
     return hipGetLastError();
 }
 
-// encode_padded_impl on the packed rows: after the front end (full windows, unchanged) the valid rows of every clip
-// (each rounded up to the attention's 16-query block) are gathered into one [M_tot][D] stream, the blocks run on those
-// M_tot rows, and the pool + final LayerNorm reads them back into out [B][TO][D], zeros past each clip's valid length.
-// Row for row the padded encode's operations: the same bytes.
-int encode_varlen_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t * n_samples, int B, const int32_t * offs,
-                       const int32_t * kl, float * out, int32_t * out_len, int32_t * status, hipStream_t s) {
-    if (B <= 0 || !pcm || !n_samples || !out || !kl) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = reserve(e, B);
-    if (rc) return rc;
-    if ((rc = ensure_packed(e))) return rc;
-    std::vector<int32_t> st_local;
-    if (!status) { st_local.resize(B); status = st_local.data(); }
-    int max_frames = 0;
-    packed_layout pl{0, 0};
-    rc = prepare_meta(e, n_samples, B, 0, offs, status, max_frames, stride > 0 ? stride : -1, s, kl, &pl);
-    if (rc) return rc;
-    if (out_len) for (int c = 0; c < B; ++c) out_len[c] = status[c] == Q2A_CLIP_ENCODED ? kl[c] / 2 : 0;
-    const int32_t * kl_dev = e->meta + 4 * B;
-    const int32_t * rs_dev = e->meta + 5 * B;
-    if (pl.m_tot > 0) {   // (every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros)
-        rc = run_frontend(e, pcm, stride, B, max_frames, s);
-        if (rc) return rc;
-        PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, rs_dev, B, e->d.T, e->d.D, pl.r_max, s));
-        const packed_rows pk{rs_dev, pl.r_max, e->Xp};
-        for (int l = 0; l < e->d.L; ++l) {
-            rc = run_block(e, l, B, pl.m_tot, s, kl_dev, &pk);
-            if (rc) return rc;
-        }
-    }
-    q2a_pool_varlen_args pa{e->Xp, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, kl_dev, rs_dev};
-    PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
-    return Q2A_OK;
+// the key-length kinds exist for the reference activation contract only
+int lens_supported(const q2a_engine * e, encode_kind kind) {
+    if (kind == ENC_PLAIN || !e->bf16) return Q2A_OK;
+    set_err("%s: reference activation contract only", kind == ENC_PADDED ? "padded encode" : "variable-length encode");
+    return Q2A_ERR_UNSUPPORTED;
 }
 
-int encode_impl(q2a_engine * e, const float * pcm, int64_t stride, const int32_t * n_samples, int B, int offset_ms,
-                const int32_t * offs, float * out, int32_t * status, hipStream_t s) {
-    if (B <= 0 || !pcm || !n_samples || !out) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
+// One encode of any kind: metadata, front end, the L blocks, pool + final LayerNorm into out [B][TO][D].
+// ENC_PADDED: the attention of every block masks keys >= kl[c] and output rows >= kl[c] / 2 (every row of a skipped
+// clip) are zeros; everything else runs over all B*T rows as in ENC_PLAIN, which leaves a skipped clip's rows alone.
+// ENC_PACKED: after the front end (full windows, unchanged) the valid rows of every clip (each rounded up to the
+// attention's 16-query block) are gathered into one [M_tot][D] stream, the blocks run on those M_tot rows, and the pool
+// reads them back into out, zeros past each clip's valid length. Row for row the padded encode's operations: the same
+// bytes.
+int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s) {
+    const dims & d = e->d;
+    const int B = c.B;
+    if (B <= 0 || !c.pcm || !c.n_samples || !c.out || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (c.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
+    int rc = lens_supported(e, kind);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    int rc = reserve(e, B);
-    if (rc) return rc;
+    if ((rc = reserve(e, B))) return rc;
+    if (kind == ENC_PACKED && (rc = ensure_packed(e))) return rc;
     int max_frames = 0;
-    rc = prepare_meta(e, n_samples, B, offset_ms, offs, status, max_frames, stride > 0 ? stride : -1, s);   // stride 0: shared PCM
-    if (rc) return rc;
-    rc = run_frontend(e, pcm, stride, B, max_frames, s);
-    if (rc) return rc;
-    for (int l = 0; l < e->d.L; ++l) {
-        rc = run_block(e, l, B, B * e->d.T, s);
-        if (rc) return rc;
+    block_rows rows;
+    if ((rc = prepare_meta(e, kind, c, s, max_frames, rows))) return rc;
+    const meta_rows dev(e->meta, B), host(e->meta_host, B);
+    if (kind != ENC_PLAIN && c.out_len)
+        for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
+    // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros)
+    if (kind != ENC_PACKED || rows.M > 0) {
+        if ((rc = run_frontend(e, c.pcm, c.stride, B, max_frames, s))) return rc;
+        if (kind == ENC_PACKED)
+            PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, dev.row_start, B, d.T, d.D, rows.r_max, s));
+        for (int l = 0; l < d.L; ++l)
+            if ((rc = run_block(e, l, rows, s))) return rc;
     }
-    q2a_pool_args pa{e->X, B, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out, e->meta + 2 * B};
-    PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
+    const float * lnw = e->g<const float *>(G_LNP_W), * lnb = e->g<const float *>(G_LNP_B);
+    if (kind == ENC_PACKED) {
+        q2a_pool_varlen_args pa{e->Xp, B, d.T, d.D, lnw, lnb, c.out, dev.key_len, dev.row_start};
+        PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
+    } else {
+        q2a_pool_args pa{e->X, B, d.T, d.D, lnw, lnb, c.out, dev.clip_ok};
+        PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
+        if (kind == ENC_PADDED) PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(c.out, dev.key_len, dev.clip_ok, B, d.TO, d.D, s));
+    }
     return Q2A_OK;
 }
 
@@ -1422,12 +1423,10 @@ int q2a_internal_engine_blob(const q2a_engine * e, const void ** blob, int64_t *
     return Q2A_OK;
 }
 
-int64_t q2a_pack_model(const char * path, void ** host_blob) { return q2a_pack_model_ex(path, Q2A_ACT_REFERENCE, host_blob); }
-
-int64_t q2a_pack_model_ex(const char * path, int act, void ** host_blob) {
+static int64_t pack_model(const char * path, int act, bool compact, void ** host_blob) {
     if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("unknown activation mode %d", act); return Q2A_ERR_ARG; }
     std::vector<uint8_t> v;
-    const int rc = pack(path, v, act);
+    const int rc = pack(path, v, act, compact);
     if (rc) return rc;
     void * p = malloc(v.size());
     if (!p) { set_err("host allocation failed"); return Q2A_ERR_OOM; }
@@ -1436,17 +1435,9 @@ int64_t q2a_pack_model_ex(const char * path, int act, void ** host_blob) {
     return (int64_t) v.size();
 }
 
-int64_t q2a_pack_model_compact(const char * path, int act, void ** host_blob) {
-    if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("unknown activation mode %d", act); return Q2A_ERR_ARG; }
-    std::vector<uint8_t> v;
-    const int rc = pack(path, v, act, true);
-    if (rc) return rc;
-    void * p = malloc(v.size());
-    if (!p) { set_err("host allocation failed"); return Q2A_ERR_OOM; }
-    memcpy(p, v.data(), v.size());
-    *host_blob = p;
-    return (int64_t) v.size();
-}
+int64_t q2a_pack_model(const char * path, void ** host_blob) { return pack_model(path, Q2A_ACT_REFERENCE, false, host_blob); }
+int64_t q2a_pack_model_ex(const char * path, int act, void ** host_blob) { return pack_model(path, act, false, host_blob); }
+int64_t q2a_pack_model_compact(const char * path, int act, void ** host_blob) { return pack_model(path, act, true, host_blob); }
 
 int64_t q2a_blob_device_size(const void * host_header, int64_t header_bytes, int64_t * transport_bytes) {
     blob_header h;
@@ -1580,16 +1571,16 @@ int q2a_encode_device(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride,
                       int n_clips, int offset_ms, float * out_dev, int32_t * status, void * stream) {
     if (!e) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = call_stream(stream);
-    return encode_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, offset_ms, nullptr, out_dev, status, s);
+    return encode(e, ENC_PLAIN, {pcm_dev, pcm_stride, n_samples, n_clips, offset_ms, nullptr, nullptr, out_dev, nullptr, status},
+                  call_stream(stream));
 }
 
 int q2a_encode_device_ex(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                          const int32_t * offsets_ms, int n_clips, float * out_dev, int32_t * status, void * stream) {
     if (!e || !offsets_ms) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = call_stream(stream);
-    return encode_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, out_dev, status, s);
+    return encode(e, ENC_PLAIN, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, nullptr, out_dev, nullptr, status},
+                  call_stream(stream));
 }
 
 int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, int n_clips, int offset_ms,
@@ -1597,12 +1588,12 @@ int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n
     return q2a_encode_host_ex(e, pcm, n_samples, nullptr, n_clips, offset_ms, out_host, status);
 }
 
-// q2a_encode_host_ex, and with kl (host [n_clips] key lengths, already checked) q2a_encode_host_padded: every clip's
-// output is then copied back (rows past its valid length, and a skipped clip's rows, are zeros); varlen:
-// q2a_encode_host_varlen (each chunk of clips packed on its own)
-static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
-                            int n_clips, int offset_ms, float * out_host, int32_t * status, const int32_t * kl,
-                            int32_t * out_len, bool varlen = false) {
+// q2a_encode_host_ex (ENC_PLAIN), q2a_encode_host_padded and q2a_encode_host_varlen (each chunk of clips packed on its
+// own), the latter two with kl (host [n_clips] key lengths, already checked): every clip's output is then copied back
+// (rows past its valid length, and a skipped clip's rows, are zeros)
+static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * const * pcm, const int32_t * n_samples,
+                            const int32_t * offsets_ms, int n_clips, int offset_ms, float * out_host, int32_t * status,
+                            const int32_t * kl, int32_t * out_len) {
     if (!e || !pcm || !n_samples || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     for (int c = 0; c < n_clips; ++c)   // (checked before any copy: a negative count would be a huge memcpy)
         if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) {
@@ -1623,7 +1614,7 @@ static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int
     maxn = (maxn + 63) & ~int64_t(63);
     if (int rc = ensure_host_bufs(e, C, maxn)) return rc;
     const size_t per_out = (size_t) e->d.TO * e->d.D;
-    // st: what encode_impl reported per clip; pub: what the caller gets — a clip's status is published only once its
+    // st: what encode reported per clip; pub: what the caller gets — a clip's status is published only once its
     // chunk's outputs reached out_host, so a failure part-way leaves every later clip (and a chunk whose copy-out
     // never ran) at Q2A_CLIP_FAILED rather than a stale "encoded"
     std::vector<int32_t> st(n_clips, Q2A_CLIP_FAILED), pub(n_clips, Q2A_CLIP_FAILED);
@@ -1634,7 +1625,7 @@ static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int
         q2a_engine::host_buf & b = e->hb[k & 1];
         if (hipEventSynchronize(b.d2h) != hipSuccess) return Q2A_ERR_HIP;
         for (int c = 0; c < n; ++c) {
-            if (st[c0 + c] == Q2A_CLIP_ENCODED || (kl && st[c0 + c] == Q2A_CLIP_SKIPPED))
+            if (st[c0 + c] == Q2A_CLIP_ENCODED || (kind != ENC_PLAIN && st[c0 + c] == Q2A_CLIP_SKIPPED))
                 memcpy(out_host + (c0 + c) * per_out, b.pin_out + c * per_out, per_out * 4);
             pub[c0 + c] = st[c0 + c];
         }
@@ -1656,15 +1647,8 @@ static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int
             rc = Q2A_ERR_HIP;
             break;
         }
-        if (kl && varlen)
-            rc = encode_varlen_impl(e, b.d_in, maxn, n_samples + c0, n, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, b.d_out,
-                                    out_len ? out_len + c0 : nullptr, st.data() + c0, s);
-        else if (kl)
-            rc = encode_padded_impl(e, b.d_in, maxn, n_samples + c0, n, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, b.d_out,
-                                    out_len ? out_len + c0 : nullptr, st.data() + c0, s);
-        else
-            rc = encode_impl(e, b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr, b.d_out,
-                             st.data() + c0, s);
+        rc = encode(e, kind, {b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr,
+                              kl ? kl + c0 : nullptr, b.d_out, out_len ? out_len + c0 : nullptr, st.data() + c0}, s);
         if (rc) break;
         if (hipEventRecord(b.comp, s) != hipSuccess || hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||
             hipMemcpyAsync(b.pin_out, b.d_out, (size_t) n * per_out * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
@@ -1685,49 +1669,47 @@ static int encode_host_impl(q2a_engine * e, const float * const * pcm, const int
 
 int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                        int n_clips, int offset_ms, float * out_host, int32_t * status) {
-    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, offset_ms, out_host, status, nullptr, nullptr);
+    return encode_host_impl(e, ENC_PLAIN, pcm, n_samples, offsets_ms, n_clips, offset_ms, out_host, status, nullptr, nullptr);
+}
+
+// the prologue of the padded and variable-length entry points: arguments, activation contract, the key lengths into kl
+static int lens_prologue(q2a_engine * e, encode_kind kind, const int32_t * n_samples, const int32_t * offsets_ms,
+                         const int32_t * key_len, int n_clips, std::vector<int32_t> & kl) {
+    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = lens_supported(e, kind)) return rc;
+    return padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl);
 }
 
 int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                              const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
                              int32_t * out_len, int32_t * status, void * stream) {
-    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     std::vector<int32_t> kl;
-    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    return encode_padded_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms, kl.data(), out_dev, out_len, status,
-                              call_stream(stream));
+    if (int rc = lens_prologue(e, ENC_PADDED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode(e, ENC_PADDED, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), out_dev, out_len, status},
+                  call_stream(stream));
 }
 
 int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                            const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
-    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("padded encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     std::vector<int32_t> kl;
-    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
+    if (int rc = lens_prologue(e, ENC_PADDED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode_host_impl(e, ENC_PADDED, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
 }
 
 int q2a_encode_device_varlen(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                              const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
                              int32_t * out_len, int32_t * status, void * stream) {
-    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     std::vector<int32_t> kl;
-    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    return encode_varlen_impl(e, pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms, kl.data(), out_dev, out_len, status,
-                              call_stream(stream));
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode(e, ENC_PACKED, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), out_dev, out_len, status},
+                  call_stream(stream));
 }
 
 int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                            const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
-    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (e->bf16) { set_err("variable-length encode: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     std::vector<int32_t> kl;
-    if (int rc = padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode_host_impl(e, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len, true);
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    return encode_host_impl(e, ENC_PACKED, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -1738,31 +1720,26 @@ int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel
     if (mel_cap < (int64_t) d.M * n_len) { set_err("mel buffer too small (%d frames)", n_len); return Q2A_ERR_ARG; }
     int rc = reserve(e, 1);
     if (rc) return rc;
+    hipStream_t s = e->stream;
+    if ((rc = ensure_frange(e, s))) return rc;
     // run the mel kernel with a window covering every frame, in chunks of TM frames
     float * dpcm = nullptr;
     HIP_TRY(hipMalloc((void **) &dpcm, (size_t) n_samples * 4));
     std::vector<float> chunk((size_t) d.M * d.TM);
-    hipStream_t s = e->stream;
-    rc = Q2A_OK;
+    const meta_rows dev(e->meta, 1);   // one clip; seek = the chunk's first frame
+    const q2a_mel_args ma = mel_args(e, dpcm, n_samples, dev, 1, n_len);
     if (hipMemcpy(dpcm, pcm, (size_t) n_samples * 4, hipMemcpyHostToDevice) != hipSuccess) rc = Q2A_ERR_HIP;
     int32_t cmax = 0;
     for (int f0 = 0; f0 < n_len && rc == Q2A_OK; f0 += d.TM) {
-        int32_t * mh = e->meta_host;
-        if (hipEventSynchronize(e->meta_evt) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        mh[0] = n_samples; mh[1] = f0; mh[2] = 1;
-        if (hipMemcpyAsync(e->meta, mh, 12, hipMemcpyHostToDevice, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        if (hipEventRecord(e->meta_evt, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        if (hipMemsetAsync(e->meta + 3, 0x80, 4, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        q2a_mel_args ma;
-        ma.pcm = dpcm; ma.pcm_stride = n_samples; ma.n_samples = e->meta; ma.seek = e->meta + 1; ma.n_clips = 1;
-        ma.n_mel = d.M; ma.n_bins = 201; ma.n_frames_win = d.TM; ma.max_frames = n_len;
-        ma.filters = e->g<const float *>(G_FILT); ma.tab = e->g<const float *>(G_TAB);
-        if (int rc = ensure_frange(e, e->stream)) return rc;
-        ma.frange = e->frange;
-        ma.mel = e->mel; ma.clip_max = e->meta + 3; ma.xc1 = e->xc1; ma.xc_f32 = e->f32 ? 1 : 0;
+        rc = upload_meta(e, 1, &meta_rows::nsamp, &meta_rows::clip_max, s, [&](const meta_rows & mh) -> int {
+            mh.nsamp[0] = n_samples; mh.seek[0] = f0; mh.clip_ok[0] = 1;
+            return Q2A_OK;
+        });
+        if (rc) break;
+        if (hipMemsetAsync(dev.clip_max, 0x80, 4, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
         if (q2a_launch_mel(ma, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
         if (hipMemcpyAsync(chunk.data(), e->mel, chunk.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(&cmax, e->meta + 3, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(&cmax, dev.clip_max, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
         const int nf = std::min(d.TM, n_len - f0);
         for (int j = 0; j < d.M; ++j) memcpy(mel_out + (size_t) j * n_len + f0, chunk.data() + (size_t) j * d.TM, (size_t) nf * 4);
@@ -1847,52 +1824,44 @@ int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M
     return Q2A_OK;
 }
 
-static int test_block_impl(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, bool with_len, void * stream) {
-    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0 || (with_len && !key_len)) return Q2A_ERR_ARG;
+// one block in place on x: the windows [n_clips*T][D], or for ENC_PACKED the packed rows [M_tot][D] (q2a_varlen_rows
+// over key_len), the variable-length encode's block
+static int test_block(q2a_engine * e, encode_kind kind, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
+    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0 || (kind != ENC_PLAIN && !key_len) || (kind == ENC_PACKED && !x))
+        return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
     if (rc) return rc;
-    if (with_len && (rc = upload_key_len(e, key_len, n_clips, s))) return rc;
-    const size_t bytes = (size_t) n_clips * e->d.T * e->d.D * 4;
-    HIP_TRY(hipMemcpyAsync(e->X, x, bytes, hipMemcpyDeviceToDevice, s));
-    rc = run_block(e, layer, n_clips, n_clips * e->d.T, s, with_len ? e->meta + 4 * n_clips : nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x, e->X, bytes, hipMemcpyDeviceToDevice, s));
+    block_rows rows;
+    if ((rc = hook_rows(e, kind, key_len, n_clips, s, rows))) return rc;
+    if (kind == ENC_PACKED) {
+        if ((rc = ensure_packed(e))) return rc;
+        rows.X = e->Xp;
+    }
+    const size_t bytes = (size_t) rows.M * e->d.D * 4;
+    HIP_TRY(hipMemcpyAsync(rows.X, x, bytes, hipMemcpyDeviceToDevice, s));
+    if ((rc = run_block(e, layer, rows, s))) return rc;
+    HIP_TRY(hipMemcpyAsync(x, rows.X, bytes, hipMemcpyDeviceToDevice, s));
     return Q2A_OK;
 }
 
 int q2a_test_block(q2a_engine * e, int layer, float * x, int n_clips, void * stream) {
-    return test_block_impl(e, layer, x, n_clips, nullptr, false, stream);
+    return test_block(e, ENC_PLAIN, layer, x, n_clips, nullptr, stream);
 }
 
 int q2a_test_block_len(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
-    return test_block_impl(e, layer, x, n_clips, key_len, true, stream);
+    return test_block(e, ENC_PADDED, layer, x, n_clips, key_len, stream);
 }
 
-// one block on packed rows x [M_tot][D] (q2a_varlen_rows over key_len): the variable-length encode's block
 int q2a_test_block_varlen(q2a_engine * e, int layer, float * x, int n_clips, const int32_t * key_len, void * stream) {
-    if (!e || layer < 0 || layer >= e->d.L || n_clips <= 0 || !key_len || !x) return Q2A_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = call_stream(stream);
-    int rc = reserve(e, n_clips);
-    if (rc) return rc;
-    packed_layout pl{0, 0};
-    if ((rc = upload_varlen(e, key_len, n_clips, s, pl))) return rc;
-    if ((rc = ensure_packed(e))) return rc;
-    const size_t bytes = (size_t) pl.m_tot * e->d.D * 4;
-    HIP_TRY(hipMemcpyAsync(e->Xp, x, bytes, hipMemcpyDeviceToDevice, s));
-    const packed_rows pk{e->meta + 5 * n_clips, pl.r_max, e->Xp};
-    rc = run_block(e, layer, n_clips, pl.m_tot, s, e->meta + 4 * n_clips, &pk);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x, e->Xp, bytes, hipMemcpyDeviceToDevice, s));
-    return Q2A_OK;
+    return test_block(e, ENC_PACKED, layer, x, n_clips, key_len, stream);
 }
 
 int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void * const * taps, void * stream) {
     if (!e || !taps) return Q2A_ERR_ARG;
     for (int i = 0; i < 4; ++i) e->taps[i] = taps[i];
-    const int rc = q2a_test_block(e, layer, x, n_clips, stream);
+    const int rc = test_block(e, ENC_PLAIN, layer, x, n_clips, nullptr, stream);
     for (int i = 0; i < 4; ++i) e->taps[i] = nullptr;
     return rc;
 }
@@ -1905,7 +1874,10 @@ int q2a_test_frontend(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride,
     int rc = reserve(e, n_clips);
     if (rc) return rc;
     int max_frames = 0;
-    rc = prepare_meta(e, n_samples, n_clips, 0, nullptr, nullptr, max_frames, pcm_stride > 0 ? pcm_stride : -1, s);
+    block_rows rows;
+    encode_call c{};   // no offsets, no status
+    c.pcm = pcm_dev; c.stride = pcm_stride; c.n_samples = n_samples; c.B = n_clips;
+    rc = prepare_meta(e, ENC_PLAIN, c, s, max_frames, rows);
     if (rc) return rc;
     rc = run_frontend(e, pcm_dev, pcm_stride, n_clips, max_frames, s);
     if (rc) return rc;
@@ -1919,13 +1891,14 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
     if (rc) return rc;
-    HIP_TRY(hipEventSynchronize(e->meta_evt));
-    for (int c = 0; c < n_clips; ++c) e->meta_host[2 * n_clips + c] = 1;   // every clip "encoded"
-    HIP_TRY(hipMemcpyAsync(e->meta + 2 * n_clips, e->meta_host + 2 * n_clips, (size_t) n_clips * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(e->meta_evt, s));
+    rc = upload_meta(e, n_clips, &meta_rows::clip_ok, &meta_rows::clip_max, s, [&](const meta_rows & mh) -> int {
+        std::fill(mh.clip_ok, mh.clip_max, 1);   // every clip "encoded"
+        return Q2A_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(e->X, x_dev, (size_t) n_clips * e->d.T * e->d.D * 4, hipMemcpyDeviceToDevice, s));
     q2a_pool_args pa{e->X, n_clips, e->d.T, e->d.D, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B), out_dev,
-                     e->meta + 2 * n_clips};
+                     meta_rows(e->meta, n_clips).clip_ok};
     LAUNCH(q2a_launch_pool_ln(pa, s));
     return Q2A_OK;
 }
@@ -1936,16 +1909,19 @@ int q2a_test_fc1_path(q2a_engine * e, int path) {
     return Q2A_OK;
 }
 
-static int test_attention_impl(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
-                               const int32_t * key_len, bool with_len, float * out, void * stream) {
-    if (!e || n_clips <= 0 || (with_len && !key_len)) return Q2A_ERR_ARG;
+// attention only: q, k, v, out are the windows [n_clips*T][D], or for ENC_PACKED the packed rows [M_tot][D]
+// (q2a_varlen_rows over key_len)
+static int test_attention(q2a_engine * e, encode_kind kind, const float * q, const float * k, const float * v, int n_clips,
+                          const int32_t * key_len, float * out, void * stream) {
+    if (!e || n_clips <= 0 || (kind != ENC_PLAIN && !key_len) || (kind == ENC_PACKED && (!q || !k || !v || !out))) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
     if (rc) return rc;
-    if (with_len && (rc = upload_key_len(e, key_len, n_clips, s))) return rc;
+    block_rows rows;
+    if ((rc = hook_rows(e, kind, key_len, n_clips, s, rows))) return rc;
     const dims & d = e->d;
-    const int64_t n = (int64_t) n_clips * d.T * d.D;
+    const int64_t n = (int64_t) rows.M * d.D;
     const dim3 g((unsigned) ((n + 255) / 256)), b(256);
     hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, q, e->qh, e->ql, n, Q2A_LOG2E);   // the kernel's log2 units
     hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, k, e->kh, e->kl, n, 1.0f);
@@ -1954,47 +1930,23 @@ static int test_attention_impl(q2a_engine * e, const float * q, const float * k,
     q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, n_clips, d.T, d.D, d.H, e->TP, nullptr, out};
     at.vtl = e->vtl;
     at.v_rows = 1;
-    at.key_len = with_len ? e->meta + 4 * n_clips : nullptr;
-    if (with_len) LAUNCH(q2a_launch_attention_len(at, s));
-    else LAUNCH(q2a_launch_attention(at, s));
+    LAUNCH(launch_attention(at, rows, s));
     return Q2A_OK;
 }
 
 int q2a_test_attention(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips, float * out,
                        void * stream) {
-    return test_attention_impl(e, q, k, v, n_clips, nullptr, false, out, stream);
+    return test_attention(e, ENC_PLAIN, q, k, v, n_clips, nullptr, out, stream);
 }
 
 int q2a_test_attention_len(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
                            const int32_t * key_len, float * out, void * stream) {
-    return test_attention_impl(e, q, k, v, n_clips, key_len, true, out, stream);
+    return test_attention(e, ENC_PADDED, q, k, v, n_clips, key_len, out, stream);
 }
 
-// attention only on packed rows: q, k, v, out [M_tot][D] (q2a_varlen_rows over key_len)
 int q2a_test_attention_varlen(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
                               const int32_t * key_len, float * out, void * stream) {
-    if (!e || n_clips <= 0 || !key_len || !q || !k || !v || !out) return Q2A_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = call_stream(stream);
-    int rc = reserve(e, n_clips);
-    if (rc) return rc;
-    packed_layout pl{0, 0};
-    if ((rc = upload_varlen(e, key_len, n_clips, s, pl))) return rc;
-    const dims & d = e->d;
-    const int64_t n = (int64_t) pl.m_tot * d.D;
-    const dim3 g((unsigned) ((n + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, q, e->qh, e->ql, n, Q2A_LOG2E);
-    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, k, e->kh, e->kl, n, 1.0f);
-    hipLaunchKernelGGL(k_split_hilo, g, b, 0, s, v, e->vt, e->vtl, n, 1.0f);
-    LAUNCH(hipGetLastError());
-    q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, n_clips, d.T, d.D, d.H, e->TP, nullptr, out};
-    at.vtl = e->vtl;
-    at.v_rows = 1;
-    at.key_len = e->meta + 4 * n_clips;
-    at.row_start = e->meta + 5 * n_clips;
-    at.r_max = pl.r_max;
-    LAUNCH(q2a_launch_attention_varlen(at, s));
-    return Q2A_OK;
+    return test_attention(e, ENC_PACKED, q, k, v, n_clips, key_len, out, stream);
 }
 
 // ---- downstream consumer: the Qwen2-Audio multi-modal projector ---------------------------

@@ -250,7 +250,58 @@ def test_varlen_encode_of_skipped_clips_only(engines, batch):
     assert list(hst) == [q2a.CLIP_SKIPPED] * 2 and list(hol) == [0, 0] and not hout.any()
 
 
-# ---------------------------------------------------------------- 6. arguments
+# ---------------------------------------------------------------- 6. launch structure
+PROF_CLASSES = ["mel", "conv1", "conv2", "ln", "gemm_qkv", "attn", "quant", "gemm_o", "gemm_fc1", "gemm_fc2", "pool"]   # Q2A_PROF_*
+
+
+@pytest.mark.parametrize("wt", ["f16", "q4_k"])
+def test_launches_per_entry_point(engines, batch, wt):
+    """What each entry point launches, by the engine's per-class profile counters (one count per launch): the three
+    families run the same front end and the same launches per layer, and differ in the pool class alone — pool (plain),
+    pool + tail zeroing (padded), gather + pool (packed). A packed encode with no clip to encode launches its pool
+    kernel (which writes the zeros) and nothing else."""
+    import ctypes as C
+
+    import q2a
+    e = engines("tiny", wt)
+    lib, h = q2a.lib(), C.c_void_p(e.h)
+    L = e.info.n_audio_layer
+    clips, lens = batch[:3], [1500, 500, 37]
+    stride = max(len(c) for c in clips)
+    pcm = torch.zeros(len(clips), stride)
+    for i, c in enumerate(clips):
+        pcm[i, :len(c)] = torch.from_numpy(np.ascontiguousarray(c))
+    pcm = pcm.cuda()
+    ns = [len(c) for c in clips]
+    out = torch.empty((len(clips),) + e.out_shape, device="cuda")
+    cnt = (C.c_int64 * len(PROF_CLASSES))()
+
+    def counts(call):
+        call()
+        torch.cuda.synchronize()
+        assert lib.q2a_profile_read(h, None, cnt, len(PROF_CLASSES), 1) == 0
+        return dict(zip(PROF_CLASSES, cnt))
+
+    def want(pool):
+        w = {c: L for c in ("gemm_qkv", "attn", "gemm_o", "gemm_fc1", "gemm_fc2")}
+        # Q4_K, default fc1 path: the attention output and the fc1 pre-activation each pass a Q8_K quantizer
+        w.update(mel=1, conv1=1, conv2=1, ln=2 * L, quant=2 * L if wt == "q4_k" else 0, pool=pool)
+        return w
+
+    assert lib.q2a_profile_read(h, None, None, 0, 1) == 0
+    assert lib.q2a_profile_enable(h, 1) == 0
+    try:
+        assert counts(lambda: e.encode_device(pcm.data_ptr(), stride, ns, out.data_ptr())) == want(1)
+        assert counts(lambda: e.encode_device_padded(pcm.data_ptr(), stride, ns, out.data_ptr(), key_len=lens)) == want(2)
+        assert counts(lambda: e.encode_device_varlen(pcm.data_ptr(), stride, ns, out.data_ptr(), key_len=lens)) == want(2)
+        skipped = counts(lambda: _encode_varlen(e, [batch[3], batch[3][:4000]]))
+        assert skipped == dict({c: 0 for c in PROF_CLASSES}, pool=1)
+    finally:
+        lib.q2a_profile_enable(h, 0)
+        lib.q2a_profile_read(h, None, None, 0, 1)
+
+
+# ---------------------------------------------------------------- 7. arguments
 def test_varlen_encode_arguments(engines, make_model, make_clip):
     """The cases of test_padded_encode_arguments against the variable-length entry points."""
     import q2a
