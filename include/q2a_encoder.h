@@ -44,7 +44,7 @@ typedef enum {
 
 typedef struct {
     int32_t n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer, n_mels;
-    int32_t wtype;          /* ggml type of the linear weights: 1 F16, 12 Q4_K, 8 Q8_0, 2 Q4_0 */
+    int32_t wtype;          /* ggml type of the linear weights: 0 F32, 1 F16, 12 Q4_K, 13 Q5_K, 14 Q6_K, 8 Q8_0, 2 Q4_0 */
     int32_t n_out;          /* output vectors per clip (n_audio_ctx / 2 = 750) */
     int32_t device;
     int64_t weight_bytes;   /* device bytes of the packed weight blob */
@@ -283,7 +283,7 @@ int q2a_test_block_varlen(q2a_engine * e, int layer, float * x_dev, int n_clips,
  * audio_features = Linear(d_model -> text hidden size, bias)(embd_enc) — transformers' Qwen2AudioMultiModalProjector
  * (modeling_qwen2_audio.py), the step after the reference's path ends at embd_enc (qwen2-whisper.cpp:2185; the
  * reference has no projector). Weights: a projector file in the ggml container (multi_modal_projector.linear.weight
- * [d_out][d_in] F16 / Q4_K / Q8_0 / Q4_0, .bias [d_out] F32; bin/q2a_tool gen-projector + quantize). Numerics: a ggml
+ * [d_out][d_in] F16 / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0, .bias [d_out] F32; bin/q2a_tool gen-projector + quantize). Numerics: a ggml
  * MUL_MAT of that weight type (activations per vec_dot_type, exact products, fp32 accumulation) + bias in f32. */
 typedef struct q2a_projector q2a_projector;
 q2a_projector * q2a_projector_open(const char * path, int device);

@@ -53,8 +53,10 @@ constexpr size_t HEADER_BYTES = 32768;
 
 enum { G_CONV1_W, G_CONV1_B, G_CONV2_W, G_CONV2_B, G_PE, G_LNP_W, G_LNP_B, G_FILT, G_TAB, G_GELU, G_GELU_C, G_COUNT };
 // per-matrix arrays: W (fp16 [N][K]); block-major DX, DMIN, BETA = DX_{b-1}/DX_b, GAMMA = DMIN_b/DX_b (f32 [nblk][N]),
-// WEXT (fp16 [nblk][N][16])
+// WEXT (fp16 [nblk][N][16]). Q6_K: W = q - 32, DX = d [K/256][N], and in the WEXT slot its sub-block scales
+// SC (f32 [K/16][N], sub-block-major: one K-step's four rows of a tile are contiguous runs)
 enum { A_W, A_DX, A_DMIN, A_WEXT, A_BETA, A_GAMMA, A_COUNT };
+constexpr int A_SC = A_WEXT;
 enum { L_BQKV, L_BO, L_B1, L_B2, L_LN1W, L_LN1B, L_LN2W, L_LN2B, L_MAT0, L_COUNT = L_MAT0 + 4 * A_COUNT };
 
 struct blob_header {
@@ -85,7 +87,15 @@ void mat_dims(const dims & d, int which, int & N, int & K) {
         default: N = d.D; K = d.F; break;
     }
 }
-int blk_of(int wtype) { return wtype == Q2A_TYPE_Q4_K ? 256 : (wtype == Q2A_TYPE_Q8_0 || wtype == Q2A_TYPE_Q4_0) ? 32 : 0; }
+// the activation block of a weight type (its vec_dot_type's: Q8_K for the k-quants, Q8_0 for Q8_0 / Q4_0), 0 = fp16
+int blk_of(int wtype) {
+    return (wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K || wtype == Q2A_TYPE_Q6_K) ? 256
+           : (wtype == Q2A_TYPE_Q8_0 || wtype == Q2A_TYPE_Q4_0) ? 32 : 0;
+}
+// the GEMM's block mode: the activation block, but for Q6_K (per-16 integer scales inside the 256-block)
+int gblk_of(int wtype) { return wtype == Q2A_TYPE_Q6_K ? Q2A_BLK_Q6K : blk_of(wtype); }
+// Q4_K's device layout (sc*q weights, min operand, block-ratio arrays): Q4_K and Q5_K
+bool kq_minmax(int wtype) { return wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K; }
 
 bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act) {
     memset(&h, 0, sizeof(h));
@@ -127,11 +137,13 @@ bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act) {
             uint64_t * a = lo + L_MAT0 + w * A_COUNT;
             a[A_W] = take((uint64_t) N * K * 2 * kx);
             if (h.blk) a[A_DX] = take((uint64_t) N * (K / h.blk) * 4);
-            if (h.blk == 256) {
+            if (h.blk && kq_minmax(wtype)) {
                 a[A_DMIN] = take((uint64_t) N * (K / 256) * 4);
                 a[A_WEXT] = take((uint64_t) N * (K / 256) * 16 * 2);
                 a[A_BETA] = take((uint64_t) N * (K / 256) * 4);
                 a[A_GAMMA] = take((uint64_t) N * (K / 256) * 4);
+            } else if (h.blk && wtype == Q2A_TYPE_Q6_K) {
+                a[A_SC] = take((uint64_t) N * (K / 16) * 4);
             }
         }
     }
@@ -204,8 +216,22 @@ inline void scale_min_k4(int j, const uint8_t * q, uint8_t * dd, uint8_t * mm) {
     }
 }
 
+// the 5-bit code of weight l of sub-block j (ggml-quants.c:2782-2783: nibble j & 1 of qs[32 (j / 2) + l], bit j of qh[l])
+inline int q5k_code(const q2a_block_q5_K * x, int j, int l) {
+    const uint8_t q = x->qs[32 * (j / 2) + l];
+    return ((j & 1) ? (q >> 4) : (q & 0xF)) + (((x->qh[l] >> j) & 1) << 4);
+}
+// the 6-bit code (0..63) of weight k of a block (ggml-quants.c:2988-2998: per 128 weights, four runs of 32 over two
+// 32-byte rows of nibbles and one of 2-bit pairs)
+inline int q6k_code(const q2a_block_q6_K * x, int k) {
+    const int h = k / 128, r = (k % 128) / 32, l = k % 32;
+    const uint8_t n = x->ql[64 * h + 32 * (r & 1) + l];
+    return ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
+}
+
 // Expand rows [r0, r1) of a ggml weight matrix into the blob arrays (rows offset by dst_row0).
-// F16: copied. Q4_K: W' = sc_j * q (exact small integers), DX = d, DMIN = dmin, WEXT = (64 m_j, m_j).
+// F16: copied. Q4_K: W' = sc_j * q (exact small integers), DX = d, DMIN = dmin, WEXT = (64 m_j, m_j). Q5_K: the same
+// with its 5-bit codes (sc_j * q <= 1953, still an exact fp16 integer). Q6_K: W' = q - 32, DX = d, SC = sc_j.
 // Q8_0: W' = q, DX = d. Q4_0: W' = q - 8, DX = d.
 // one ggml row -> f32 values, as ggml's dequantize_row_* computes them (ggml-quants.c: q8_0 :1734, q4_0 :1694,
 // q4_K :2555-2577 with d1 = d*sc, m1 = dmin*m, y = d1*q - m1)
@@ -238,6 +264,23 @@ void dequant_row(const uint8_t * row, int wtype, int K, float * y) {
                 const uint8_t * q = x->qs + 32 * (j / 2);
                 for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * ((j & 1) ? (q[l] >> 4) : (q[l] & 0xF)) - m1;
             }
+        }
+    } else if (wtype == Q2A_TYPE_Q5_K) {   // dequantize_row_q5_K, ggml-quants.c:2763-2788
+        for (int b = 0; b < K / 256; ++b) {
+            const q2a_block_q5_K * x = (const q2a_block_q5_K *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
+            for (int j = 0; j < 8; ++j) {
+                uint8_t sc, m;
+                scale_min_k4(j, x->scales, &sc, &m);
+                const float d1 = d * sc, m1 = dmin * m;
+                for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * q5k_code(x, j, l) - m1;
+            }
+        }
+    } else if (wtype == Q2A_TYPE_Q6_K) {   // dequantize_row_q6_K, ggml-quants.c:2977-3006: (d * sc) * q
+        for (int b = 0; b < K / 256; ++b) {
+            const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d);
+            for (int k = 0; k < 256; ++k) y[b * 256 + k] = d * x->scales[k / 16] * (int8_t) (q6k_code(x, k) - 32);
         }
     }
 }
@@ -272,8 +315,10 @@ void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1
                 w3[K + k] = hi;
                 w3[2 * K + k] = q2a_fp32_to_fp16(x[k] - q2a_fp16_to_fp32(hi));
             }
-        } else if (wtype == Q2A_TYPE_Q4_K) {
+        } else if (wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K) {
             // block-major scale arrays: [nb][Ntot] / [nb][Ntot][16] so a tile's block scales are contiguous
+            // (block_q5_K begins like block_q4_K: d, dmin, scales[12]; only the codes are read by type)
+            const bool q5 = wtype == Q2A_TYPE_Q5_K;
             const int nb = K / 256;
             float * dx = (float *) (blob + a[A_DX]);
             float * dm = (float *) (blob + a[A_DMIN]);
@@ -282,7 +327,8 @@ void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1
             uint16_t * we = (uint16_t *) (blob + a[A_WEXT]);
             float dprev = 1.0f;
             for (int b = 0; b < nb; ++b) {
-                const q2a_block_q4_K * x = (const q2a_block_q4_K *) row + b;
+                const q2a_block_q5_K * x5 = (const q2a_block_q5_K *) row + b;
+                const q2a_block_q4_K * x = q5 ? (const q2a_block_q4_K *) x5 : (const q2a_block_q4_K *) row + b;
                 // d = 0: the block's d*sc*q terms vanish; store dx = 1 with zero weights instead (same products,
                 // and the block-ratio rescaling of the 8-phase kernel never divides by zero)
                 const float d = q2a_fp16_to_fp32(x->d);
@@ -299,10 +345,21 @@ void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1
                     we[((size_t) b * Ntot + n) * 16 + 2 * j + 1] = q2a_fp32_to_fp16((float) m);
                     const uint8_t * q = x->qs + 32 * (j / 2);
                     for (int l = 0; l < 32; ++l) {
-                        const int v = (j & 1) ? (q[l] >> 4) : (q[l] & 0xF);
+                        const int v = q5 ? q5k_code(x5, j, l) : (j & 1) ? (q[l] >> 4) : (q[l] & 0xF);
                         wr[b * 256 + 32 * j + l] = q2a_fp32_to_fp16(d != 0.0f ? (float) (sc * v) : 0.0f);
                     }
                 }
+            }
+        } else if (wtype == Q2A_TYPE_Q6_K) {
+            // (a block the quantizer zeroed, d = 0 with every byte 0, needs no special case: nothing divides by d)
+            const int nb = K / 256;
+            float * dx = (float *) (blob + a[A_DX]);
+            float * sc = (float *) (blob + a[A_SC]);
+            for (int b = 0; b < nb; ++b) {
+                const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
+                dx[(size_t) b * Ntot + n] = q2a_fp16_to_fp32(x->d);
+                for (int j = 0; j < 16; ++j) sc[(size_t) (b * 16 + j) * Ntot + n] = (float) x->scales[j];
+                for (int k = 0; k < 256; ++k) wr[b * 256 + k] = q2a_fp32_to_fp16((float) (q6k_code(x, k) - 32));
             }
         } else if (wtype == Q2A_TYPE_Q8_0) {
             const int nb = K / 32;
@@ -511,11 +568,13 @@ uint64_t q2a_pack_layout(int wtype, int N, int K, uint64_t off[6]) {
     for (int i = 0; i < A_COUNT; ++i) off[i] = 0;
     off[A_W] = take((uint64_t) N * K * 2);
     if (blk) off[A_DX] = take((uint64_t) N * (K / blk) * 4);
-    if (blk == 256) {
+    if (kq_minmax(wtype)) {
         off[A_DMIN] = take((uint64_t) N * (K / 256) * 4);
         off[A_WEXT] = take((uint64_t) N * (K / 256) * 16 * 2);
         off[A_BETA] = take((uint64_t) N * (K / 256) * 4);
         off[A_GAMMA] = take((uint64_t) N * (K / 256) * 4);
+    } else if (wtype == Q2A_TYPE_Q6_K) {
+        off[A_SC] = take((uint64_t) N * (K / 16) * 4);
     }
     return o;
 }
@@ -579,6 +638,15 @@ __device__ __forceinline__ void scale_min_k4_d(int j, const uint8_t * q, int & d
     if (j < 4) { dd = q[j] & 63; mm = q[j + 4] & 63; }
     else { dd = (q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4); mm = (q[j + 4] >> 4) | ((q[j - 0] >> 6) << 4); }
 }
+__device__ __forceinline__ int q5k_code_d(const q2a_block_q5_K * x, int j, int l) {   // as q5k_code
+    const int q = x->qs[32 * (j / 2) + l];
+    return ((j & 1) ? (q >> 4) : (q & 0xF)) + (((x->qh[l] >> j) & 1) << 4);
+}
+__device__ __forceinline__ int q6k_code_d(const q2a_block_q6_K * x, int k) {   // as q6k_code
+    const int h = k / 128, r = (k % 128) / 32, l = k % 32;
+    const int n = x->ql[64 * h + 32 * (r & 1) + l];
+    return ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
+}
 
 struct expand_args {
     const uint8_t * raw;    // ggml rows [nrows][row_size]
@@ -592,18 +660,21 @@ struct expand_args {
 __global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
 #pragma clang fp contract(off)
     const int n = blockIdx.x, t = threadIdx.x, k = blockIdx.y * 256 + t;
-    const size_t rs = p.wtype == Q2A_TYPE_Q4_K ? (size_t) p.K / 256 * 144 : p.wtype == Q2A_TYPE_Q8_0 ? (size_t) p.K / 32 * 34
+    const size_t rs = p.wtype == Q2A_TYPE_Q4_K ? (size_t) p.K / 256 * 144 : p.wtype == Q2A_TYPE_Q5_K ? (size_t) p.K / 256 * 176
+                    : p.wtype == Q2A_TYPE_Q6_K ? (size_t) p.K / 256 * 210 : p.wtype == Q2A_TYPE_Q8_0 ? (size_t) p.K / 32 * 34
                     : p.wtype == Q2A_TYPE_Q4_0 ? (size_t) p.K / 32 * 18 : p.wtype == Q2A_TYPE_F16 ? (size_t) p.K * 2 : (size_t) p.K * 4;
     const uint8_t * row = p.raw + (size_t) n * rs;
     uint16_t * W = (uint16_t *) (p.blob + p.a[A_W]);
     if (k >= p.K) return;
     float val = 0.0f;   // dequantized value (bf16 mode)
-    if (p.wtype == Q2A_TYPE_Q4_K) {
+    if (p.wtype == Q2A_TYPE_Q4_K || p.wtype == Q2A_TYPE_Q5_K) {
+        const bool q5 = p.wtype == Q2A_TYPE_Q5_K;   // (block_q5_K begins like block_q4_K: d, dmin, scales[12])
         const int b = k / 256, j = (k % 256) / 32, l = k % 32;
-        const q2a_block_q4_K * x = (const q2a_block_q4_K *) row + b;
+        const q2a_block_q5_K * x5 = (const q2a_block_q5_K *) row + b;
+        const q2a_block_q4_K * x = q5 ? (const q2a_block_q4_K *) x5 : (const q2a_block_q4_K *) row + b;
         int sc, m;
         scale_min_k4_d(j, x->scales, sc, m);
-        const int v = (j & 1) ? (x->qs[32 * (j / 2) + l] >> 4) : (x->qs[32 * (j / 2) + l] & 0xF);
+        const int v = q5 ? q5k_code_d(x5, j, l) : (j & 1) ? (x->qs[32 * (j / 2) + l] >> 4) : (x->qs[32 * (j / 2) + l] & 0xF);
         const float d = h2f(x->d), dmin = h2f(x->dmin);
         if (p.act) {
             const float d1 = d * (float) sc, m1 = dmin * (float) m;
@@ -614,7 +685,10 @@ __global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
             const float deff = d != 0.0f ? d : 1.0f;
             if (t == 0) {
                 float dprev = 1.0f;
-                if (b > 0) { const float dp = h2f(((const q2a_block_q4_K *) row + b - 1)->d); dprev = dp != 0.0f ? dp : 1.0f; }
+                if (b > 0) {
+                    const float dp = q5 ? h2f((x5 - 1)->d) : h2f((x - 1)->d);
+                    dprev = dp != 0.0f ? dp : 1.0f;
+                }
                 ((float *) (p.blob + p.a[A_DX]))[bi] = deff;
                 ((float *) (p.blob + p.a[A_DMIN]))[bi] = dmin;
                 ((float *) (p.blob + p.a[A_BETA]))[bi] = dprev / deff;
@@ -625,6 +699,18 @@ __global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
                 scale_min_k4_d(t / 2, x->scales, sj, mj);
                 ((uint16_t *) (p.blob + p.a[A_WEXT]))[bi * 16 + t] = f2h((t & 1) ? (float) mj : 64.0f * (float) mj);
             }
+            return;
+        }
+    } else if (p.wtype == Q2A_TYPE_Q6_K) {
+        const int b = k / 256, kk = k % 256;
+        const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
+        const int q = q6k_code_d(x, kk) - 32;
+        const float d = h2f(x->d);
+        if (p.act) val = d * (float) x->scales[kk / 16] * (float) q;
+        else {
+            W[(size_t) n * p.K + k] = f2h((float) q);
+            if (t == 0) ((float *) (p.blob + p.a[A_DX]))[(size_t) b * p.Ntot + n] = d;
+            if (t < 16) ((float *) (p.blob + p.a[A_SC]))[(size_t) (b * 16 + t) * p.Ntot + n] = (float) x->scales[t];
             return;
         }
     } else if (p.wtype == Q2A_TYPE_Q8_0) {
@@ -712,11 +798,11 @@ struct q2a_engine {
     hipStream_t stream = nullptr;
     blob_header h;
     dims d;
-    int wtype = 0, blk = 0;
+    int wtype = 0, blk = 0;   // blk: the activation quantizer's block (blk_of), 0 under the bf16 contract
     bool f32 = false;        // all-F32 model file: fp16 hi/lo split operands, GEMM K tripled (kx = 3)
     int kx = 1;
     bool bf16 = false;       // bf16-activation mode (Q2A_ACT_BF16): bf16 weights and inter-op activations
-    int gblk = 0;            // the GEMM launcher's blk: blk, or Q2A_BLK_BF16
+    int gblk = 0;            // the GEMM launcher's blk: blk, Q2A_BLK_Q6K for Q6_K weights, or Q2A_BLK_BF16
     uint8_t * blob = nullptr;
     bool own_blob = false;
     int64_t blob_size = 0;
@@ -833,7 +919,7 @@ int engine_adopt_header(q2a_engine * e) {
     e->f32 = e->wtype == Q2A_TYPE_F32;
     e->bf16 = e->h.act == Q2A_ACT_BF16;
     e->kx = e->f32 && !e->bf16 ? 3 : 1;
-    e->gblk = e->bf16 ? Q2A_BLK_BF16 : e->blk;
+    e->gblk = e->bf16 ? Q2A_BLK_BF16 : gblk_of(e->wtype);
     e->TP = ((e->d.T + 63) / 64) * 64;
     return Q2A_OK;
 }
@@ -988,7 +1074,9 @@ q2a_gemm_args gemm_base(const q2a_engine * e, int l, int which, const q2a_half *
         a.dx = (const float *) (e->blob + m[A_DX]);
         a.dy = K == e->d.D ? e->dyD : e->dyF;
         a.dy_ld = e->dy_ld;
-        if (e->blk == 256) {
+        if (e->gblk == Q2A_BLK_Q6K) {
+            a.sc = (const float *) (e->blob + m[A_SC]);
+        } else if (e->blk == 256) {
             a.dmin = (const float *) (e->blob + m[A_DMIN]);
             a.wext = (const q2a_half *) (e->blob + m[A_WEXT]);
             a.beta = (const float *) (e->blob + m[A_BETA]);
@@ -1107,8 +1195,8 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
             a.outH = e->actF; a.ldo = (int64_t) d.F * e->kx; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
             a.o_dup = mode == 3 ? 2 * d.F : 0;
             PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_H, e->gblk, s));
-        } else if (mode == 1 && q2a_gemm_wide_tiles(M, d.F, e->blk) &&
-                   e->fc1_path == 2 && q2a_gemm_pipe8(a, e->blk)) {
+        } else if (mode == 1 && q2a_gemm_wide_tiles(M, d.F, e->gblk) &&
+                   e->fc1_path == 2 && q2a_gemm_pipe8(a, e->gblk)) {   // (never Q6_K: its mode has no 8-phase kernel)
             // fused fc1 + GELU + Q8_K quantization of the fc2 input (one Q8_K block per 256-column tile)
             a.outH = e->actF; a.ldo = d.F; a.qdy = e->dyF; a.qaext = e->aextF;
             PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_Q8K, e->blk, s));
@@ -1117,14 +1205,14 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
             // GELU table from LDS on the way (same codes as the GELU epilogue + quantizer below)
             q2a_half * hH = (q2a_half *) e->hF;
             a.outH = hH; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_PRE_H, e->blk, s));
+            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_PRE_H, e->gblk, s));
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_gelu_quant_q8k(hH, M, d.F, e->g<const uint16_t *>(G_GELU), e->actF,
                                                                    e->dyF, e->aextF, e->dy_ld, s));
         } else {
             // GELU output is exactly fp16-valued (LUT): keep it as fp16, then quantize for fc2
             q2a_half * hH = (q2a_half *) e->hF;
             a.outH = hH; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_H, e->blk, s));
+            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_H, e->gblk, s));
             q2a_quant_args qa{nullptr, hH, M, d.F, mode, e->actF, e->dyF, e->aextF, e->dy_ld};
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_act(qa, s));
         }
@@ -1958,7 +2046,7 @@ int q2a_test_attention_varlen(q2a_engine * e, const float * q, const float * k, 
 struct q2a_projector {
     int device = 0;
     hipStream_t stream = nullptr;
-    int d_in = 0, d_out = 0, wtype = 0, blk = 0;
+    int d_in = 0, d_out = 0, wtype = 0, blk = 0, gblk = 0;   // blk: activation block, gblk: the GEMM's block mode
     void * wdev = nullptr;          // q2a_pack_linear layout
     uint64_t off[A_COUNT] = {};
     float * bias = nullptr;
@@ -1985,11 +2073,11 @@ q2a_projector * q2a_projector_open(const char * path, int device) {
     std::vector<uint8_t> packed;
     uint64_t off[A_COUNT];
     if (q2a_pack_linear(mf->data + wt->offset, wt->type, N, K, packed, off) != Q2A_OK)
-        return fail(Q2A_ERR_UNSUPPORTED, "weight type not supported (F16, Q4_K, Q8_0, Q4_0)");
+        return fail(Q2A_ERR_UNSUPPORTED, "weight type not supported (F16, Q4_K, Q5_K, Q6_K, Q8_0, Q4_0)");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) { (void) hipGetLastError(); return fail(Q2A_ERR_HIP, "no such HIP device"); }
     q2a_projector * p = new q2a_projector();
-    p->device = device; p->d_in = K; p->d_out = N; p->wtype = wt->type; p->blk = blk_of(wt->type);
+    p->device = device; p->d_in = K; p->d_out = N; p->wtype = wt->type; p->blk = blk_of(wt->type); p->gblk = gblk_of(wt->type);
     for (int i = 0; i < A_COUNT; ++i) p->off[i] = off[i];
     std::vector<uint16_t> gtab(65536);
     q2a_make_gelu_table(gtab.data());
@@ -2037,7 +2125,7 @@ int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float 
     const int64_t MP = (rows + 255) / 256 * 256;
     const size_t a_bytes = ((size_t) M * K * 2 + 255) & ~size_t(255);
     const size_t dy_bytes = blk ? ((size_t) (K / blk) * MP * 4 + 255) & ~size_t(255) : 0;
-    const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;
+    const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;   // (Q6_K: written by the quantizer, unread)
     const size_t need = a_bytes + dy_bytes + ae_bytes;
     if (need > p->ws_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -2070,7 +2158,9 @@ int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float 
         a.nblk = K / blk;
         a.dx = (const float *) (w + p->off[A_DX]);
         a.dy = dy; a.dy_ld = (int) MP;
-        if (blk == 256) {
+        if (p->gblk == Q2A_BLK_Q6K) {
+            a.sc = (const float *) (w + p->off[A_SC]);
+        } else if (blk == 256) {
             a.dmin = (const float *) (w + p->off[A_DMIN]);
             a.wext = (const q2a_half *) (w + p->off[A_WEXT]);
             a.beta = (const float *) (w + p->off[A_BETA]);
@@ -2078,7 +2168,7 @@ int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float 
             a.aext = aext;
         }
     }
-    LAUNCH(q2a_launch_gemm(a, Q2A_EPI_STORE_F, blk, s));
+    LAUNCH(q2a_launch_gemm(a, Q2A_EPI_STORE_F, p->gblk, s));
     return Q2A_OK;
 }
 

@@ -64,6 +64,8 @@ extern "C" size_t q2a_row_size(int t, int64_t n) {
         case Q2A_TYPE_Q4_0: return (size_t) (n / 32) * sizeof(q2a_block_q4_0);
         case Q2A_TYPE_Q8_0: return (size_t) (n / 32) * sizeof(q2a_block_q8_0);
         case Q2A_TYPE_Q4_K: return (size_t) (n / 256) * sizeof(q2a_block_q4_K);
+        case Q2A_TYPE_Q5_K: return (size_t) (n / 256) * sizeof(q2a_block_q5_K);
+        case Q2A_TYPE_Q6_K: return (size_t) (n / 256) * sizeof(q2a_block_q6_K);
         case Q2A_TYPE_Q8_K: return (size_t) (n / 256) * sizeof(q2a_block_q8_K);
         default: return 0;
     }
@@ -72,6 +74,8 @@ extern "C" size_t q2a_row_size(int t, int64_t n) {
 static_assert(sizeof(q2a_block_q4_0) == 18, "q4_0");
 static_assert(sizeof(q2a_block_q8_0) == 34, "q8_0");
 static_assert(sizeof(q2a_block_q4_K) == 144, "q4_K");
+static_assert(sizeof(q2a_block_q5_K) == 176, "q5_K");
+static_assert(sizeof(q2a_block_q6_K) == 210, "q6_K");
 static_assert(sizeof(q2a_block_q8_K) == 292, "q8_K");
 
 // ------------------------------------------------------------------------------------------------
@@ -299,6 +303,172 @@ extern "C" void q2a_quantize_row_q4_K(const float * x, void * vy, int64_t k) {
     }
 }
 
+// quantize_row_q5_K_ref, ggml-quants.c:2676-2761: Q4_K's scale / min search with 5-bit codes (nmax 31, its own search
+// range), the same 6-bit scale / min packing, the codes' fifth bits in qh
+extern "C" void q2a_quantize_row_q5_K(const float * x, void * vy, int64_t k) {
+    q2a_block_q5_K * y = (q2a_block_q5_K *) vy;
+    const int64_t nb = k / 256;
+    uint8_t L[256], Laux[32];
+    float weights[32], mins[8], scales[8];
+    for (int64_t i = 0; i < nb; i++) {
+        float max_scale = 0, max_min = 0;
+        for (int j = 0; j < 8; ++j) {
+            float sum_x2 = 0;
+            for (int l = 0; l < 32; ++l) sum_x2 += x[32 * j + l] * x[32 * j + l];
+            const float av_x = sqrtf(sum_x2 / 32);
+            for (int l = 0; l < 32; ++l) weights[l] = av_x + fabsf(x[32 * j + l]);
+            scales[j] = make_qkx2(32, 31, x + 32 * j, weights, L + 32 * j, &mins[j], Laux, -0.5f, 0.1f, 15);
+            if (scales[j] > max_scale) max_scale = scales[j];
+            if (mins[j] > max_min) max_min = mins[j];
+        }
+        const float inv_scale = max_scale > 0 ? 63.f / max_scale : 0.f;
+        const float inv_min = max_min > 0 ? 63.f / max_min : 0.f;
+        memset(y[i].scales, 0, 12);   // (every byte is assigned below before it is or-ed into)
+        for (int j = 0; j < 8; ++j) {
+            uint8_t ls = (uint8_t) nearest_int(inv_scale * scales[j]);
+            uint8_t lm = (uint8_t) nearest_int(inv_min * mins[j]);
+            ls = std::min<uint8_t>(63, ls);
+            lm = std::min<uint8_t>(63, lm);
+            if (j < 4) {
+                y[i].scales[j] = ls;
+                y[i].scales[j + 4] = lm;
+            } else {
+                y[i].scales[j + 4] = (uint8_t) ((ls & 0xF) | ((lm & 0xF) << 4));
+                y[i].scales[j - 4] |= (uint8_t) ((ls >> 4) << 6);
+                y[i].scales[j - 0] |= (uint8_t) ((lm >> 4) << 6);
+            }
+        }
+        y[i].d = q2a_fp32_to_fp16(max_scale / 63.f);
+        y[i].dmin = q2a_fp32_to_fp16(max_min / 63.f);
+        for (int j = 0; j < 8; ++j) {
+            uint8_t sc, m;
+            scale_min_k4(j, y[i].scales, &sc, &m);
+            const float d = q2a_fp16_to_fp32(y[i].d) * sc;
+            if (!d) continue;
+            const float dm = q2a_fp16_to_fp32(y[i].dmin) * m;
+            for (int ii = 0; ii < 32; ++ii) {
+                int l = nearest_int((x[32 * j + ii] + dm) / d);
+                L[32 * j + ii] = (uint8_t) std::max(0, std::min(31, l));
+            }
+        }
+        uint8_t * qh = y[i].qh;
+        uint8_t * ql = y[i].qs;
+        memset(qh, 0, 32);
+        uint8_t m1 = 1, m2 = 2;
+        for (int n = 0; n < 256; n += 64) {
+            for (int j = 0; j < 32; ++j) {
+                int l1 = L[n + j];
+                if (l1 > 15) { l1 -= 16; qh[j] |= m1; }
+                int l2 = L[n + j + 32];
+                if (l2 > 15) { l2 -= 16; qh[j] |= m2; }
+                ql[j] = (uint8_t) (l1 | (l2 << 4));
+            }
+            m1 = (uint8_t) (m1 << 2); m2 = (uint8_t) (m2 << 2);
+            ql += 32;
+        }
+        x += 256;
+    }
+}
+
+// make_qx_quants with rmse_type 1 and no weights, ggml-quants.c:1646-1713 (the w = x^2 weighted scale search, 19
+// candidate scales around -nmax / max)
+static float make_qx_rmse1(int n, int nmax, const float * x, int8_t * L) {
+    float max = 0, amax = 0;
+    for (int i = 0; i < n; ++i) {
+        const float ax = fabsf(x[i]);
+        if (ax > amax) { amax = ax; max = x[i]; }
+    }
+    if (amax < 1e-15f) {   // GROUP_MAX_EPS: all zero
+        for (int i = 0; i < n; ++i) L[i] = 0;
+        return 0.f;
+    }
+    float iscale = -nmax / max;
+    float sumlx = 0, suml2 = 0;
+    for (int i = 0; i < n; ++i) {
+        int l = nearest_int(iscale * x[i]);
+        l = std::max(-nmax, std::min(nmax - 1, l));
+        L[i] = (int8_t) (l + nmax);
+        const float w = x[i] * x[i];
+        sumlx += w * x[i] * l;
+        suml2 += w * l * l;
+    }
+    float scale = suml2 ? sumlx / suml2 : 0.0f;
+    float best = scale * sumlx;
+    for (int is = -9; is <= 9; ++is) {
+        if (is == 0) continue;
+        iscale = -(nmax + 0.1f * is) / max;
+        sumlx = suml2 = 0;
+        for (int i = 0; i < n; ++i) {
+            int l = nearest_int(iscale * x[i]);
+            l = std::max(-nmax, std::min(nmax - 1, l));
+            const float w = x[i] * x[i];
+            sumlx += w * x[i] * l;
+            suml2 += w * l * l;
+        }
+        if (suml2 > 0 && sumlx * sumlx > best * suml2) {
+            for (int i = 0; i < n; ++i) {
+                int l = nearest_int(iscale * x[i]);
+                L[i] = (int8_t) (nmax + std::max(-nmax, std::min(nmax - 1, l)));
+            }
+            scale = sumlx / suml2;
+            best = scale * sumlx;
+        }
+    }
+    return scale;
+}
+
+// quantize_row_q6_K_ref, ggml-quants.c:2907-2975: sixteen sub-blocks of 16 with int8 scales (the largest mapped to
+// -128), codes q - 32 in -32 .. 31
+extern "C" void q2a_quantize_row_q6_K(const float * x, void * vy, int64_t k) {
+    q2a_block_q6_K * y = (q2a_block_q6_K *) vy;
+    const int64_t nb = k / 256;
+    int8_t L[256];
+    float scales[16];
+    for (int64_t i = 0; i < nb; i++) {
+        float max_scale = 0, max_abs_scale = 0;
+        for (int ib = 0; ib < 16; ++ib) {
+            const float scale = make_qx_rmse1(16, 32, x + 16 * ib, L + 16 * ib);
+            scales[ib] = scale;
+            const float abs_scale = fabsf(scale);
+            if (abs_scale > max_abs_scale) { max_abs_scale = abs_scale; max_scale = scale; }
+        }
+        if (max_abs_scale < 1e-15f) {   // GROUP_MAX_EPS
+            memset(&y[i], 0, sizeof(q2a_block_q6_K));
+            y[i].d = q2a_fp32_to_fp16(0.f);
+            x += 256;
+            continue;
+        }
+        const float iscale = -128.f / max_scale;
+        y[i].d = q2a_fp32_to_fp16(1 / iscale);
+        for (int ib = 0; ib < 16; ++ib) y[i].scales[ib] = (int8_t) std::min(127, nearest_int(iscale * scales[ib]));
+        for (int j = 0; j < 16; ++j) {
+            const float d = q2a_fp16_to_fp32(y[i].d) * y[i].scales[j];
+            if (!d) continue;
+            for (int ii = 0; ii < 16; ++ii) {
+                int l = nearest_int(x[16 * j + ii] / d);
+                l = std::max(-32, std::min(31, l));
+                L[16 * j + ii] = (int8_t) (l + 32);
+            }
+        }
+        uint8_t * ql = y[i].ql;
+        uint8_t * qh = y[i].qh;
+        for (int j = 0; j < 256; j += 128) {
+            for (int l = 0; l < 32; ++l) {
+                const uint8_t q1 = L[j + l + 0] & 0xF;
+                const uint8_t q2 = L[j + l + 32] & 0xF;
+                const uint8_t q3 = L[j + l + 64] & 0xF;
+                const uint8_t q4 = L[j + l + 96] & 0xF;
+                ql[l + 0] = (uint8_t) (q1 | (q3 << 4));
+                ql[l + 32] = (uint8_t) (q2 | (q4 << 4));
+                qh[l] = (uint8_t) ((L[j + l] >> 4) | ((L[j + l + 32] >> 4) << 2) | ((L[j + l + 64] >> 4) << 4) | ((L[j + l + 96] >> 4) << 6));
+            }
+            ql += 64;
+            qh += 32;
+        }
+        x += 256;
+    }
+}
+
 extern "C" void q2a_quantize_row_q8_0(const float * x, void * vy, int64_t k) {
     q2a_block_q8_0 * y = (q2a_block_q8_0 *) vy;
     const int64_t nb = k / 32;
@@ -518,6 +688,8 @@ int ftype_to_wtype(int ft) {
         case Q2A_FTYPE_MOSTLY_Q4_0: return Q2A_TYPE_Q4_0;
         case Q2A_FTYPE_MOSTLY_Q8_0: return Q2A_TYPE_Q8_0;
         case Q2A_FTYPE_MOSTLY_Q4_K: return Q2A_TYPE_Q4_K;
+        case Q2A_FTYPE_MOSTLY_Q5_K: return Q2A_TYPE_Q5_K;
+        case Q2A_FTYPE_MOSTLY_Q6_K: return Q2A_TYPE_Q6_K;
         default: return -1;
     }
 }
@@ -614,6 +786,8 @@ extern "C" int q2a_quantize_model(const char * in_path, const char * out_path, i
     void (*qrow)(const float *, void *, int64_t);
     switch (qtype) {
         case Q2A_TYPE_Q4_K: ftype = Q2A_FTYPE_MOSTLY_Q4_K; qrow = q2a_quantize_row_q4_K; break;
+        case Q2A_TYPE_Q5_K: ftype = Q2A_FTYPE_MOSTLY_Q5_K; qrow = q2a_quantize_row_q5_K; break;
+        case Q2A_TYPE_Q6_K: ftype = Q2A_FTYPE_MOSTLY_Q6_K; qrow = q2a_quantize_row_q6_K; break;
         case Q2A_TYPE_Q8_0: ftype = Q2A_FTYPE_MOSTLY_Q8_0; qrow = q2a_quantize_row_q8_0; break;
         case Q2A_TYPE_Q4_0: ftype = Q2A_FTYPE_MOSTLY_Q4_0; qrow = q2a_quantize_row_q4_0; break;
         default: q2a_model_file_free(mf); return -2;

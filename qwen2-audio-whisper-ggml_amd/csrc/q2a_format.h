@@ -21,6 +21,8 @@ enum q2a_ggml_type {
     Q2A_TYPE_Q4_0 = 2,
     Q2A_TYPE_Q8_0 = 8,
     Q2A_TYPE_Q4_K = 12,
+    Q2A_TYPE_Q5_K = 13,
+    Q2A_TYPE_Q6_K = 14,
     Q2A_TYPE_Q8_K = 15,
 };
 
@@ -31,6 +33,8 @@ enum q2a_ggml_ftype {
     Q2A_FTYPE_MOSTLY_Q4_0 = 2,
     Q2A_FTYPE_MOSTLY_Q8_0 = 7,
     Q2A_FTYPE_MOSTLY_Q4_K = 12,
+    Q2A_FTYPE_MOSTLY_Q5_K = 13,
+    Q2A_FTYPE_MOSTLY_Q6_K = 14,
 };
 
 #define Q2A_FILE_MAGIC 0x67676d6cu
@@ -39,10 +43,12 @@ enum q2a_ggml_ftype {
 #define Q2A_QK8_0 32
 #define Q2A_QK4_0 32
 
-// block layouts (ggml/src/ggml-common.h:143-149, 186-191, 282-297, 329-335)
+// block layouts (ggml/src/ggml-common.h:143-149, 186-191, 282-297, 299-326, 329-335)
 typedef struct { uint16_t d; uint8_t qs[16]; } q2a_block_q4_0;           // 18 B / 32 weights
 typedef struct { uint16_t d; int8_t qs[32]; } q2a_block_q8_0;            // 34 B / 32 weights
 typedef struct { uint16_t d, dmin; uint8_t scales[12]; uint8_t qs[128]; } q2a_block_q4_K;  // 144 B / 256
+typedef struct { uint16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8_t qs[128]; } q2a_block_q5_K;  // 176 B / 256
+typedef struct { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; uint16_t d; } q2a_block_q6_K;         // 210 B / 256
 typedef struct { float d; int8_t qs[256]; int16_t bsums[16]; } q2a_block_q8_K;             // 292 B / 256
 
 // whisper_hparams order as stored (qwen2-whisper.cpp:1374-1384)
@@ -74,11 +80,14 @@ int q2a_write_synthetic_projector(const char * path, int d_in, int d_out, int ft
 
 // Re-quantize a F16/F32 model file the way whisper.cpp's quantize flow does (examples/common-ggml.cpp:41-244
 // with to_quant {".*"} and skip {"embed_positions.weight","conv1.bias","conv2.bias"}; only 2-D tensors).
-// qtype: Q2A_TYPE_Q4_K / Q2A_TYPE_Q8_0 / Q2A_TYPE_Q4_0. Byte-identical to ggml_quantize_chunk. 0 on success.
+// qtype: Q2A_TYPE_Q4_K / Q2A_TYPE_Q5_K / Q2A_TYPE_Q6_K / Q2A_TYPE_Q8_0 / Q2A_TYPE_Q4_0. Byte-identical to
+// ggml_quantize_chunk. 0 on success.
 int q2a_quantize_model(const char * in_path, const char * out_path, int qtype, int n_threads);
 
 // Row quantizers (ggml "_ref" weight quantizers, byte-exact): k must be a multiple of the block size.
 void q2a_quantize_row_q4_K(const float * x, void * y, int64_t k);   // quantize_row_q4_K_ref ggml-quants.c:2483
+void q2a_quantize_row_q5_K(const float * x, void * y, int64_t k);   // quantize_row_q5_K_ref ggml-quants.c:2676
+void q2a_quantize_row_q6_K(const float * x, void * y, int64_t k);   // quantize_row_q6_K_ref ggml-quants.c:2907
 void q2a_quantize_row_q8_0(const float * x, void * y, int64_t k);   // quantize_row_q8_0_ref ggml-quants.c:848
 void q2a_quantize_row_q4_0(const float * x, void * y, int64_t k);   // quantize_row_q4_0_ref ggml-quants.c:761
 

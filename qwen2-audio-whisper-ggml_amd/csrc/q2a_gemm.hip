@@ -684,7 +684,11 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
     //   BLK=256: dy_{b-1}[BM] | dy_b[BM] f32 | aext[BM][16] f16 | beta[BN] | gamma[BN] | dx[BN] f32 | wext[BN][16] f16
     //            (two buffers by block parity: block b+1's scales land while block b computes)
     //   BLK=32 : dy[2][BM] f32 | dx[2][BN] f32 for the two 32-blocks of a K-step            (two buffers)
-    constexpr int SB = BLK == 256 ? (BM * 8 + BM * 32 + BN * 12 + BN * 32) : BLK == 32 ? 2 * (BM * 4 + BN * 4) : 0;
+    //   Q6_K   : dy[BM] | dx[BN] of the K-step's 256-block | sc[4][BN] of its four sub-blocks, f32 (two buffers)
+    constexpr bool Q6 = BLK == Q2A_BLK_Q6K;
+    static_assert(!Q6 || PIPE == 0, "Q6_K: small-tile kernels only");
+    constexpr int SB = BLK == 256 ? (BM * 8 + BM * 32 + BN * 12 + BN * 32) : BLK == 32 ? 2 * (BM * 4 + BN * 4)
+                       : Q6 ? BM * 4 + BN * 4 + 4 * BN * 4 : 0;
     constexpr int NSB = BLK ? 2 : 1;
     constexpr int NT = NW * 64;
     constexpr int SCH = (SB / 16 + NT - 1) / NT;          // 16-B scale chunks per thread
@@ -718,7 +722,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
     constexpr int NS_MAX = BLK == 256 ? 6 - SP : 5;
     // deep pipelines only on the narrow 64-row tiles (grids under one workgroup per CU); the 128-row tiles keep two
     // stages so two workgroups share a CU (their grids have several tiles per CU)
-    constexpr int NS = EX ? 2 : PIPE || BLK == 32 || BM > 64 ? 2 : (NS_FIT >= NS_MAX ? NS_MAX : NS_FIT >= 2 ? NS_FIT : 2);
+    constexpr int NS = EX ? 2 : PIPE || BLK == 32 || Q6 || BM > 64 ? 2 : (NS_FIT >= NS_MAX ? NS_MAX : NS_FIT >= 2 ? NS_FIT : 2);
     static_assert(PIPE || BLK != 256 || SP + NS <= 6, "Q4_K scale prefetch distance");
     static_assert(NBUF == 2 || (NS == 2 && SP <= 3), "single Q4_K scale buffer: pieces on steps 4b+1 .. 4b+3");
     constexpr int LDS_MAIN = PIPE == 2 ? SBUF_OFF + SBUF_BYTES + 512 : PIPE ? (BLK ? SBUF_OFF + SBUF_BYTES : 2 * OPB) : NS * OPB + SCALE_LDS;
@@ -936,6 +940,12 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
                 if (c < BN / 4) return (const uint4 *) (p.dx + (int64_t) g * p.N + n0) + c;
                 c -= BN / 4;
                 return (const uint4 *) (p.wext + ((int64_t) g * p.N + n0) * 16) + c;
+            } else if (Q6) {   // g = the K-step: its 256-block g / 4, its sub-blocks 4g .. 4g + 3
+                if (c < BM / 4) return (const uint4 *) (p.dy + (int64_t) (g / 4) * p.dy_ld + m0) + c;
+                c -= BM / 4;
+                if (c < BN / 4) return (const uint4 *) (p.dx + (int64_t) (g / 4) * p.N + n0) + c;
+                c -= BN / 4;
+                return (const uint4 *) (p.sc + (int64_t) (4 * g + c / (BN / 4)) * p.N + n0) + c % (BN / 4);
             } else {
                 if (c < BM / 2) return (const uint4 *) (p.dy + (int64_t) (2 * g + c / (BM / 4)) * p.dy_ld + m0) + c % (BM / 4);
                 c -= BM / 2;
@@ -954,7 +964,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
             if (q >= SBP || g >= p.K / 256) dst = sbuf + NBUF * SBP * 1024 + wave * 1024;
             __builtin_amdgcn_global_load_lds((const void *) src, (lds_ptr_t) dst, 16, 0, 0);
         };
-        uint4 sreg[BLK == 32 ? SCH : 1];
+        uint4 sreg[(BLK == 32 || Q6) ? SCH : 1];
         auto scale_load = [&](int g) {
     #pragma unroll
             for (int u = 0; u < SCH; ++u) {
@@ -975,6 +985,14 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
         constexpr bool FRESH = BLK == 32 || EX;
         f4 blk[FRESH ? MI : 1][FRESH ? NJ : 1];
         double acc64[EX ? MI : 1][EX ? NJ : 1][4];
+        // Q6_K: the 256-block's integer sum Σ_j sc_j Σ (q - 32) y, built from one fresh 16-deep product per sub-block
+        f4 bi[Q6 ? MI : 1][Q6 ? NJ : 1];
+        if (Q6) {
+    #pragma unroll
+            for (int i = 0; i < (Q6 ? MI : 1); ++i)
+    #pragma unroll
+                for (int j = 0; j < (Q6 ? NJ : 1); ++j) bi[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+        }
         if (FRESH) {
     #pragma unroll
             for (int i = 0; i < (FRESH ? MI : 1); ++i)
@@ -1027,7 +1045,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
         // prologue: block 0's scales, then stages 0 .. NS-2; K-step kt reads stage kt % NS and, before its MFMAs,
         // issues stage kt + NS - 1 into the slot K-step kt - 1 read (behind the barrier that ended kt - 1)
         constexpr int GL = LA + LB;                       // glds instructions per stage per thread
-        if (BLK == 32) scale_load(gb0);
+        if (BLK == 32 || Q6) scale_load(gb0);
         if (BLK == 256) {                                 // block 0's scales, every piece
     #pragma unroll
             for (int u = 0; u < SP; ++u) scale_piece(u * NW + wave, 0);
@@ -1036,7 +1054,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
         for (int q = 0; q < NS - 1; ++q)
             if (q < nk) stage(LDS_STAGE(q), kb0 + q * BK);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (BLK == 32) scale_store(0);
+        if (BLK == 32 || Q6) scale_store(0);
         __syncthreads();
 
         for (int kt = 0; kt < nk; ++kt) {
@@ -1053,7 +1071,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
                 if (kt % 4 == 0) kq_block_start(sbuf + ((kt / 4) & (NBUF - 1)) * SBP * 1024, std::false_type{});
                 if (NBUF == 2 && kt % 4 < SP) scale_piece((kt % 4) * NW + wave, kt / 4 + 1);   // uniform: one per wave
                 if (NBUF == 1 && kt % 4 >= 1 && kt % 4 <= SP) scale_piece((kt % 4 - 1) * NW + wave, kt / 4 + 1);
-            } else if (BLK == 32 && kt + 1 < nk) {
+            } else if ((BLK == 32 || Q6) && kt + 1 < nk) {
                 sload = true;
                 scale_load(gb0 + kt + 1);
             }
@@ -1065,6 +1083,37 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
                 half8 b[NJ];
     #pragma unroll
                 for (int j = 0; j < NJ; ++j) b[j] = frag(iw, wn * (BN / WN) + j * 16 + (lane & 15), chunk);
+                if constexpr (Q6) {
+                    // this 32-deep half of the K-step holds sub-blocks 2s (lanes 0..31: k = 0..15) and 2s + 1 (lanes
+                    // 32..63): one 16x16x32 per sub-block with the other sub-block's activation lanes zeroed (the 16-deep
+                    // product at the 32-deep fragment layout, so the tile images and their ds_read_b128 reads stay),
+                    // each into a fresh fragment: an exact integer, times the sub-block's integer scale per column
+                    const float * s_sc = (const float *) (sbuf + (kt & 1) * SB + BM * 4 + BN * 4) + 2 * s * BN;
+                    f4 sc0[NJ], sc1[NJ];
+    #pragma unroll
+                    for (int j = 0; j < NJ; ++j) {
+                        sc0[j] = *(const f4 *) (s_sc + wn * (BN / WN) + j * 16 + (lane >> 4) * 4);
+                        sc1[j] = *(const f4 *) (s_sc + BN + wn * (BN / WN) + j * 16 + (lane >> 4) * 4);
+                    }
+                    const bool lo = lane < 32;
+                    const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    #pragma unroll
+                    for (int i = 0; i < MI; ++i) {
+                        const half8 a = frag(ia, wm * (BM / WM) + i * 16 + (lane & 15), chunk);
+                        const half8 a0 = lo ? a : z, a1 = lo ? z : a;
+    #pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+                            const f4 p0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[j], a0, f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                            const f4 p1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[j], a1, f4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    #pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                bi[i][j][r] += sc0[j][r] * p0[r];
+                                bi[i][j][r] += sc1[j][r] * p1[r];
+                            }
+                        }
+                    }
+                    continue;
+                }
     #pragma unroll
                 for (int i = 0; i < MI; ++i) {
                     const half8 a = frag(ia, wm * (BM / WM) + i * 16 + (lane & 15), chunk);
@@ -1091,6 +1140,25 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
     #pragma unroll
                             for (int r = 0; r < 4; ++r) acc[i][j][r] += (dx[j][r] * dyi) * blk[i][j][r];
                             blk[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+                        }
+                    }
+                }
+            }
+            if constexpr (Q6) {
+                if (kt % 4 == 3) {   // the 256-block is complete: acc += (dx * dy) * blkI (ggml: fmadd(d, sumi, acc))
+                    const float * s_dy = (const float *) (sbuf + (kt & 1) * SB);
+                    const float * s_dx = s_dy + BM;
+                    f4 dx[NJ];
+    #pragma unroll
+                    for (int j = 0; j < NJ; ++j) dx[j] = *(const f4 *) (s_dx + wn * (BN / WN) + j * 16 + (lane >> 4) * 4);
+    #pragma unroll
+                    for (int i = 0; i < MI; ++i) {
+                        const float dyi = s_dy[wm * (BM / WM) + i * 16 + (lane & 15)];
+    #pragma unroll
+                        for (int j = 0; j < NJ; ++j) {
+    #pragma unroll
+                            for (int r = 0; r < 4; ++r) acc[i][j][r] += (dx[j][r] * dyi) * bi[i][j][r];
+                            bi[i][j] = f4{0.f, 0.f, 0.f, 0.f};
                         }
                     }
                 }
@@ -1887,6 +1955,14 @@ hipError_t launch_epi(const q2a_gemm_args & a, int blk, hipStream_t s) {
         if (blk == 32) {
             if (narrow) return launch_cfg<64, 128, 4, 2, EPI, 32>(a, s);
             return big ? launch_cfg<128, 256, 2, 4, EPI, 32>(a, s) : launch_cfg<128, 128, 2, 2, EPI, 32>(a, s);
+        }
+        if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_PRE_H ||
+                      EPI == Q2A_EPI_STORE_F) {
+            // Q6_K: one tile configuration whatever the batch (one K order and one block sum: batch invariant)
+            if (blk == Q2A_BLK_Q6K) {
+                if (!a.sc || !a.dx || !a.dy || a.K % 256 != 0) return hipErrorInvalidValue;
+                return launch_cfg<128, 128, 2, 2, EPI, Q2A_BLK_Q6K>(a, s);
+            }
         }
         if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_STORE_F) {
             if (blk == Q2A_BLK_BF16) {

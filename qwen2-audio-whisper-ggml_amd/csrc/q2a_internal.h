@@ -66,7 +66,10 @@ struct q2a_gemm_args {
     const float * dx;                 // [nblk][N]
     const float * dmin;               // [nblk][N] (Q4_K only)
     const q2a_half * aext;            // [nblk][dy_ld][16] bsum hi/lo pairs (Q4_K only)
-    const q2a_half * wext;            // [nblk][N][16] (64*m_j, m_j) pairs (Q4_K only)
+    union {                           // (one slot: the struct's layout, hence every kernel's argument offsets, stays)
+        const q2a_half * wext;        // [nblk][N][16] (64*m_j, m_j) pairs (Q4_K / Q5_K only)
+        const float * sc;             // Q2A_BLK_Q6K: sub-block-major integer scales [K/16][N] (with dx [K/256][N], dy [K/256][dy_ld])
+    };
     const float * beta;               // [nblk][N] dx_{b-1}/dx_b  (Q4_K 8-phase path: block-ratio rescaling)
     const float * gamma;              // [nblk][N] -(dmin_b/dx_b), negated so the recurrence's addend is gamma * S2
     float * qdy;                      // Q2A_EPI_GELU_Q8K outputs: block-major d [N/256][dy_ld] and
@@ -113,7 +116,7 @@ struct q2a_gemm_args {
 int q2a_gemm_resid_ksplit(int M, int N, int K, int blk);
 // the same for the block-quantized weights (whole scale groups per split), used when a.split_kq is set
 int q2a_gemm_kq_ksplit(int M, int N, int K, int blk);
-// blk: 0 (plain fp16 GEMM), 256 (Q4_K x Q8_K), 32 (Q8_0/Q4_0 x Q8_0), Q2A_BLK_BF16 (bf16 x bf16 MFMA, no block
+// blk: 0 (plain fp16 GEMM), 256 (Q4_K / Q5_K x Q8_K), 32 (Q8_0/Q4_0 x Q8_0), Q2A_BLK_Q6K (below), Q2A_BLK_BF16 (bf16 x bf16 MFMA, no block
 // scales: the bf16-activation mode, whose fp16-typed operand and output pointers then hold bf16 bits)
 constexpr int Q2A_BLK_BF16 = 1;
 // Q2A_BLK_EXACT: fp16 x fp16 (like blk 0) with each 64-deep K-step's MFMA sum (two chained 16x16x32) added into f64
@@ -121,6 +124,13 @@ constexpr int Q2A_BLK_BF16 = 1;
 // backend's conv MUL_MAT): summed this way the conv output is within rounding of the exact dot product instead of
 // carrying a 120-deep f32 accumulation chain ("the conv's own summation")
 constexpr int Q2A_BLK_EXACT = 2;
+// Q2A_BLK_Q6K: Q6_K x Q8_K. W holds q - 32 and A the Q8_K codes (both exact fp16 integers); per 64-deep K-step four
+// 16-deep products, one per Q6_K sub-block, each into a fresh f32 fragment: blkI += sc[n] * part (exact: part is an
+// integer <= 16*32*127, sc an int8), and after every fourth K-step acc += (dx[n] * dy[m]) * blkI, blkI = 0 — ggml's
+// acc = fmadd(d, sumi, acc) per 256-block (ggml_vec_dot_q6_K_q8_K). One tile configuration (128x128, 4 waves) in every
+// batch regime, so a clip's outputs do not depend on its batch; K % 256 == 0; epilogues QKV (V row-major or V^T),
+// RESID, GELU_H, PRE_H, STORE_F
+constexpr int Q2A_BLK_Q6K = 16;
 hipError_t q2a_launch_gemm(const q2a_gemm_args & a, int epi, int blk, hipStream_t s);
 // true when the launcher will use the 256-column tile configuration for this shape (Q2A_EPI_GELU_Q8K needs it)
 bool q2a_gemm_wide_tiles(int M, int N, int blk);

@@ -1,8 +1,8 @@
-// q2a_tool — model-file tooling CLI ("the build's own loader and Q4_K/Q8_0 quantizer
+// q2a_tool — model-file tooling CLI ("the build's own loader and k-quant/Q8_0 quantizer
 // for the unchanged ggml file"; the reference ships no quantize executable).
 //
 //   q2a_tool gen-model OUT {tiny|full|L,D,H,M} {f32|f16} [seed] [threads]
-//   q2a_tool quantize IN OUT {q4_k|q8_0|q4_0} [threads]
+//   q2a_tool quantize IN OUT {q4_k|q5_k|q6_k|q8_0|q4_0} [threads]
 //   q2a_tool synth-clip OUT.f32 N_SAMPLES CLIP_INDEX
 //   q2a_tool gen-projector OUT D_IN D_OUT {f32|f16} [seed]   (Qwen2-Audio multi-modal projector, q2a_format.cpp)
 #include "../csrc/q2a_format.h"
@@ -16,7 +16,7 @@
 static int usage() {
     fprintf(stderr,
             "usage:\n  q2a_tool gen-model OUT {tiny|full|L,D,H,M} {f32|f16} [seed] [threads]\n"
-            "  q2a_tool quantize IN OUT {q4_k|q8_0|q4_0} [threads]\n"
+            "  q2a_tool quantize IN OUT {q4_k|q5_k|q6_k|q8_0|q4_0} [threads]\n"
             "  q2a_tool synth-clip OUT.f32 N_SAMPLES CLIP_INDEX\n"
             "  q2a_tool gen-projector OUT D_IN D_OUT {f32|f16} [seed]\n");
     return 1;
@@ -42,7 +42,7 @@ int main(int argc, char ** argv) {
     }
     if (cmd == "quantize" && argc >= 5) {
         const std::string t = argv[4];
-        const int qt = t == "q4_k" ? Q2A_TYPE_Q4_K : t == "q8_0" ? Q2A_TYPE_Q8_0 : t == "q4_0" ? Q2A_TYPE_Q4_0 : -1;
+        const int qt = t == "q4_k" ? Q2A_TYPE_Q4_K : t == "q5_k" ? Q2A_TYPE_Q5_K : t == "q6_k" ? Q2A_TYPE_Q6_K : t == "q8_0" ? Q2A_TYPE_Q8_0 : t == "q4_0" ? Q2A_TYPE_Q4_0 : -1;
         if (qt < 0) return usage();
         return q2a_quantize_model(argv[2], argv[3], qt, argc > 5 ? atoi(argv[5]) : 8);
     }
