@@ -259,6 +259,25 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
  * quantizer, 1 GELU in the fc1 epilogue + quantizer, 2 GELU + Q8_K fused into the fc1 epilogue. All three give
  * identical codes (tests/test_gpu_parity.py::test_deferred_gelu_equals_epilogue_gelu); a test hook, not a tuning knob. */
 int q2a_test_fc1_path(q2a_engine * e, int path);
+/* One activation conversion — the kernels that write a weight GEMM's A operand — on caller rows, launched with the
+ * arguments and dispatch of the encoder block and q2a_test_linear. The engine supplies the device, the stream and the
+ * GELU table only: M and K are free (any model file serves), within the launchers' own limits.
+ *   producer  Q2A_OPERAND_LN         LayerNorm(x; g, b) + conversion: x f32 [M][K], g, b f32 [K], K % 4 == 0, K <= 2048;
+ *                                    mode 0 fp16, 1 Q8_K, 2 Q8_0, 3 the F32 files' split [M][3K] = hi | lo | hi, 4 bf16
+ *             Q2A_OPERAND_QUANT_F32  quantizer of f32 rows x [M][K] (the O-projection operand; K > 2048: the 1024-wide
+ *                                    segments of the fc2 operand), mode 1 or 2, K % 256 == 0, K <= 8192
+ *             Q2A_OPERAND_QUANT_H16  the same on fp16 rows x [M][K]
+ *             Q2A_OPERAND_GELU_Q8K   GELU table + Q8_K of fp16 pre-activation rows x [M][K], mode 1, M * K < 2^31
+ *   out       [M][K] 2-byte elements (mode 3: [M][3K]): fp16 / bf16 values, or the integer codes held in fp16
+ *   dy        modes 1, 2: the block scales, block-major f32 [K/256 or K/32][ld], block bf of row m at dy[bf * ld + m]
+ *   aext      mode 1: the block-sum operand, fp16 [K/256][ld][16] — for each of the 8 32-wide sub-blocks the pair
+ *             (hi, lo), bsum32 = 64 hi + lo, 0 <= lo < 64
+ *   ld        leading dimension of dy and aext, >= M
+ * Nothing outside rows 0 .. M-1 of out, dy and aext is written. g, b, dy, aext may be NULL where the mode has no use
+ * for them. Q2A_ERR_ARG for anything else. */
+enum { Q2A_OPERAND_LN = 0, Q2A_OPERAND_QUANT_F32 = 1, Q2A_OPERAND_QUANT_H16 = 2, Q2A_OPERAND_GELU_Q8K = 3 };
+int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x_dev, int M, int K, const float * g_dev,
+                     const float * b_dev, void * out_dev, float * dy_dev, void * aext_dev, int ld, void * stream);
 /* Attention only: q,k,v [n_clips*T][D] f32 (q already scaled), out [n_clips*T][D] f32.
  * Every operand enters the kernel as an fp16 pair hi = fp16(x), lo = fp16(x - hi) (q after the log2 e factor), which
  * carries 22 bits only while x - hi stays above fp16's 2^-24 spacing. Against float64 the F32-class bar (2e-5 max-rel,

@@ -1997,6 +1997,37 @@ int q2a_test_fc1_path(q2a_engine * e, int path) {
     return Q2A_OK;
 }
 
+// one conversion kernel on caller rows, launched exactly as run_block / q2a_test_linear launch it; the engine gives
+// the device, the stream and the GELU table only (M and K are the caller's, not the model's)
+int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x, int M, int K, const float * g, const float * b,
+                     void * out, float * dy, void * aext, int ld, void * stream) {
+    if (!e || !x || !out || M <= 0 || K <= 0 || ld < M) return Q2A_ERR_ARG;
+    const bool quant = mode == 1 || mode == 2;
+    if (quant && (!dy || (mode == 1 && !aext))) return Q2A_ERR_ARG;
+    if (mode == 1 && K % 256) return Q2A_ERR_ARG;
+    if (mode == 2 && K % 32) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    if (producer == Q2A_OPERAND_LN) {
+        if (mode < 0 || mode > 4 || !g || !b || K % 4 || K > 2048) return Q2A_ERR_ARG;
+        q2a_ln_args ln{(const float *) x, M, K, g, b, mode, (q2a_half *) out, dy, (q2a_half *) aext, ld};
+        LAUNCH(q2a_launch_layernorm(ln, s));
+    } else if (producer == Q2A_OPERAND_QUANT_F32 || producer == Q2A_OPERAND_QUANT_H16) {
+        if (!quant || K % 256 || K > 8192) return Q2A_ERR_ARG;
+        const bool h16 = producer == Q2A_OPERAND_QUANT_H16;
+        q2a_quant_args qa{h16 ? nullptr : (const float *) x, h16 ? (const q2a_half *) x : nullptr, M, K, mode,
+                          (q2a_half *) out, dy, (q2a_half *) aext, ld};
+        LAUNCH(q2a_launch_quant_act(qa, s));
+    } else if (producer == Q2A_OPERAND_GELU_Q8K) {
+        if (mode != 1 || (int64_t) M * K >= ((int64_t) 1 << 31)) return Q2A_ERR_ARG;
+        LAUNCH(q2a_launch_gelu_quant_q8k((const q2a_half *) x, M, K, e->g<const uint16_t *>(G_GELU), (q2a_half *) out, dy,
+                                         (q2a_half *) aext, ld, s));
+    } else {
+        return Q2A_ERR_ARG;
+    }
+    return Q2A_OK;
+}
+
 // attention only: q, k, v, out are the windows [n_clips*T][D], or for ENC_PACKED the packed rows [M_tot][D]
 // (q2a_varlen_rows over key_len)
 static int test_attention(q2a_engine * e, encode_kind kind, const float * q, const float * k, const float * v, int n_clips,

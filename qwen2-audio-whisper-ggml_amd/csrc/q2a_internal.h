@@ -28,7 +28,10 @@ enum q2a_epi {
                             // the Q8_K quantizer applies (q2a_launch_gelu_quant_q8k). ggml's x <= -10 branch (+0) needs
                             // no marker: for every fp16 h <= -10 the table holds -0 (tanhf saturates: 0.5 h (1 - 1)),
                             // or +0 (the patched -inf entry), and Q8_K turns +0 and -0 into the same code 0 (|x| for
-                            // the block max, nearest_int(-0) = 0), so the fc2 operand is bit-identical
+                            // the block max, nearest_int(-0) = 0), so the fc2 operand is bit-identical.
+                            // ggml's x >= 10 branch returns the f32 x; here (and in GELU_H + quantizer, and in the
+                            // 8-phase GELU_Q8K epilogue) it reaches the quantizer as fp16(x): a stated deviation,
+                            // pinned and measured in tests/test_gpu_operands.py
 };
 
 // compact GELU table: entries for fp16 bits 0x0000..0x4900 (+0..+10) then 0x8000..0xC900 (-0..-10), padded to

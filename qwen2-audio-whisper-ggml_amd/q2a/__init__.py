@@ -27,7 +27,7 @@ EXPORTS = (
     "q2a_valid_lengths", "q2a_encode_device_padded", "q2a_encode_host_padded", "q2a_test_attention_len",
     "q2a_test_block_len",
     "q2a_varlen_rows", "q2a_encode_device_varlen", "q2a_encode_host_varlen", "q2a_test_attention_varlen",
-    "q2a_test_block_varlen",
+    "q2a_test_block_varlen", "q2a_test_operand",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -45,6 +45,9 @@ class Info(C.Structure):
                 ("device", C.c_int32), ("weight_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
                 ("act", C.c_int32), ("reserved", C.c_int32)]
 
+
+# producers of q2a_test_operand (include/q2a_encoder.h)
+OPERAND_LN, OPERAND_QUANT_F32, OPERAND_QUANT_H16, OPERAND_GELU_Q8K = 0, 1, 2, 3
 
 # activation contracts (include/q2a_encoder.h)
 ACT_REFERENCE = 0
@@ -122,6 +125,8 @@ def lib() -> C.CDLL:
                          ("q2a_test_block_varlen", [vp, C.c_int, vp, C.c_int, i32p, vp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = at
+        if hasattr(L, "q2a_test_operand"):   # (optional like the hooks above)
+            L.q2a_test_operand.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
         if hasattr(L, "q2a_varlen_rows"):
             L.q2a_varlen_rows.restype = C.c_int64
             L.q2a_varlen_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
@@ -302,6 +307,12 @@ class Engine:
 
     def test_fc1_path(self, path):
         _check(lib().q2a_test_fc1_path(self.h, path))
+
+    def test_operand(self, producer, mode, x_ptr, M, K, out_ptr, dy_ptr=0, aext_ptr=0, ld=None, g_ptr=0, b_ptr=0, stream=None):
+        """q2a_test_operand: one conversion kernel (OPERAND_*) on caller rows; ld defaults to M."""
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_test_operand(self.h, producer, mode, p(x_ptr), M, K, p(g_ptr), p(b_ptr), p(out_ptr), p(dy_ptr),
+                                      p(aext_ptr), M if ld is None else ld, p(stream)))
 
     def test_attention(self, q_ptr, k_ptr, v_ptr, n_clips, out_ptr, stream=None):
         _check(lib().q2a_test_attention(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
