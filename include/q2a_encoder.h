@@ -278,6 +278,38 @@ int q2a_test_fc1_path(q2a_engine * e, int path);
 enum { Q2A_OPERAND_LN = 0, Q2A_OPERAND_QUANT_F32 = 1, Q2A_OPERAND_QUANT_H16 = 2, Q2A_OPERAND_GELU_Q8K = 3 };
 int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x_dev, int M, int K, const float * g_dev,
                      const float * b_dev, void * out_dev, float * dy_dev, void * aext_dev, int ld, void * stream);
+/* One weight GEMM of the encoder block with the block's own fused epilogue, on caller rows and into caller buffers.
+ * x_dev [M][K] f32 becomes the GEMM operand as in q2a_test_linear; the GEMM arguments come from the helpers run_block
+ * itself uses, with only the output pointers replaced by out[] — the kernel stores straight into the caller's memory,
+ * so a store outside rows 0 .. M-1 lands in the caller's guard rows.
+ *   which, epi                 out[]
+ *   0, Q2A_TEST_EPI_QKV        reference contract: Q hi, Q lo, K hi, K lo, V hi, V lo, fp16 [M][D] each (Q scaled as in
+ *                              the block); bf16 contract: Q, K bf16 [M][D] and V^T bf16 [clips][H][64][TP]
+ *   1 | 3, Q2A_TEST_EPI_RESID  one f32 [M][D] buffer: the residual on entry, (acc + bias) + residual on exit (in place)
+ *   2, Q2A_TEST_EPI_GELU_H     fp16 (bf16 contract: bf16) [M][F]; F32 files [M][3F] with the copy at column 2F
+ *   2, Q2A_TEST_EPI_PRE_H      fp16 [M][F]: Q4_K / Q5_K / Q6_K files (fc1 path 0)
+ *   2, Q2A_TEST_EPI_GELU_Q8K   codes fp16 [M][F], d f32 [F/256][ld], block sums fp16 [F/256][ld][16] as in
+ *                              q2a_test_operand; ld % 256 == 0, ld >= M; only where fc1 path 2 takes it (Q4_K-layout
+ *                              weights at a row count of the 8-phase wide tiles)
+ * ld is read for GELU_Q8K only. Q2A_ERR_ARG for every combination the block never launches on this engine (PRE_H on
+ * an F16 file, QKV with which != 0, ...). */
+enum { Q2A_TEST_EPI_QKV = 0, Q2A_TEST_EPI_RESID = 1, Q2A_TEST_EPI_GELU_H = 2, Q2A_TEST_EPI_GELU_Q8K = 6, Q2A_TEST_EPI_PRE_H = 7 };
+int q2a_test_gemm_epi(q2a_engine * e, int layer, int which, int epi, const float * x_dev, int M, void * const * out,
+                      int ld, void * stream);
+/* The tile regime the GEMM launcher picks for that GEMM at M rows on this engine's device (the launcher's own
+ * decision function, nothing is launched), or Q2A_ERR_ARG where q2a_test_gemm_epi would return it. */
+enum {
+    Q2A_REGIME_NONE = -1,             /* no kernel for these arguments */
+    Q2A_REGIME_NARROW = 0,            /* 64x128 tiles, 8 waves (few rows) */
+    Q2A_REGIME_128 = 1,               /* 128x128 tiles, 4 waves */
+    Q2A_REGIME_128x256 = 2,           /* 128x256 tiles, 8 waves (block-quantized weights, many rows) */
+    Q2A_REGIME_256 = 3,               /* 256x256 tiles without the 8-phase pipeline (fp16 / bf16, odd K-step count) */
+    Q2A_REGIME_PIPE8 = 4,             /* 8-phase 256x256 tiles, one grid */
+    Q2A_REGIME_PIPE8_PERSISTENT = 5,  /* 8-phase persistent workgroups walking a tile list */
+    Q2A_REGIME_PIPE8_TAIL = 6,        /* 8-phase whole rounds + 128x128 tiles on the rows of the partial round */
+    Q2A_REGIME_FIXED = 7              /* one configuration whatever M: Q6_K (128x128), the conv GEMMs' exact tiles */
+};
+int q2a_test_gemm_regime(q2a_engine * e, int which, int epi, int M);
 /* Attention only: q,k,v [n_clips*T][D] f32 (q already scaled), out [n_clips*T][D] f32.
  * Every operand enters the kernel as an fp16 pair hi = fp16(x), lo = fp16(x - hi) (q after the log2 e factor), which
  * carries 22 bits only while x - hi stays above fp16's 2^-24 spacing. Against float64 the F32-class bar (2e-5 max-rel,

@@ -1137,6 +1137,58 @@ hipError_t launch_attention(q2a_attn_args & at, const block_rows & rows, hipStre
     return rows.row_start ? q2a_launch_attention_varlen(at, s) : rows.key_len ? q2a_launch_attention_len(at, s) : q2a_launch_attention(at, s);
 }
 
+// ---- the four weight GEMMs of a block: their arguments, built here for run_block and for q2a_test_gemm_epi alike
+// (outputs into the workspace; the hook replaces the output pointers only)
+q2a_gemm_args qkv_gemm(const q2a_engine * e, int l, int M) {
+    q2a_gemm_args a = gemm_base(e, l, 0, e->actD, M);
+    a.bias = e->lv<const float *>(l, L_BQKV);
+    a.qh = e->qh; a.ql = e->ql; a.kh = e->kh; a.kl = e->kl; a.vt = e->vt; a.vtl = e->vtl;
+    a.v_rows = e->bf16 ? 0 : 1;   // reference contract: V hi / lo row-major like K (bf16 contract: V^T)
+    // ggml_scale(Q, 1/sqrt(dh)) (:2054); the reference-contract attention also wants log2(e) folded in (its
+    // softmax runs in log2 units): one f32 multiply by fl(log2 e)/8, 2^-3 being exact
+    a.qscale = (1.0f / sqrtf((float) (e->d.D / e->d.H))) * (e->bf16 ? 1.0f : Q2A_LOG2E);
+    return a;
+}
+
+// the O projection (which 1) and fc2 (which 3): (acc + bias) + X in place on the residual rows X
+q2a_gemm_args resid_gemm(const q2a_engine * e, int l, int which, int M, float * X) {
+    q2a_gemm_args a = gemm_base(e, l, which, which == 1 ? e->actD : e->actF, M);
+    a.bias = e->lv<const float *>(l, which == 1 ? L_BO : L_B2);
+    a.outF = X; a.ldo = e->d.D;
+    a.part = e->part; a.split_stride = (int64_t) M * e->d.D;
+    return a;
+}
+
+// fc1: which epilogue the block launches at M rows under fc1 path `path` (q2a_test_fc1_path), and its arguments
+int fc1_epi(const q2a_engine * e, int M, int path) {
+    const int mode = ln_mode(e);
+    if (mode == 0 || mode == 3 || mode == 4) return Q2A_EPI_GELU_H;
+    if (mode == 1 && path == 2 && q2a_gemm_wide_tiles(M, e->d.F, e->gblk) &&
+        q2a_gemm_pipe8(gemm_base(e, 0, 2, e->actD, M), e->gblk))   // (never Q6_K: its mode has no 8-phase kernel)
+        return Q2A_EPI_GELU_Q8K;
+    return mode == 1 && path != 1 ? Q2A_EPI_PRE_H : Q2A_EPI_GELU_H;
+}
+
+q2a_gemm_args fc1_gemm(const q2a_engine * e, int l, int M, int epi) {
+    const dims & d = e->d;
+    const int mode = ln_mode(e);
+    q2a_gemm_args a = gemm_base(e, l, 2, e->actD, M);
+    a.bias = e->lv<const float *>(l, L_B1);
+    if (mode == 0 || mode == 3 || mode == 4) {
+        // F32 weights: the GELU output is exactly fp16 (LUT), so the fc2 operand is [h | 0 | h] (middle third
+        // stays zero from the workspace memset) against [W2h | W2h | W2l]
+        a.outH = e->actF; a.ldo = (int64_t) d.F * e->kx; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
+        a.o_dup = mode == 3 ? 2 * d.F : 0;
+    } else if (epi == Q2A_EPI_GELU_Q8K) {
+        // fused fc1 + GELU + Q8_K quantization of the fc2 input (one Q8_K block per 256-column tile)
+        a.outH = e->actF; a.ldo = d.F; a.qdy = e->dyF; a.qaext = e->aextF;
+    } else {
+        // the fp16 pre-activation (Q2A_EPI_PRE_H) or the GELU output, exactly fp16-valued (LUT), for the quantizer
+        a.outH = (q2a_half *) e->hF; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
+    }
+    return a;
+}
+
 // one pre-LN encoder block on the M rows of `rows` (qwen2-whisper.cpp:2014-2155). Everything but the attention is a
 // function of M alone (rows are independent); dy_ld stays the workspace's stride.
 int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
@@ -1152,13 +1204,7 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
     PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln, s));
     LAUNCH(tap(0, e->actD, d.D));
     {
-        q2a_gemm_args a = gemm_base(e, l, 0, e->actD, M);
-        a.bias = e->lv<const float *>(l, L_BQKV);
-        a.qh = e->qh; a.ql = e->ql; a.kh = e->kh; a.kl = e->kl; a.vt = e->vt; a.vtl = e->vtl;
-        a.v_rows = e->bf16 ? 0 : 1;   // reference contract: V hi / lo row-major like K (bf16 contract: V^T)
-        // ggml_scale(Q, 1/sqrt(dh)) (:2054); the reference-contract attention also wants log2(e) folded in (its
-        // softmax runs in log2 units): one f32 multiply by fl(log2 e)/8, 2^-3 being exact
-        a.qscale = (1.0f / sqrtf((float) (d.D / d.H))) * (e->bf16 ? 1.0f : Q2A_LOG2E);
+        const q2a_gemm_args a = qkv_gemm(e, l, M);
         PLAUNCH(e, s, Q2A_PROF_GEMM_QKV, q2a_launch_gemm(a, Q2A_EPI_QKV, e->gblk, s));
     }
     {
@@ -1177,52 +1223,31 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
     }
     LAUNCH(tap(1, e->actD, d.D));
     {
-        q2a_gemm_args a = gemm_base(e, l, 1, e->actD, M);
-        a.bias = e->lv<const float *>(l, L_BO);
-        a.outF = X; a.ldo = d.D;
-        a.part = e->part; a.split_stride = (int64_t) M * d.D;
+        const q2a_gemm_args a = resid_gemm(e, l, 1, M, X);
         PLAUNCH(e, s, Q2A_PROF_GEMM_O, q2a_launch_gemm(a, Q2A_EPI_RESID, e->gblk, s));
     }
     q2a_ln_args ln2{X, M, d.D, e->lv<const float *>(l, L_LN2W), e->lv<const float *>(l, L_LN2B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
     PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln2, s));
     LAUNCH(tap(2, e->actD, d.D));
     {
-        q2a_gemm_args a = gemm_base(e, l, 2, e->actD, M);
-        a.bias = e->lv<const float *>(l, L_B1);
-        if (mode == 0 || mode == 3 || mode == 4) {
-            // F32 weights: the GELU output is exactly fp16 (LUT), so the fc2 operand is [h | 0 | h] (middle third
-            // stays zero from the workspace memset) against [W2h | W2h | W2l]
-            a.outH = e->actF; a.ldo = (int64_t) d.F * e->kx; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
-            a.o_dup = mode == 3 ? 2 * d.F : 0;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_H, e->gblk, s));
-        } else if (mode == 1 && q2a_gemm_wide_tiles(M, d.F, e->gblk) &&
-                   e->fc1_path == 2 && q2a_gemm_pipe8(a, e->gblk)) {   // (never Q6_K: its mode has no 8-phase kernel)
-            // fused fc1 + GELU + Q8_K quantization of the fc2 input (one Q8_K block per 256-column tile)
-            a.outH = e->actF; a.ldo = d.F; a.qdy = e->dyF; a.qaext = e->aextF;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_Q8K, e->blk, s));
-        } else if (mode == 1 && e->fc1_path != 1) {
-            // fc1 writes its fp16 pre-activation (plain stores); the Q8_K quantizer of the fc2 input applies the
+        const int epi = fc1_epi(e, M, e->fc1_path);
+        const q2a_gemm_args a = fc1_gemm(e, l, M, epi);
+        // the fused epilogue is a Q4_K-layout kernel (blk); every other fc1 launch goes by the engine's GEMM mode
+        PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, epi, epi == Q2A_EPI_GELU_Q8K ? e->blk : e->gblk, s));
+        if (epi == Q2A_EPI_PRE_H) {
+            // fc1 wrote its fp16 pre-activation (plain stores); the Q8_K quantizer of the fc2 input applies the
             // GELU table from LDS on the way (same codes as the GELU epilogue + quantizer below)
-            q2a_half * hH = (q2a_half *) e->hF;
-            a.outH = hH; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_PRE_H, e->gblk, s));
-            PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_gelu_quant_q8k(hH, M, d.F, e->g<const uint16_t *>(G_GELU), e->actF,
+            PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_gelu_quant_q8k(a.outH, M, d.F, e->g<const uint16_t *>(G_GELU), e->actF,
                                                                    e->dyF, e->aextF, e->dy_ld, s));
-        } else {
+        } else if (epi == Q2A_EPI_GELU_H && (mode == 1 || mode == 2)) {
             // GELU output is exactly fp16-valued (LUT): keep it as fp16, then quantize for fc2
-            q2a_half * hH = (q2a_half *) e->hF;
-            a.outH = hH; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
-            PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, q2a_launch_gemm(a, Q2A_EPI_GELU_H, e->gblk, s));
-            q2a_quant_args qa{nullptr, hH, M, d.F, mode, e->actF, e->dyF, e->aextF, e->dy_ld};
+            q2a_quant_args qa{nullptr, a.outH, M, d.F, mode, e->actF, e->dyF, e->aextF, e->dy_ld};
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_act(qa, s));
         }
     }
     LAUNCH(tap(3, e->actF, d.F));
     {
-        q2a_gemm_args a = gemm_base(e, l, 3, e->actF, M);
-        a.bias = e->lv<const float *>(l, L_B2);
-        a.outF = X; a.ldo = d.D;
-        a.part = e->part; a.split_stride = (int64_t) M * d.D;
+        const q2a_gemm_args a = resid_gemm(e, l, 3, M, X);
         PLAUNCH(e, s, Q2A_PROF_GEMM_FC2, q2a_launch_gemm(a, Q2A_EPI_RESID, e->gblk, s));
     }
     return Q2A_OK;
@@ -1882,13 +1907,10 @@ int q2a_profile_read(q2a_engine * e, double * ms, int64_t * counts, int n, int r
     return Q2A_OK;
 }
 
-int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M, float * y, void * stream) {
-    if (!e || layer < 0 || layer >= e->d.L || which < 0 || which > 3 || M <= 0) return Q2A_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t s = call_stream(stream);
+// x [M][K] f32 (device) -> the A operand of weight `which` in the workspace, by the engine's own mode (ggml's activation
+// conversion); dy_ld: the row stride of the block scales the GEMM will read
+static int stage_operand(q2a_engine * e, int which, const float * x, int M, int dy_ld, hipStream_t s, q2a_half ** A_out) {
     const dims & d = e->d;
-    int rc = reserve(e, (M + d.T - 1) / d.T);
-    if (rc) return rc;
     int N, K;
     mat_dims(d, which, N, K);
     q2a_half * A = K == d.D ? e->actD : e->actF;
@@ -1903,12 +1925,95 @@ int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M
         hipLaunchKernelGGL(k_split3, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, A, K, n);
         LAUNCH(hipGetLastError());
     } else {
-        q2a_quant_args qa{x, nullptr, M, K, mode, A, K == d.D ? e->dyD : e->dyF, K == d.D ? e->aextD : e->aextF, e->dy_ld};
+        q2a_quant_args qa{x, nullptr, M, K, mode, A, K == d.D ? e->dyD : e->dyF, K == d.D ? e->aextD : e->aextF, dy_ld};
         LAUNCH(q2a_launch_quant_act(qa, s));
     }
+    *A_out = A;
+    return Q2A_OK;
+}
+
+int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M, float * y, void * stream) {
+    if (!e || layer < 0 || layer >= e->d.L || which < 0 || which > 3 || M <= 0) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    const dims & d = e->d;
+    int rc = reserve(e, (M + d.T - 1) / d.T);
+    if (rc) return rc;
+    int N, K;
+    mat_dims(d, which, N, K);
+    q2a_half * A = nullptr;
+    if ((rc = stage_operand(e, which, x, M, e->dy_ld, s, &A))) return rc;
     q2a_gemm_args a = gemm_base(e, layer, which, A, M);
     a.outF = y; a.ldo = N;
     LAUNCH(q2a_launch_gemm(a, Q2A_EPI_STORE_F, e->gblk, s));
+    return Q2A_OK;
+}
+
+static_assert(Q2A_TEST_EPI_QKV == Q2A_EPI_QKV && Q2A_TEST_EPI_RESID == Q2A_EPI_RESID && Q2A_TEST_EPI_GELU_H == Q2A_EPI_GELU_H &&
+              Q2A_TEST_EPI_GELU_Q8K == Q2A_EPI_GELU_Q8K && Q2A_TEST_EPI_PRE_H == Q2A_EPI_PRE_H, "public epilogue numbers");
+
+// The block's GEMM `which` with epilogue `epi` at M rows, from run_block's own argument helpers, or false when the
+// block never launches that pair on this engine (fc1: under no fc1 path). blk: the launcher mode the block passes.
+static bool block_gemm(const q2a_engine * e, int layer, int which, int epi, int M, q2a_gemm_args & a, int & blk) {
+    blk = e->gblk;
+    if (which == 0 && epi == Q2A_EPI_QKV) { a = qkv_gemm(e, layer, M); return true; }
+    if ((which == 1 || which == 3) && epi == Q2A_EPI_RESID) { a = resid_gemm(e, layer, which, M, nullptr); return true; }
+    if (which != 2) return false;
+    for (int path = 0; path < 3; ++path)
+        if (fc1_epi(e, M, path) == epi) {
+            a = fc1_gemm(e, layer, M, epi);
+            if (epi == Q2A_EPI_GELU_Q8K) blk = e->blk;
+            return true;
+        }
+    return false;
+}
+
+int q2a_test_gemm_regime(q2a_engine * e, int which, int epi, int M) {
+    if (!e || which < 0 || which > 3 || M <= 0) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = reserve(e, 1)) return rc;   // (the launcher checks the workspace's scale pointers; no-op once reserved)
+    q2a_gemm_args a;
+    int blk = 0;
+    if (!block_gemm(e, 0, which, epi, M, a, blk)) return Q2A_ERR_ARG;
+    if (epi == Q2A_EPI_RESID) a.outF = (float *) e->blob;   // (any non-null pointer: the plan reads no output pointer)
+    const q2a_gemm_plan pl = q2a_gemm_plan_for(a, epi, blk);
+    return pl.regime == Q2A_REGIME_NONE ? Q2A_ERR_ARG : pl.regime;
+}
+
+int q2a_test_gemm_epi(q2a_engine * e, int layer, int which, int epi, const float * x, int M, void * const * out, int ld,
+                      void * stream) {
+    if (!e || layer < 0 || layer >= e->d.L || which < 0 || which > 3 || M <= 0 || !x || !out || !out[0]) return Q2A_ERR_ARG;
+    const bool q8k = epi == Q2A_EPI_GELU_Q8K;
+    if (q8k && (ld < M || ld % 256 || !out[1] || !out[2])) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    const dims & d = e->d;
+    // (the fused Q8_K epilogue writes its scales with the stride it reads the operand's with: ld on both sides)
+    int rc = reserve(e, (std::max(M, q8k ? ld : 0) + d.T - 1) / d.T);
+    if (rc) return rc;
+    q2a_gemm_args a;
+    int blk = 0;
+    if (!block_gemm(e, layer, which, epi, M, a, blk)) return Q2A_ERR_ARG;
+    const int dy_ld = q8k ? ld : e->dy_ld;
+    q2a_half * A = nullptr;
+    if ((rc = stage_operand(e, which, x, M, dy_ld, s, &A))) return rc;
+    a.dy_ld = dy_ld;
+    if (epi == Q2A_EPI_QKV) {
+        const int n = e->bf16 ? 3 : 6;
+        for (int i = 0; i < n; ++i) if (!out[i]) return Q2A_ERR_ARG;
+        if (e->bf16) {
+            a.qh = (q2a_half *) out[0]; a.kh = (q2a_half *) out[1]; a.vt = (q2a_half *) out[2];
+        } else {
+            a.qh = (q2a_half *) out[0]; a.ql = (q2a_half *) out[1]; a.kh = (q2a_half *) out[2]; a.kl = (q2a_half *) out[3];
+            a.vt = (q2a_half *) out[4]; a.vtl = a.vtl ? (q2a_half *) out[5] : nullptr;
+        }
+    } else if (epi == Q2A_EPI_RESID) {
+        a.outF = (float *) out[0];
+    } else {
+        a.outH = (q2a_half *) out[0];
+        if (q8k) { a.qdy = (float *) out[1]; a.qaext = (q2a_half *) out[2]; }
+    }
+    LAUNCH(q2a_launch_gemm(a, epi, blk, s));
     return Q2A_OK;
 }
 

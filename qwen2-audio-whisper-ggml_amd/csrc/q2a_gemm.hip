@@ -1881,40 +1881,6 @@ int cu_count() {
 // only for deep K: measured at 64 clips Q4_K (diag/gpurun_r03ta.sh, same box, alternating) fc2 (K = 5120) 45.2 -> 44.4
 // ms/step, but O (K = 1280) 17.05 -> 17.3 and fc1 (K = 1280) 48.6 -> 48.75 — a shallow tile's partial round costs less
 // than the second launch and the 128x128 tiles' lower rate.
-template <int EPI, int BLK>
-hipError_t launch_pipe8(const q2a_gemm_args & a, hipStream_t s) {
-    if constexpr ((EPI == Q2A_EPI_PRE_H || EPI == Q2A_EPI_QKV) && BLK == 256) {
-        // persistent tiles (k_gemm PIPE = 2): whole 256-row tiles only, at least two Q4_K blocks; Q|K|V only with V
-        // row-major (the V^T image needs the LDS-staged transposing epilogue)
-        const int cus = cu_count();
-        const int ntl = (a.N / 256) * ((a.M - a.m_base) / 256);
-        const int grid = std::min(ntl, cus / 8 * 8);
-        // (the workgroup's tile list holds 64 entries)
-        if ((a.M - a.m_base) % 256 == 0 && a.K >= 512 && ntl > 0 && cus >= 8 && ntl <= 64 * grid &&
-            (EPI != Q2A_EPI_QKV || (a.v_rows && a.vtl && a.D % 256 == 0))) {
-            hipLaunchKernelGGL((k_gemm<256, 256, 2, 4, EPI, BLK, 2>), dim3(grid), dim3(512), 0, s, a);
-            return hipGetLastError();
-        }
-    }
-    constexpr bool TAILABLE = (EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_PRE_H || EPI == Q2A_EPI_GELU_H);
-    if constexpr (TAILABLE) {
-        const int cus = cu_count();
-        const int nbn = a.N / 256, nbm = (a.M - a.m_base + 255) / 256;
-        const int64_t ntl = (int64_t) nbn * nbm, rem = cus > 0 ? ntl % cus : 0;
-        const int m_main = (int) ((ntl - rem) / nbn);   // whole M-tiles inside the full rounds
-        if (a.K >= 4096 && a.m_base == 0 && rem > 0 && rem * 8 <= (int64_t) cus * 5 && m_main > 0 && m_main < nbm) {
-            q2a_gemm_args h = a;
-            h.M = m_main * 256;
-            const hipError_t err = launch_cfg<256, 256, 2, 4, EPI, BLK, 1>(h, s);
-            if (err != hipSuccess) return err;
-            q2a_gemm_args t = a;
-            t.m_base = m_main * 256;
-            return launch_cfg<128, 128, 2, 2, EPI, BLK>(t, s);
-        }
-    }
-    return launch_cfg<256, 256, 2, 4, EPI, BLK, 1>(a, s);
-}
-
 // the 8-phase kernels: 256x256 tiles, 32-bit operand offsets, K-steps in pairs (fp16) or whole Q4_K blocks
 bool pipe8_ok(const q2a_gemm_args & a, int blk) {
     if (!wide_tiles(a.M, a.N)) return false;
@@ -1925,51 +1891,128 @@ bool pipe8_ok(const q2a_gemm_args & a, int blk) {
     return false;
 }
 
-template <int EPI>
-hipError_t launch_epi(const q2a_gemm_args & a, int blk, hipStream_t s) {
+// which of the 8-phase launches: the persistent kernel, the two-launch partial-round tail, or one 256x256 grid
+q2a_gemm_plan pipe8_plan(const q2a_gemm_args & a, int epi, int blk, int cus) {
+    if ((epi == Q2A_EPI_PRE_H || epi == Q2A_EPI_QKV) && blk == 256) {
+        // persistent tiles (k_gemm PIPE = 2): whole 256-row tiles only, at least two Q4_K blocks; Q|K|V only with V
+        // row-major (the V^T image needs the LDS-staged transposing epilogue)
+        const int ntl = (a.N / 256) * ((a.M - a.m_base) / 256);
+        const int grid = std::min(ntl, cus / 8 * 8);
+        // (the workgroup's tile list holds 64 entries)
+        if ((a.M - a.m_base) % 256 == 0 && a.K >= 512 && ntl > 0 && cus >= 8 && ntl <= 64 * grid &&
+            (epi != Q2A_EPI_QKV || (a.v_rows && a.vtl && a.D % 256 == 0)))
+            return {Q2A_REGIME_PIPE8_PERSISTENT, grid, 0};
+    }
+    if (epi == Q2A_EPI_RESID || epi == Q2A_EPI_PRE_H || epi == Q2A_EPI_GELU_H) {   // (TAILABLE in launch_pipe8)
+        const int nbn = a.N / 256, nbm = (a.M - a.m_base + 255) / 256;
+        const int64_t ntl = (int64_t) nbn * nbm, rem = cus > 0 ? ntl % cus : 0;
+        const int m_main = (int) ((ntl - rem) / nbn);   // whole M-tiles inside the full rounds
+        if (a.K >= 4096 && a.m_base == 0 && rem > 0 && rem * 8 <= (int64_t) cus * 5 && m_main > 0 && m_main < nbm)
+            return {Q2A_REGIME_PIPE8_TAIL, 0, m_main};
+    }
+    return {Q2A_REGIME_PIPE8, 0, 0};
+}
+
+}  // namespace
+
+// The launcher's decision, a pure function of the arguments, the epilogue, the weight mode and the device's CU count:
+// launch_epi / launch_pipe8 below act on it and q2a_test_gemm_regime reports it. Q2A_REGIME_NONE = no kernel exists.
+q2a_gemm_plan q2a_gemm_plan_of(const q2a_gemm_args & a, int epi, int blk, int cus) {
+    const q2a_gemm_plan none{Q2A_REGIME_NONE, 0, 0};
     const bool big = wide_tiles(a.M, a.N);
     const bool p8 = pipe8_ok(a, blk) && (blk != 256 || a.beta);
+    if (epi == Q2A_EPI_GELU_Q8K) {
+        if (!big || blk != 256) return none;
+        return {p8 ? Q2A_REGIME_PIPE8 : Q2A_REGIME_128x256, 0, 0};
+    }
+    // every configuration sums K in the same order (64-deep K-steps, two 32-deep MFMAs each; Q4_K with the
+    // same block recurrence): a clip's outputs are bit-identical whichever tile regime its batch size selects
+    const bool narrow = !big && narrow_tiles(a.M, a.N) && a.ksplit <= 1 && a.ngroup != 2;
+    const bool h16 = epi == Q2A_EPI_QKV || epi == Q2A_EPI_RESID || epi == Q2A_EPI_GELU_H || epi == Q2A_EPI_STORE_F;
+    if (blk == 0 || blk == 256 || (blk == Q2A_BLK_BF16 && h16)) {
+        if (blk == 256 && (!a.beta || !a.gamma)) return none;   // the block recurrence needs beta / gamma
+        if (p8) return pipe8_plan(a, epi, blk, cus);
+        if (narrow) return {Q2A_REGIME_NARROW, 0, 0};
+        return {big ? (blk == 256 ? Q2A_REGIME_128x256 : Q2A_REGIME_256) : Q2A_REGIME_128, 0, 0};
+    }
+    // the conv GEMMs' exact accumulation: 64x128 tiles in every regime (one K order, batch invariant)
+    if (blk == Q2A_BLK_EXACT && (epi == Q2A_EPI_GELU_H || epi == Q2A_EPI_CONV2 || epi == Q2A_EPI_STORE_F))
+        return {Q2A_REGIME_FIXED, 0, 0};
+    if (blk == 32) {
+        if (narrow) return {Q2A_REGIME_NARROW, 0, 0};
+        return {big ? Q2A_REGIME_128x256 : Q2A_REGIME_128, 0, 0};
+    }
+    // Q6_K: one tile configuration whatever the batch (one K order and one block sum: batch invariant)
+    if (blk == Q2A_BLK_Q6K && (h16 || epi == Q2A_EPI_PRE_H)) {
+        if (!a.sc || !a.dx || !a.dy || a.K % 256 != 0) return none;
+        return {Q2A_REGIME_FIXED, 0, 0};
+    }
+    return none;
+}
+
+namespace {
+
+template <int EPI, int BLK>
+hipError_t launch_pipe8(const q2a_gemm_args & a, const q2a_gemm_plan & pl, hipStream_t s) {
+    if constexpr ((EPI == Q2A_EPI_PRE_H || EPI == Q2A_EPI_QKV) && BLK == 256) {
+        if (pl.regime == Q2A_REGIME_PIPE8_PERSISTENT) {
+            hipLaunchKernelGGL((k_gemm<256, 256, 2, 4, EPI, BLK, 2>), dim3(pl.grid), dim3(512), 0, s, a);
+            return hipGetLastError();
+        }
+    }
+    constexpr bool TAILABLE = (EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_PRE_H || EPI == Q2A_EPI_GELU_H);
+    if constexpr (TAILABLE) {
+        if (pl.regime == Q2A_REGIME_PIPE8_TAIL) {
+            q2a_gemm_args h = a;
+            h.M = pl.m_main * 256;
+            const hipError_t err = launch_cfg<256, 256, 2, 4, EPI, BLK, 1>(h, s);
+            if (err != hipSuccess) return err;
+            q2a_gemm_args t = a;
+            t.m_base = pl.m_main * 256;
+            return launch_cfg<128, 128, 2, 2, EPI, BLK>(t, s);
+        }
+    }
+    return launch_cfg<256, 256, 2, 4, EPI, BLK, 1>(a, s);
+}
+
+template <int EPI>
+hipError_t launch_epi(const q2a_gemm_args & a, int blk, hipStream_t s) {
+    const q2a_gemm_plan pl = q2a_gemm_plan_of(a, EPI, blk, cu_count());
+    const int rg = pl.regime;
+    if (rg == Q2A_REGIME_NONE) return hipErrorInvalidValue;
+    const bool p8 = rg == Q2A_REGIME_PIPE8 || rg == Q2A_REGIME_PIPE8_PERSISTENT || rg == Q2A_REGIME_PIPE8_TAIL;
+    const bool narrow = rg == Q2A_REGIME_NARROW, small = rg == Q2A_REGIME_128;
     if constexpr (EPI == Q2A_EPI_GELU_Q8K) {
-        if (!big || blk != 256) return hipErrorInvalidValue;
         if (p8) return launch_cfg<256, 256, 2, 4, EPI, 256, 1>(a, s);
         return launch_cfg<128, 256, 2, 4, EPI, 256>(a, s);
     } else {
-        // every configuration sums K in the same order (64-deep K-steps, two 32-deep MFMAs each; Q4_K with the
-        // same block recurrence): a clip's outputs are bit-identical whichever tile regime its batch size selects
-        const bool narrow = !big && narrow_tiles(a.M, a.N) && a.ksplit <= 1 && a.ngroup != 2;
         if (blk == 0) {
-            if (p8) return launch_pipe8<EPI, 0>(a, s);
+            if (p8) return launch_pipe8<EPI, 0>(a, pl, s);
             if (narrow) return launch_cfg<64, 128, 4, 2, EPI, 0>(a, s);
-            return big ? launch_cfg<256, 256, 2, 4, EPI, 0>(a, s) : launch_cfg<128, 128, 2, 2, EPI, 0>(a, s);
+            return small ? launch_cfg<128, 128, 2, 2, EPI, 0>(a, s) : launch_cfg<256, 256, 2, 4, EPI, 0>(a, s);
         }
         if constexpr (EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_CONV2 || EPI == Q2A_EPI_STORE_F) {
-            // the conv GEMMs' exact accumulation: 64x128 tiles in every regime (one K order, batch invariant)
             if (blk == Q2A_BLK_EXACT) return launch_cfg<64, 128, 2, 2, EPI, Q2A_BLK_EXACT>(a, s);
         }
         if (blk == 256) {
-            if (!a.beta || !a.gamma) return hipErrorInvalidValue;   // the block recurrence needs beta / gamma
-            if (p8) return launch_pipe8<EPI, 256>(a, s);
+            if (p8) return launch_pipe8<EPI, 256>(a, pl, s);
             if (narrow) return launch_cfg<64, 128, 4, 2, EPI, 256>(a, s);
-            return big ? launch_cfg<128, 256, 2, 4, EPI, 256>(a, s) : launch_cfg<128, 128, 2, 2, EPI, 256>(a, s);
+            return small ? launch_cfg<128, 128, 2, 2, EPI, 256>(a, s) : launch_cfg<128, 256, 2, 4, EPI, 256>(a, s);
         }
         if (blk == 32) {
             if (narrow) return launch_cfg<64, 128, 4, 2, EPI, 32>(a, s);
-            return big ? launch_cfg<128, 256, 2, 4, EPI, 32>(a, s) : launch_cfg<128, 128, 2, 2, EPI, 32>(a, s);
+            return small ? launch_cfg<128, 128, 2, 2, EPI, 32>(a, s) : launch_cfg<128, 256, 2, 4, EPI, 32>(a, s);
         }
         if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_PRE_H ||
                       EPI == Q2A_EPI_STORE_F) {
-            // Q6_K: one tile configuration whatever the batch (one K order and one block sum: batch invariant)
-            if (blk == Q2A_BLK_Q6K) {
-                if (!a.sc || !a.dx || !a.dy || a.K % 256 != 0) return hipErrorInvalidValue;
-                return launch_cfg<128, 128, 2, 2, EPI, Q2A_BLK_Q6K>(a, s);
-            }
+            if (blk == Q2A_BLK_Q6K) return launch_cfg<128, 128, 2, 2, EPI, Q2A_BLK_Q6K>(a, s);
         }
         if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_STORE_F) {
             if (blk == Q2A_BLK_BF16) {
                 constexpr int B16 = Q2A_BLK_BF16;
-                if (p8) return launch_pipe8<EPI, B16>(a, s);
+                if (p8) return launch_pipe8<EPI, B16>(a, pl, s);
                 if (narrow) return launch_cfg<64, 128, 4, 2, EPI, B16>(a, s);
-                return big ? launch_cfg<256, 256, 2, 4, EPI, B16>(a, s) : launch_cfg<128, 128, 2, 2, EPI, B16>(a, s);
+                return small ? launch_cfg<128, 128, 2, 2, EPI, B16>(a, s) : launch_cfg<256, 256, 2, 4, EPI, B16>(a, s);
             }
         }
         return hipErrorInvalidValue;
@@ -2001,17 +2044,29 @@ int q2a_gemm_kq_ksplit(int M, int N, int K, int blk) {
     return 0;
 }
 
-hipError_t q2a_launch_gemm(const q2a_gemm_args & a_in, int epi, int blk, hipStream_t s) {
-    q2a_gemm_args a = a_in;
+// the launcher's own argument checks and its split decision, applied to a copy of the caller's arguments
+static bool launch_args(q2a_gemm_args & a, int epi, int blk) {
     a.m_base = 0;
-    if (a.ngroup == 2 && (epi != Q2A_EPI_STORE_F || (blk != 0 && blk != 256) || wide_tiles(a.M, a.N))) return hipErrorInvalidValue;
-    if (a.ngroup == 2 && blk == 256 && (!a.dx2 || !a.beta2 || !a.gamma2 || !a.wext2)) return hipErrorInvalidValue;
+    if (a.ngroup == 2 && (epi != Q2A_EPI_STORE_F || (blk != 0 && blk != 256) || wide_tiles(a.M, a.N))) return false;
+    if (a.ngroup == 2 && blk == 256 && (!a.dx2 || !a.beta2 || !a.gamma2 || !a.wext2)) return false;
     if (!(epi == Q2A_EPI_RESID || (epi == Q2A_EPI_STORE_F && a.split_store)) || !a.part || a.ldo != a.N || a.ngroup == 2)
         a.ksplit = 0;
     else if (blk == 256 || blk == 32) a.ksplit = a.split_kq ? q2a_gemm_kq_ksplit(a.M, a.N, a.K, blk) : 0;
     else a.ksplit = q2a_gemm_resid_ksplit(a.M, a.N, a.K, blk);
-    if (a.N % 128 != 0 || a.K % BK != 0 || a.M <= 0) return hipErrorInvalidValue;
-    if (blk > 1 && (a.K % blk != 0)) return hipErrorInvalidValue;
+    if (a.N % 128 != 0 || a.K % BK != 0 || a.M <= 0) return false;
+    if (blk > 1 && (a.K % blk != 0)) return false;
+    return true;
+}
+
+q2a_gemm_plan q2a_gemm_plan_for(const q2a_gemm_args & a_in, int epi, int blk) {
+    q2a_gemm_args a = a_in;
+    if (!launch_args(a, epi, blk)) return {Q2A_REGIME_NONE, 0, 0};
+    return q2a_gemm_plan_of(a, epi, blk, cu_count());
+}
+
+hipError_t q2a_launch_gemm(const q2a_gemm_args & a_in, int epi, int blk, hipStream_t s) {
+    q2a_gemm_args a = a_in;
+    if (!launch_args(a, epi, blk)) return hipErrorInvalidValue;
     switch (epi) {
         case Q2A_EPI_QKV: return launch_epi<Q2A_EPI_QKV>(a, blk, s);
         case Q2A_EPI_RESID: return launch_epi<Q2A_EPI_RESID>(a, blk, s);

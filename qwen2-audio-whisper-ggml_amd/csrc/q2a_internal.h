@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "q2a_encoder.h"   // Q2A_REGIME_*
+
 typedef _Float16 q2a_half;
 
 // sets the calling thread's q2a_last_error() text (defined with the engine; used by q2a_group.cpp)
@@ -142,6 +144,16 @@ int q2a_cu_count();
 // true when the launcher will use the 8-phase 256x256 kernel for these arguments (its Q4_K flavour fuses
 // Q2A_EPI_GELU_Q8K efficiently)
 bool q2a_gemm_pipe8(const q2a_gemm_args & a, int blk);
+// The launcher's whole decision for one GEMM (a as q2a_launch_gemm sees it after its own checks: m_base 0, ksplit
+// resolved): the tile regime (Q2A_REGIME_*, include/q2a_encoder.h), and for the persistent kernel its grid, for the
+// two-launch tail the 256-row tiles of the main launch. A pure function of its arguments — cus is the device's CU
+// count — that the launcher acts on and q2a_test_gemm_regime reports.
+struct q2a_gemm_plan {
+    int regime, grid, m_main;
+};
+q2a_gemm_plan q2a_gemm_plan_of(const q2a_gemm_args & a, int epi, int blk, int cus);
+// the same for the arguments as a caller of q2a_launch_gemm holds them (its checks and split decision applied first)
+q2a_gemm_plan q2a_gemm_plan_for(const q2a_gemm_args & a, int epi, int blk);
 
 struct q2a_attn_args {
     const q2a_half *qh, *ql, *kh, *kl, *vt;

@@ -27,7 +27,7 @@ EXPORTS = (
     "q2a_valid_lengths", "q2a_encode_device_padded", "q2a_encode_host_padded", "q2a_test_attention_len",
     "q2a_test_block_len",
     "q2a_varlen_rows", "q2a_encode_device_varlen", "q2a_encode_host_varlen", "q2a_test_attention_varlen",
-    "q2a_test_block_varlen", "q2a_test_operand",
+    "q2a_test_block_varlen", "q2a_test_operand", "q2a_test_gemm_epi", "q2a_test_gemm_regime",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -48,6 +48,11 @@ class Info(C.Structure):
 
 # producers of q2a_test_operand (include/q2a_encoder.h)
 OPERAND_LN, OPERAND_QUANT_F32, OPERAND_QUANT_H16, OPERAND_GELU_Q8K = 0, 1, 2, 3
+
+# epilogues of q2a_test_gemm_epi and the launcher's tile regimes (include/q2a_encoder.h)
+EPI_QKV, EPI_RESID, EPI_GELU_H, EPI_GELU_Q8K, EPI_PRE_H = 0, 1, 2, 6, 7
+(REGIME_NARROW, REGIME_128, REGIME_128x256, REGIME_256, REGIME_PIPE8, REGIME_PIPE8_PERSISTENT, REGIME_PIPE8_TAIL,
+ REGIME_FIXED) = range(8)
 
 # activation contracts (include/q2a_encoder.h)
 ACT_REFERENCE = 0
@@ -127,6 +132,9 @@ def lib() -> C.CDLL:
                 getattr(L, name).argtypes = at
         if hasattr(L, "q2a_test_operand"):   # (optional like the hooks above)
             L.q2a_test_operand.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
+        if hasattr(L, "q2a_test_gemm_epi"):   # (optional like the hooks above)
+            L.q2a_test_gemm_epi.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp), C.c_int, vp]
+            L.q2a_test_gemm_regime.argtypes = [vp, C.c_int, C.c_int, C.c_int]
         if hasattr(L, "q2a_varlen_rows"):
             L.q2a_varlen_rows.restype = C.c_int64
             L.q2a_varlen_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
@@ -313,6 +321,20 @@ class Engine:
         p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
         _check(lib().q2a_test_operand(self.h, producer, mode, p(x_ptr), M, K, p(g_ptr), p(b_ptr), p(out_ptr), p(dy_ptr),
                                       p(aext_ptr), M if ld is None else ld, p(stream)))
+
+    def test_gemm_epi(self, layer, which, epi, x_ptr, M, out_ptrs, ld=0, stream=None):
+        """q2a_test_gemm_epi: the block's GEMM `which` with its fused epilogue EPI_* on caller rows, stored straight into
+        the caller's buffers out_ptrs (their order: include/q2a_encoder.h)."""
+        arr = (C.c_void_p * 6)(*([C.c_void_p(p) if p else None for p in out_ptrs] + [None] * (6 - len(out_ptrs))))
+        _check(lib().q2a_test_gemm_epi(self.h, layer, which, epi, C.c_void_p(x_ptr), M, arr, ld,
+                                       C.c_void_p(stream) if stream else None))
+
+    def test_gemm_regime(self, which, epi, M) -> int:
+        """q2a_test_gemm_regime: the REGIME_* the launcher picks for that GEMM at M rows on this device."""
+        rg = lib().q2a_test_gemm_regime(self.h, which, epi, M)
+        if rg < 0:
+            _check(rg)
+        return rg
 
     def test_attention(self, q_ptr, k_ptr, v_ptr, n_clips, out_ptr, stream=None):
         _check(lib().q2a_test_attention(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,

@@ -288,8 +288,9 @@ def test_block_taps_are_the_hooks_operands(eng, zero_o_model, make_clip, wt, mod
     """The encoder block reaches the LayerNorm producers the way q2a_test_operand does: taps 0 and 2 of block 0 (the
     QKV and fc1 operands as the MFMA consumed them) equal the hook's LayerNorm operand of the same rows under the
     layer's own gains, bit for bit. Tap 2 is predictable because this model's out_proj is zero: x1 = x. (Taps 1 and 3
-    follow the attention and the fc1 GEMM, whose outputs no entry point returns; tap 3 is checked against the oracle in
-    the x >= 10 tests below.)"""
+    follow the attention and the fc1 GEMM: the GEMM outputs themselves — Q, K, V hi / lo, the residual, fc1's fp16 and
+    Q8_K images — are returned by q2a_test_gemm_epi and pinned in tests/test_gpu_gemm_epilogues.py; tap 3 is checked
+    against the oracle in the x >= 10 tests below.)"""
     import q2a
     path = zero_o_model(wt)
     mf = ggmlfile.read(path)

@@ -402,8 +402,9 @@ def test_linear_big_tiles_match_oracle(engines, make_model, wt, which):
 def test_linear_full_size_bench_shape_matches_oracle(engines, make_model, wt, which):
     """The bench's GEMM shapes exactly: full-size weights (K = 1 280 or 5 120: five / twenty Q4_K blocks, so the
     block recurrence runs between blocks, which the tiny model's single block never does), M = 96 000 rows in ONE
-    launch (the 8-phase 256x256 grid, and for fc2 its partial last round on 128x128 tiles). Checked against the C
-    oracle on 384 sampled rows, including the last rows of the grid's main rounds and of the tail."""
+    launch: the single 8-phase 256x256 grid. (Q2A_EPI_STORE_F never takes the two-launch partial-round tail — that is
+    for RESID, PRE_H and GELU_H, run by tests/test_gpu_gemm_epilogues.py::test_partial_round_tail.) Checked against the
+    C oracle on 384 sampled rows, including the rows around 91 648, where fc2's RESID launch of this M has its seam on 256 CUs."""
     e = engines("full", wt)
     mf = ggmlfile.read(make_model("full", wt))
     D, F = 1280, 5120
