@@ -193,6 +193,44 @@ int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int3
  * mel_cap floats) and *n_len. Runs the same kernels as the encoder on the engine's device. */
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len);
 
+/* ---- encode from log-mel features instead of PCM ------------------------------------------------------------
+ * The reference's second way in: whisper_set_mel + whisper_encode (include/qwen2-whisper.h:228-250,
+ * src/qwen2-whisper.cpp:2264-2286, 3281-3308). The caller's mel is f32, already normalised: the values
+ * q2a_pcm_to_mel / whisper_pcm_to_mel return and transformers' WhisperFeatureExtractor produces as input_features
+ * (clamp to max - 8, then (x + 4) / 4). Clip c is [n_mels][ld] with n_len[c] <= ld frames; its encoder window is
+ * frames seek[c] .. seek[c] + 2 n_audio_ctx - 1, and window frames at or past n_len[c] are ZEROS (the reference clears
+ * the window and copies what exists) — not the value the PCM path's padding takes. Nothing at or past frame n_len[c] of
+ * a row is read. There is no 1 s rule at this level (whisper_encode has none): every clip is encoded, Q2A_CLIP_ENCODED.
+ * One kernel writes the conv1 operand from the caller's array (no mel scratch, no clip maximum); everything behind it
+ * is the PCM entry points' path, so mel = q2a_pcm_to_mel(pcm), seek = offset_ms / 10 returns their bytes.
+ *
+ * q2a_mel_valid_lengths: q2a_valid_lengths for n_len frames encoded from frame seek (host arithmetic, also exported
+ * from libq2a_host.so):
+ *   frames  = clamp(n_len - seek, 1, 2 * n_audio_ctx);  enc_len = (frames - 1) / 2 + 1;  out_len = enc_len / 2
+ * Either output pointer may be NULL. Q2A_ERR_ARG for n_len < 1, seek < 0 or n_audio_ctx <= 0. */
+enum { Q2A_ENCODE_PLAIN = 0, Q2A_ENCODE_PADDED = 1, Q2A_ENCODE_VARLEN = 2 };
+int q2a_mel_valid_lengths(int n_len, int seek, int n_audio_ctx, int32_t * enc_len, int32_t * out_len);
+
+/* kind         Q2A_ENCODE_PLAIN: q2a_encode_device_ex behind the mel (all n_audio_ctx keys; key_len and out_len are
+ *              not read or written); Q2A_ENCODE_PADDED / Q2A_ENCODE_VARLEN: q2a_encode_device_padded / _varlen behind
+ *              it (Q2A_ERR_UNSUPPORTED for Q2A_ACT_BF16, nothing written)
+ * mel_dev      device f32, clip c at mel_dev + c * clip_stride, [n_mels][ld]; ld, seek and the pointer need no
+ *              alignment beyond a float's
+ * clip_stride  floats between clips: >= n_mels * ld, or 0: every clip reads the same array (the windows of one
+ *              recording at different seeks)
+ * n_len        host [n_clips], 1 <= n_len[c] <= ld
+ * seek         host [n_clips], seek[c] >= 0 (at or past n_len[c]: an all-zero window), or NULL: 0 for every clip
+ * key_len      host [n_clips], 1 <= key_len[c] <= n_audio_ctx, or NULL: q2a_mel_valid_lengths' enc_len of each clip
+ * out_dev, out_len, status, stream   as in q2a_encode_device_padded (no clip is skipped)
+ * Every argument is checked before anything is launched (Q2A_ERR_ARG). */
+int q2a_encode_device_mel(q2a_engine * e, int kind, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                          const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                          float * out_dev, int32_t * out_len, int32_t * status, void * stream);
+/* Same with host buffers in and out (synchronous): mel[c] is clip c's [n_mels][n_len[c]] (ld = n_len[c]). Only the
+ * window columns of each row are copied to the device; chunks, overlap and Q2A_CLIP_FAILED as in q2a_encode_host_ex. */
+int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, const int32_t * n_len, const int32_t * seek,
+                        const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status);
+
 /* ---- one process, several GPUs (ncclCommInitAll + a host thread per device) -----------------------
  * Replaces the single-device choice of whisper_backend_init_gpu (qwen2-whisper.cpp:1217-1279) for batches of
  * independent clips, and is what whisper_full_parallel (declared, never defined, include/qwen2-whisper.h:464-469)
@@ -252,6 +290,10 @@ int q2a_test_block_taps(q2a_engine * e, int layer, float * x_dev, int n_clips, v
  * first block's input X [n_clips*T][D] f32 (device) — the reference's embd_conv + pe (qwen2-whisper.cpp:1892-2005). */
 int q2a_test_frontend(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples, int n_clips,
                       float * x_dev, void * stream);
+/* The same from log-mel (q2a_encode_device_mel's mel_dev, clip_stride, ld, n_len, seek and checks): the ingest kernel
+ * in place of the mel kernels, then the same conv launches. */
+int q2a_test_frontend_mel(q2a_engine * e, const float * mel_dev, int64_t clip_stride, int64_t ld, const int32_t * n_len,
+                          const int32_t * seek, int n_clips, float * x_dev, void * stream);
 /* AvgPool1d(2) + final LayerNorm only: X [n_clips*T][D] f32 (device) -> out [n_clips][T/2][D] f32 (device)
  * (qwen2-whisper.cpp:2157-2181). */
 int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * out_dev, void * stream);

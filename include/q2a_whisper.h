@@ -10,6 +10,7 @@
  *                                                 gpu_device and the other visible devices, at most
  *                                                 Q2A_PARALLEL_DEVICES of them, on one replica per device)
  *   whisper_pcm_to_mel / whisper_n_len   :211 / :288
+ *   whisper_set_mel                       :228   (the caller's normalised log-mel becomes the state's input)
  *   whisper_encode                        :245   (encode the stored mel at `offset` frames)
  *   whisper_print_emb_enc                 :527   (first 20 values of embd_enc, " %.3f" each)
  *   whisper_free / whisper_init_state / whisper_free_state, default-params, model-dimension getters, timings.
@@ -128,6 +129,14 @@ void whisper_free_state(struct whisper_state * state);
 int whisper_pcm_to_mel(struct whisper_context * ctx, const float * samples, int n_samples, int n_threads);
 int whisper_pcm_to_mel_with_state(struct whisper_context * ctx, struct whisper_state * state, const float * samples,
                                   int n_samples, int n_threads);
+/* The caller's log-mel [n_mel][n_len] f32, already normalised (what whisper_pcm_to_mel computes), becomes the state's
+ * input and replaces a remembered PCM: whisper_encode(offset) then encodes frames offset .. offset + 2 n_audio_ctx - 1
+ * of it, zeros past n_len, and whisper_full(samples = NULL, n_samples = 0) applies the 1 s rule to n_len and encodes
+ * from frame offset_ms / 10. whisper_n_len returns n_len. -1 (and a log line) when n_mel is not the model's. A later
+ * whisper_pcm_to_mel or whisper_full with samples makes PCM the input again. */
+int whisper_set_mel(struct whisper_context * ctx, const float * data, int n_len, int n_mel);
+int whisper_set_mel_with_state(struct whisper_context * ctx, struct whisper_state * state, const float * data, int n_len,
+                               int n_mel);
 int whisper_encode(struct whisper_context * ctx, int offset, int n_threads);
 int whisper_encode_with_state(struct whisper_context * ctx, struct whisper_state * state, int offset, int n_threads);
 

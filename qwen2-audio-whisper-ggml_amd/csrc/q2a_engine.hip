@@ -1277,14 +1277,29 @@ q2a_mel_args mel_args(const q2a_engine * e, const float * pcm, int64_t stride, c
     return ma;
 }
 
-// mel + conv frontend: PCM -> X [B*T][D] (conv graph qwen2-whisper.cpp:1892-1952 + pe add :2005)
-int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int max_frames, hipStream_t s) {
+// what the front end reads: PCM (pcm [B][stride], the mel kernels), or with `mel` set caller-owned log-mel (clip c:
+// [n_mels][ld] at mel + c * stride, the ingest kernel). The per-clip lengths and seeks are in the call's device rows.
+struct frontend_src {
+    const float * pcm;
+    int64_t stride;             // 0: every clip reads the same PCM / the same mel
+    const float * mel;
+    int64_t ld;
+};
+
+// mel + conv frontend: PCM or log-mel -> X [B*T][D] (conv graph qwen2-whisper.cpp:1892-1952 + pe add :2005); the same
+// conv launches after either mel producer
+int run_frontend(q2a_engine * e, const frontend_src & src, int B, int max_frames, hipStream_t s) {
     const dims & d = e->d;
     const meta_rows dev(e->meta, B);
-    LAUNCH(hipMemsetAsync(dev.clip_max, 0x80, (size_t) B * 4, s));
-    if (int rc = ensure_frange(e, s)) return rc;
-    const q2a_mel_args ma = mel_args(e, pcm, stride, dev, B, max_frames);
-    PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel(ma, s));
+    if (src.mel) {
+        const q2a_mel_ingest_args ia{src.mel, src.stride, src.ld, dev.nsamp, dev.seek, B, d.M, d.TM, e->xc1, e->f32 ? 1 : 0};
+        PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel_ingest(ia, s));
+    } else {
+        LAUNCH(hipMemsetAsync(dev.clip_max, 0x80, (size_t) B * 4, s));
+        if (int rc = ensure_frange(e, s)) return rc;
+        const q2a_mel_args ma = mel_args(e, src.pcm, src.stride, dev, B, max_frames);
+        PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel(ma, s));
+    }
     const int P1 = 3, P2 = e->f32 ? 2 : 1;   // operand parts per mel row / per conv1 output row
     // both convs sum each 64-deep K-step's MFMA partial in f64 (Q2A_BLK_EXACT): within rounding of the exact dot
     // product, where a plain f32 MFMA chain carried twice the reference builds' own conv error
@@ -1320,7 +1335,9 @@ int run_frontend(q2a_engine * e, const float * pcm, int64_t stride, int B, int m
 // the attention, the blocks on all B*T rows) and the variable-length ones (the blocks on the packed valid rows)
 enum encode_kind { ENC_PLAIN, ENC_PADDED, ENC_PACKED };
 
-// the arguments of one encode: B clips in device memory, host arrays of B entries
+// the arguments of one encode: B clips in device memory, host arrays of B entries. The input is PCM, or with `mel`
+// set (q2a_encode_device_mel) log-mel: pcm is then NULL, stride the clip stride of mel, n_samples the clips' n_len and
+// seek their first window frames (NULL: 0); offset_ms and offs are not read
 struct encode_call {
     const float * pcm;
     int64_t stride;             // 0: every clip reads the same PCM
@@ -1332,6 +1349,10 @@ struct encode_call {
     float * out;                // device [B][TO][D]
     int32_t * out_len;          // NULL, or the clips' valid output rows (ENC_PADDED, ENC_PACKED)
     int32_t * status;           // NULL, or Q2A_CLIP_* per clip
+    const float * mel;          // device, clip c: [n_mels][ld] at mel + c * stride
+    int64_t ld;
+    const int32_t * seek;
+    frontend_src src() const { return {pcm, stride, mel, ld}; }
 };
 
 // the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
@@ -1361,13 +1382,19 @@ int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStr
     max_frames = 0;
     const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start : &meta_rows::end;
     return upload_meta(e, B, &meta_rows::nsamp, last, s, [&](const meta_rows & mh) -> int {
+        if (c.mel && c.stride != 0 && c.stride < e->d.M * c.ld) { set_err("clip_stride %lld below n_mels * ld", (long long) c.stride); return Q2A_ERR_ARG; }
         for (int i = 0; i < B; ++i) {
-            const int seek = (c.offs ? c.offs[i] : c.offset_ms) / 10;
+            const int seek = c.mel ? (c.seek ? c.seek[i] : 0) : (c.offs ? c.offs[i] : c.offset_ms) / 10;
             if (seek < 0) { set_err("clip %d: negative offset", i); return Q2A_ERR_ARG; }
             const int n = c.n_samples[i];
-            if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", i, n); return Q2A_ERR_ARG; }
-            const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
-            const bool ok = n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+            bool ok = true;
+            if (c.mel) {   // log-mel input: n is n_len (into the nsamp row); no 1 s rule at this level, every clip is encoded
+                if (n < 1 || n > c.ld) { set_err("clip %d: n_len %d outside 1..ld", i, n); return Q2A_ERR_ARG; }
+            } else {
+                if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", i, n); return Q2A_ERR_ARG; }
+                const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
+                ok = n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+            }
             mh.nsamp[i] = ok ? n : 0;
             mh.seek[i] = seek;
             mh.clip_ok[i] = ok ? 1 : 0;
@@ -1483,7 +1510,7 @@ int lens_supported(const q2a_engine * e, encode_kind kind) {
 int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s) {
     const dims & d = e->d;
     const int B = c.B;
-    if (B <= 0 || !c.pcm || !c.n_samples || !c.out || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (B <= 0 || !(c.pcm || c.mel) || !c.n_samples || !c.out || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     if (c.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
     int rc = lens_supported(e, kind);
     if (rc) return rc;
@@ -1498,7 +1525,7 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
     // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros)
     if (kind != ENC_PACKED || rows.M > 0) {
-        if ((rc = run_frontend(e, c.pcm, c.stride, B, max_frames, s))) return rc;
+        if ((rc = run_frontend(e, c.src(), B, max_frames, s))) return rc;
         if (kind == ENC_PACKED)
             PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, dev.row_start, B, d.T, d.D, rows.r_max, s));
         for (int l = 0; l < d.L; ++l)
@@ -1703,17 +1730,29 @@ int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n
 
 // q2a_encode_host_ex (ENC_PLAIN), q2a_encode_host_padded and q2a_encode_host_varlen (each chunk of clips packed on its
 // own), the latter two with kl (host [n_clips] key lengths, already checked): every clip's output is then copied back
-// (rows past its valid length, and a skipped clip's rows, are zeros)
+// (rows past its valid length, and a skipped clip's rows, are zeros).
+// q2a_encode_host_mel: `mel` set (clip c: [n_mels][n_len[c]] host floats; pcm, n_samples and the offsets are then not
+// read). Only the window columns seek .. min(seek + 2 n_ctx, n_len) - 1 of each row are staged, as clip c of a device
+// array [chunk][n_mels][2 n_ctx] that the encode reads from frame 0.
+struct host_mel {
+    const float * const * mel;
+    const int32_t * n_len;
+    const int32_t * seek;       // NULL: 0
+};
 static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * const * pcm, const int32_t * n_samples,
                             const int32_t * offsets_ms, int n_clips, int offset_ms, float * out_host, int32_t * status,
-                            const int32_t * kl, int32_t * out_len) {
-    if (!e || !pcm || !n_samples || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    for (int c = 0; c < n_clips; ++c)   // (checked before any copy: a negative count would be a huge memcpy)
-        if (n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c])) {
-            set_err("clip %d: bad samples (%d, %p)", c, n_samples[c], (const void *) pcm[c]);
+                            const int32_t * kl, int32_t * out_len, const host_mel * hm = nullptr) {
+    if (!e || !(hm ? hm->mel && hm->n_len : pcm && n_samples) || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    for (int c = 0; c < n_clips; ++c) {   // (checked before any copy: a negative count would be a huge memcpy)
+        const bool bad = hm ? hm->n_len[c] < 1 || !hm->mel[c] || (hm->seek && hm->seek[c] < 0)
+                            : n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c]);
+        if (bad) {
+            if (hm) set_err("clip %d: bad mel (n_len %d, seek %d, %p)", c, hm->n_len[c], hm->seek ? hm->seek[c] : 0, (const void *) hm->mel[c]);
+            else set_err("clip %d: bad samples (%d, %p)", c, n_samples[c], (const void *) pcm[c]);
             if (status) for (int k = 0; k < n_clips; ++k) status[k] = Q2A_CLIP_FAILED;
             return Q2A_ERR_ARG;
         }
+    }
     HIP_TRY(hipSetDevice(e->device));
     // Chunks of clips through two staging sets: chunk k's host->pinned copy and H2D (copy stream) run while chunk k-1
     // encodes (compute stream), and chunk k-1's D2H + pinned->host copy while chunk k encodes. One chunk below 32
@@ -1723,8 +1762,11 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
     const int nchunk = n_clips < 32 ? 1 : std::max(2, (n_clips + 63) / 64);
     const int C = (n_clips + nchunk - 1) / nchunk;
     int64_t maxn = 1;
-    for (int c = 0; c < n_clips; ++c) maxn = std::max<int64_t>(maxn, n_samples[c]);
+    for (int c = 0; !hm && c < n_clips; ++c) maxn = std::max<int64_t>(maxn, n_samples[c]);
     maxn = (maxn + 63) & ~int64_t(63);
+    const int M = e->d.M, TM = e->d.TM;
+    if (hm) maxn = (int64_t) M * TM;   // one staged window per clip
+    std::vector<int32_t> win_len, win_seek;   // the staged windows of a chunk as the encode sees them
     if (int rc = ensure_host_bufs(e, C, maxn)) return rc;
     const size_t per_out = (size_t) e->d.TO * e->d.D;
     // st: what encode reported per clip; pub: what the caller gets — a clip's status is published only once its
@@ -1749,8 +1791,17 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
         q2a_engine::host_buf & b = e->hb[k & 1];
         // staging set k&1 was last used by chunk k-2: its H2D must have left pin_in, its D2H must have left d_out
         if (hipEventSynchronize(b.h2d) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        for (int c = 0; c < n; ++c) {
+        for (int c = 0; !hm && c < n; ++c) {
             memcpy(b.pin_in + c * maxn, pcm[c0 + c], (size_t) n_samples[c0 + c] * 4);
+        }
+        if (hm) { win_len.assign(n, 1); win_seek.assign(n, 0); }
+        for (int c = 0; hm && c < n; ++c) {
+            const int64_t n_len = hm->n_len[c0 + c], seek = hm->seek ? hm->seek[c0 + c] : 0;
+            const int w = (int) std::max<int64_t>(0, std::min<int64_t>(n_len - seek, TM));
+            // a window behind the last frame has no columns: one (unread) frame at seek 1 makes it all zeros
+            if (w > 0) win_len[c] = w; else win_seek[c] = 1;
+            for (int j = 0; j < M && w > 0; ++j)
+                memcpy(b.pin_in + c * maxn + (int64_t) j * TM, hm->mel[c0 + c] + j * n_len + seek, (size_t) w * 4);
         }
         if (hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||   // chunk k-2's encode no longer reads d_in
             hipMemcpyAsync(b.d_in, b.pin_in, (size_t) n * maxn * 4, hipMemcpyHostToDevice, cs) != hipSuccess ||
@@ -1760,8 +1811,12 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
             rc = Q2A_ERR_HIP;
             break;
         }
-        rc = encode(e, kind, {b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr,
-                              kl ? kl + c0 : nullptr, b.d_out, out_len ? out_len + c0 : nullptr, st.data() + c0}, s);
+        if (hm)
+            rc = encode(e, kind, {nullptr, maxn, win_len.data(), n, 0, nullptr, kl ? kl + c0 : nullptr, b.d_out,
+                                  out_len ? out_len + c0 : nullptr, st.data() + c0, b.d_in, TM, win_seek.data()}, s);
+        else
+            rc = encode(e, kind, {b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr,
+                                  kl ? kl + c0 : nullptr, b.d_out, out_len ? out_len + c0 : nullptr, st.data() + c0}, s);
         if (rc) break;
         if (hipEventRecord(b.comp, s) != hipSuccess || hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||
             hipMemcpyAsync(b.pin_out, b.d_out, (size_t) n * per_out * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
@@ -1823,6 +1878,48 @@ int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int3
     std::vector<int32_t> kl;
     if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
     return encode_host_impl(e, ENC_PACKED, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
+}
+
+// the prologue of the log-mel entry points: the kind, the activation contract, and for the key-length kinds the key
+// lengths into kl (the caller's, checked, or q2a_mel_valid_lengths' enc_len)
+static int mel_prologue(q2a_engine * e, int kind, const int32_t * n_len, const int32_t * seek, const int32_t * key_len,
+                        int n_clips, encode_kind & ek, std::vector<int32_t> & kl) {
+    if (!e || !n_len || n_clips <= 0 || kind < Q2A_ENCODE_PLAIN || kind > Q2A_ENCODE_VARLEN) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    ek = kind == Q2A_ENCODE_PLAIN ? ENC_PLAIN : kind == Q2A_ENCODE_PADDED ? ENC_PADDED : ENC_PACKED;
+    if (int rc = lens_supported(e, ek)) return rc;
+    if (ek == ENC_PLAIN) return Q2A_OK;
+    kl.resize(n_clips);
+    for (int c = 0; c < n_clips; ++c) {
+        if (key_len) {
+            kl[c] = key_len[c];
+            if (kl[c] < 1 || kl[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, kl[c], e->d.T); return Q2A_ERR_ARG; }
+        } else if (q2a_mel_valid_lengths(n_len[c], seek ? seek[c] : 0, e->d.T, &kl[c], nullptr) != Q2A_OK) {
+            set_err("clip %d: bad n_len %d or seek", c, n_len[c]);
+            return Q2A_ERR_ARG;
+        }
+    }
+    return Q2A_OK;
+}
+
+int q2a_encode_device_mel(q2a_engine * e, int kind, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                          const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                          float * out_dev, int32_t * out_len, int32_t * status, void * stream) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, kind, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    return encode(e, ek, {nullptr, clip_stride, n_len, n_clips, 0, nullptr, ek == ENC_PLAIN ? nullptr : kl.data(), out_dev,
+                          out_len, status, mel_dev, ld, seek}, call_stream(stream));
+}
+
+int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, const int32_t * n_len, const int32_t * seek,
+                        const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, kind, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    const host_mel hm{mel, n_len, seek};
+    return encode_host_impl(e, ek, nullptr, nullptr, nullptr, n_clips, 0, out_host, status, ek == ENC_PLAIN ? nullptr : kl.data(),
+                            out_len, &hm);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -2059,23 +2156,35 @@ int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void 
     return rc;
 }
 
-int q2a_test_frontend(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples, int n_clips,
-                      float * x_dev, void * stream) {
-    if (!e || !pcm_dev || !n_samples || !x_dev || n_clips <= 0) return Q2A_ERR_ARG;
+// the front end of the clips `c` describes (plain metadata, no status) -> x_dev [B*T][D]
+static int test_frontend(q2a_engine * e, const encode_call & c, float * x_dev, void * stream) {
+    if (!e || !(c.pcm || c.mel) || !c.n_samples || !x_dev || c.B <= 0) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
-    int rc = reserve(e, n_clips);
+    int rc = reserve(e, c.B);
     if (rc) return rc;
     int max_frames = 0;
     block_rows rows;
-    encode_call c{};   // no offsets, no status
-    c.pcm = pcm_dev; c.stride = pcm_stride; c.n_samples = n_samples; c.B = n_clips;
     rc = prepare_meta(e, ENC_PLAIN, c, s, max_frames, rows);
     if (rc) return rc;
-    rc = run_frontend(e, pcm_dev, pcm_stride, n_clips, max_frames, s);
+    rc = run_frontend(e, c.src(), c.B, max_frames, s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x_dev, e->X, (size_t) n_clips * e->d.T * e->d.D * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(x_dev, e->X, (size_t) c.B * e->d.T * e->d.D * 4, hipMemcpyDeviceToDevice, s));
     return Q2A_OK;
+}
+
+int q2a_test_frontend(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples, int n_clips,
+                      float * x_dev, void * stream) {
+    encode_call c{};   // no offsets
+    c.pcm = pcm_dev; c.stride = pcm_stride; c.n_samples = n_samples; c.B = n_clips;
+    return test_frontend(e, c, x_dev, stream);
+}
+
+int q2a_test_frontend_mel(q2a_engine * e, const float * mel_dev, int64_t clip_stride, int64_t ld, const int32_t * n_len,
+                          const int32_t * seek, int n_clips, float * x_dev, void * stream) {
+    encode_call c{};
+    c.stride = clip_stride; c.n_samples = n_len; c.B = n_clips; c.mel = mel_dev; c.ld = ld; c.seek = seek;
+    return test_frontend(e, c, x_dev, stream);
 }
 
 int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * out_dev, void * stream) {

@@ -196,6 +196,67 @@ __global__ __launch_bounds__(256) void k_mel_norm(const q2a_mel_args p) {
     }
 }
 
+// The same operand rows from caller-owned log-mel (q2a_mel_ingest_args): the values arrive clamped and normalised, so
+// only the window cut, the transpose and the split remain. Window frame t of clip c is frame seek[c] + t of its
+// [n_mel][ld] array, zeros from frame n_len[c] on (the reference clears the window and copies [i0, i1),
+// qwen2-whisper.cpp:2264-2286); nothing at or past frame n_len[c] of a row is read. One workgroup per 64 frames of a
+// clip: a wave reads 64 consecutive frames of one mel row (256 B; ld and seek need no alignment), the tile is stored
+// transposed [frame][mel] (row stride 130 floats: the 2-way ds_write_b32 conflict costs nothing, the pair reads are
+// conflict-free ds_read_b64), and a lane writes two neighbouring mel bins of each part as one 4-byte store.
+// The split is k_mel_norm's, written out again here: that kernel keeps its instructions.
+struct mel_parts { _Float16 h, m, l; };
+__device__ __forceinline__ mel_parts mel_split(float v, int xc_f32) {
+    const _Float16 h = (_Float16) v;
+    const float r = v - (float) h;             // exact (|r| <= ulp_fp16(v) / 2)
+    const _Float16 m = (_Float16) r;
+    return {h, m, xc_f32 ? h : (_Float16) (r - (float) m)};
+}
+
+__global__ __launch_bounds__(256) void k_mel_ingest(const q2a_mel_ingest_args p) {
+    __shared__ __attribute__((aligned(8))) float tile[64][130];
+    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+    const int c = blockIdx.y, t0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nm = p.n_mel;
+    const int64_t n_len = p.n_len[c], frame0 = (int64_t) p.seek[c] + t0, frame = frame0 + lane;
+    const bool live = frame < n_len;
+    // eight rows per wave and pass, their loads issued together at clamped (always readable: n_len >= 1) addresses and
+    // then selected: a load under the range branch waited alone, one serial round trip per row. A tile that lies
+    // behind the clip's last frame (most tiles of a short clip) loads nothing.
+    const float * src = p.mel + (int64_t) c * p.clip_stride + min(frame, n_len - 1);
+    for (int j0 = w; j0 < nm; j0 += 32) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = 0.f;
+        if (frame0 < n_len) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = src[(int64_t) min(j0 + 4 * u, nm - 1) * p.ld];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (j0 + 4 * u < nm) tile[lane][j0 + 4 * u] = live ? v[u] : 0.f;
+    }
+    if ((nm & 1) && w == 0) tile[lane][nm] = 0.f;   // the pair partner of the last bin
+    __syncthreads();
+    const int np = (nm + 1) / 2;
+    q2a_half * xc = p.xc1 + (int64_t) c * (p.n_frames_win + 2) * 3 * nm;
+    for (int e = threadIdx.x; e < np * 64; e += 256) {
+        const int tt = e / np, j = 2 * (e % np);
+        if (t0 + tt >= p.n_frames_win) continue;
+        const float2 v = *(const float2 *) &tile[tt][j];
+        const mel_parts a = mel_split(v.x, p.xc_f32), b = mel_split(v.y, p.xc_f32);
+        q2a_half * row = xc + (int64_t) (t0 + tt + 1) * 3 * nm;
+        if (nm & 1) {   // rows of an odd length are not 4-byte aligned
+            row[j] = a.h; row[nm + j] = a.m; row[2 * nm + j] = a.l;
+            if (j + 1 < nm) { row[j + 1] = b.h; row[nm + j + 1] = b.m; row[2 * nm + j + 1] = b.l; }
+        } else {
+            *(h2_t *) (row + j) = h2_t{a.h, b.h};
+            *(h2_t *) (row + nm + j) = h2_t{a.m, b.m};
+            *(h2_t *) (row + 2 * nm + j) = h2_t{a.l, b.l};
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LayerNorm (ggml_compute_forward_norm_f32 ggml.c:11941-11990: double sums, eps 1e-5) + affine (MUL, ADD),
 // fused with the conversion ggml applies to the next MUL_MAT's src1 (ggml.c:12462-12475):
@@ -649,6 +710,12 @@ hipError_t q2a_launch_mel(const q2a_mel_args & a, hipStream_t s) {
     if (a.n_bins > 208 || a.n_mel > 128 * 4) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_mel_frames, dim3((a.max_frames + 3) / 4, a.n_clips), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_mel_norm, dim3((a.n_frames_win + 63) / 64, a.n_clips), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s) {
+    if (a.n_mel < 1 || a.n_mel > 128 || a.n_clips < 1 || a.n_frames_win < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mel_ingest, dim3((a.n_frames_win + 63) / 64, a.n_clips), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -118,6 +118,17 @@ extern "C" int q2a_valid_lengths(int n_samples, int offset_ms, int n_audio_ctx, 
     return Q2A_OK;
 }
 
+// the same for log-mel input of n_len frames encoded from frame `seek` (include/q2a_encoder.h)
+extern "C" int q2a_mel_valid_lengths(int n_len, int seek, int n_audio_ctx, int32_t * enc_len, int32_t * out_len) {
+    if (n_len < 1 || seek < 0 || n_audio_ctx <= 0) return Q2A_ERR_ARG;
+    const int64_t left = (int64_t) n_len - seek;
+    const int frames = (int) std::min<int64_t>(std::max<int64_t>(left, 1), 2 * (int64_t) n_audio_ctx);
+    const int el = (frames - 1) / 2 + 1;
+    if (enc_len) *enc_len = el;
+    if (out_len) *out_len = el / 2;
+    return Q2A_OK;
+}
+
 // the packed layout of the variable-length encode (include/q2a_encoder.h); here for the same reason
 extern "C" int64_t q2a_varlen_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * row_start) {
     if (!key_len || !row_start || n_clips <= 0 || n_audio_ctx <= 0) return Q2A_ERR_ARG;

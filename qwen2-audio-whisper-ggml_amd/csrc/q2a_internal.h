@@ -209,6 +209,23 @@ struct q2a_mel_args {
 hipError_t q2a_launch_mel(const q2a_mel_args & a, hipStream_t s);
 hipError_t q2a_launch_filter_ranges(const float * filters, int n_mel, int n_bins, int2 * out, hipStream_t s);
 
+// The conv1 operand from caller-owned log-mel (whisper_set_mel semantics, qwen2-whisper.cpp:2264-2286) instead of PCM:
+// the values are already clamped and normalised, so the launch only cuts each clip's window, transposes it and writes
+// the same three fp16 parts as q2a_launch_mel. No scratch, no clip maximum.
+struct q2a_mel_ingest_args {
+    const float * mel;          // clip c: [n_mel][ld] f32 at mel + c * clip_stride (clip_stride 0: one recording)
+    int64_t clip_stride, ld;    // in floats; neither needs any alignment
+    const int32_t * n_len;      // [clips] (device) frames of clip c, 1 <= n_len[c] <= ld; nothing at or past frame
+                                //   n_len[c] of a row is read
+    const int32_t * seek;       // [clips] (device) first frame of the window, >= 0; window frames >= n_len[c] are zeros
+    int n_clips;
+    int n_mel;                  // <= 128
+    int n_frames_win;           // 2*n_ctx = 3000
+    q2a_half * xc1;             // as q2a_mel_args.xc1: rows 1 .. n_frames_win of each clip are written, 0 / last left alone
+    int xc_f32;
+};
+hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s);
+
 // LayerNorm over rows of X [M][D] (ggml_norm + mul + add, eps 1e-5), output by mode:
 //   0: fp16 [M][D]                     (F16 weights)
 //   1: Q8_K as fp16 codes + dy[M][D/256] + aext (Q4_K weights)

@@ -19,7 +19,8 @@
 struct whisper_state {
     q2a_engine * eng = nullptr;
     std::vector<float> pcm;       // last input (whisper_encode re-encodes it at a new offset)
-    std::vector<float> mel;       // [n_mel][n_len] of the last whisper_pcm_to_mel
+    std::vector<float> mel;       // [n_mel][n_len] of the last whisper_pcm_to_mel / whisper_set_mel
+    bool mel_input = false;       // the last input was whisper_set_mel: encodes read `mel`, not `pcm`
     int n_len = 0;                // frames in `mel`
     int n_len_org = 0;            // mel.n_len_org: frames that carry audio (qwen2-whisper.cpp:2613)
     std::vector<float> embd;      // [n_out][n_state]
@@ -99,6 +100,22 @@ int encode_window(whisper_context * ctx, whisper_state * st, const float * pcm, 
         st->t_encode_us += (double) (now_us() - t0);
         st->n_encode++;
     }
+    return 0;
+}
+
+// one 30 s window of the state's own mel (whisper_set_mel) from frame `seek`: zeros past n_len, no length rule
+// (whisper_encode_qwen2_internal, qwen2-whisper.cpp:2264-2286)
+int encode_mel_window(whisper_context * ctx, whisper_state * st, int seek) {
+    const float * mel = st->mel.data();
+    const int32_t n_len = st->n_len, sk = seek;
+    int32_t status = Q2A_CLIP_FAILED;
+    const int64_t t0 = now_us();
+    st->embd.resize((size_t) ctx->info.n_out * ctx->info.n_audio_state);
+    const int rc = q2a_encode_host_mel(st->eng, Q2A_ENCODE_PLAIN, &mel, &n_len, &sk, nullptr, 1, st->embd.data(), nullptr, &status);
+    if (rc != Q2A_OK) { wlog(GGML_LOG_LEVEL_ERROR, "whisper_encode: failed to encode: %s\n", q2a_last_error()); return -1; }
+    st->has_embd = true;
+    st->t_encode_us += (double) (now_us() - t0);
+    st->n_encode++;
     return 0;
 }
 
@@ -237,6 +254,7 @@ int whisper_pcm_to_mel_with_state(struct whisper_context * ctx, struct whisper_s
     state->n_len = got;
     state->n_len_org = n_len_org_of(n_samples);
     state->pcm.assign(samples, samples + n_samples);
+    state->mel_input = false;
     state->t_mel_us += (double) (now_us() - t0);
     state->n_mel_calls++;
     return 0;
@@ -246,9 +264,33 @@ int whisper_pcm_to_mel(struct whisper_context * ctx, const float * samples, int 
     return ctx ? whisper_pcm_to_mel_with_state(ctx, ctx->state, samples, n_samples, n_threads) : -1;
 }
 
+// qwen2-whisper.cpp:3281-3308: the caller's (already normalised) mel becomes the state's input
+int whisper_set_mel_with_state(struct whisper_context * ctx, struct whisper_state * state, const float * data, int n_len,
+                               int n_mel) {
+    if (!ctx || !state) return -1;
+    if (n_mel != ctx->info.n_mels) {
+        wlog(GGML_LOG_LEVEL_ERROR, "%s: invalid number of mel bands: %d (expected %d)\n", __func__, n_mel, ctx->info.n_mels);
+        return -1;
+    }
+    if (!data || n_len < 1) return -1;   // (the reference would read through NULL / keep an empty mel)
+    state->mel.assign(data, data + (size_t) n_len * n_mel);
+    state->n_len = n_len;
+    state->n_len_org = n_len;
+    state->pcm.clear();
+    state->pcm.shrink_to_fit();
+    state->mel_input = true;
+    return 0;
+}
+
+int whisper_set_mel(struct whisper_context * ctx, const float * data, int n_len, int n_mel) {
+    return ctx ? whisper_set_mel_with_state(ctx, ctx->state, data, n_len, n_mel) : -1;
+}
+
 int whisper_encode_with_state(struct whisper_context * ctx, struct whisper_state * state, int offset, int n_threads) {
     (void) n_threads;
-    if (!ctx || !state || state->pcm.empty() || offset < 0) return -1;
+    if (!ctx || !state || offset < 0) return -1;
+    if (state->mel_input) return encode_mel_window(ctx, state, offset);
+    if (state->pcm.empty()) return -1;
     return encode_window(ctx, state, state->pcm.data(), (int) state->pcm.size(), offset * 10, true);
 }
 
@@ -266,8 +308,9 @@ int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state *
         }
         state->pcm.assign(samples, samples + n_samples);
         state->n_len_org = n_len_org_of(n_samples);
+        state->mel_input = false;
     }
-    if (state->pcm.empty()) return -2;
+    if (state->pcm.empty() && !state->mel_input) return -2;
     // the 1 s rule (qwen2-whisper.cpp:2356-2364): duration_ms, when set, replaces the audio length
     const int seek_start = params.offset_ms / 10;
     const int seek_end = params.duration_ms == 0 ? state->n_len_org : seek_start + params.duration_ms / 10;
@@ -275,8 +318,12 @@ int whisper_full_with_state(struct whisper_context * ctx, struct whisper_state *
         wlog(GGML_LOG_LEVEL_WARN, "whisper_full: input is too short - %d ms < 1000 ms\n", (seek_end - seek_start) * 10);
         return 0;
     }
-    if (state->pcm.size() <= 200) return 0;   // (not reachable with duration_ms unset: under 1 s)
-    const int rc = encode_window(ctx, state, state->pcm.data(), (int) state->pcm.size(), params.offset_ms, params.duration_ms != 0);
+    if (!state->mel_input && state->pcm.size() <= 200) return 0;   // (not reachable with duration_ms unset: under 1 s)
+    if (state->mel_input && seek_start < 0) return -1;
+    // n_samples == 0 after whisper_set_mel: the state's mel from frame offset_ms / 10
+    const int rc = state->mel_input ? encode_mel_window(ctx, state, seek_start)
+                                    : encode_window(ctx, state, state->pcm.data(), (int) state->pcm.size(), params.offset_ms,
+                                                    params.duration_ms != 0);
     if (rc) return rc;
     if (params.abort_callback && params.abort_callback(params.abort_callback_user_data)) {
         wlog(GGML_LOG_LEVEL_ERROR, "whisper_full: failed to encode\n");

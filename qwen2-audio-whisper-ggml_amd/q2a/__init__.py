@@ -28,6 +28,8 @@ EXPORTS = (
     "q2a_test_block_len",
     "q2a_varlen_rows", "q2a_encode_device_varlen", "q2a_encode_host_varlen", "q2a_test_attention_varlen",
     "q2a_test_block_varlen", "q2a_test_operand", "q2a_test_gemm_epi", "q2a_test_gemm_regime",
+    "q2a_mel_valid_lengths", "q2a_encode_device_mel", "q2a_encode_host_mel", "q2a_test_frontend_mel",
+    "whisper_set_mel", "whisper_set_mel_with_state",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -53,6 +55,10 @@ OPERAND_LN, OPERAND_QUANT_F32, OPERAND_QUANT_H16, OPERAND_GELU_Q8K = 0, 1, 2, 3
 EPI_QKV, EPI_RESID, EPI_GELU_H, EPI_GELU_Q8K, EPI_PRE_H = 0, 1, 2, 6, 7
 (REGIME_NARROW, REGIME_128, REGIME_128x256, REGIME_256, REGIME_PIPE8, REGIME_PIPE8_PERSISTENT, REGIME_PIPE8_TAIL,
  REGIME_FIXED) = range(8)
+
+# kinds of the log-mel entry points (include/q2a_encoder.h): all keys / per-clip key lengths / the packed valid rows
+ENCODE_PLAIN, ENCODE_PADDED, ENCODE_VARLEN = 0, 1, 2
+_KINDS = {"plain": ENCODE_PLAIN, "padded": ENCODE_PADDED, "varlen": ENCODE_VARLEN}
 
 # activation contracts (include/q2a_encoder.h)
 ACT_REFERENCE = 0
@@ -135,6 +141,11 @@ def lib() -> C.CDLL:
         if hasattr(L, "q2a_test_gemm_epi"):   # (optional like the hooks above)
             L.q2a_test_gemm_epi.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(vp), C.c_int, vp]
             L.q2a_test_gemm_regime.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "q2a_encode_device_mel"):   # log-mel input (optional like the hooks above)
+            L.q2a_mel_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, i32p, i32p]
+            L.q2a_encode_device_mel.argtypes = [vp, C.c_int, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, vp, i32p, i32p, vp]
+            L.q2a_encode_host_mel.argtypes = [vp, C.c_int, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, i32p, i32p]
+            L.q2a_test_frontend_mel.argtypes = [vp, vp, C.c_int64, C.c_int64, i32p, i32p, C.c_int, vp, vp]
         if hasattr(L, "q2a_varlen_rows"):
             L.q2a_varlen_rows.restype = C.c_int64
             L.q2a_varlen_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
@@ -280,6 +291,100 @@ class Engine:
         return self.encode_host_padded(clips, offsets_ms=offsets_ms, key_len=key_len, out=out, return_status=return_status,
                                        _fn="q2a_encode_host_varlen")
 
+    # ---- log-mel input (q2a_encode_device_mel / q2a_encode_host_mel): the caller's normalised f32 mel, zeros past n_len
+    @staticmethod
+    def _i32(a, n, what):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if len(a) != n:
+            raise ValueError(f"{what} needs {n} entries")
+        return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def encode_device_mel(self, mel_ptr: int, clip_stride: int, ld: int, n_len, out_ptr: int, kind: int = ENCODE_PLAIN,
+                          seek=None, key_len=None, stream: int | None = None):
+        """q2a_encode_device_mel: clip c is [n_mels][ld] f32 at mel_ptr + 4 * c * clip_stride (clip_stride 0: one array
+        for every clip) with n_len[c] frames, encoded from frame seek[c] (None: 0). kind ENCODE_*; key_len=None:
+        mel_valid_lengths' enc_len. Returns (out_len, status); out_len is not written for ENCODE_PLAIN (zeros)."""
+        i32p = C.POINTER(C.c_int32)
+        nl = np.ascontiguousarray(n_len, dtype=np.int32)
+        n = len(nl)
+        _sk, skp = self._i32(seek, n, "seek")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        _check(lib().q2a_encode_device_mel(self.h, kind, C.c_void_p(mel_ptr), C.c_int64(clip_stride), C.c_int64(ld),
+                                           nl.ctypes.data_as(i32p), skp, klp, n, C.c_void_p(out_ptr),
+                                           ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
+                                           C.c_void_p(stream) if stream else None))
+        return ol, st
+
+    def encode_host_mel(self, mels, kind: int = ENCODE_PLAIN, seek=None, key_len=None, out: np.ndarray | None = None,
+                        raise_on_error: bool = True):
+        """q2a_encode_host_mel over host arrays mels[c] = [n_mels][n_len[c]] f32 -> (out, out_len, status); with
+        raise_on_error=False a failing call returns (out, out_len, status, rc)."""
+        i32p = C.POINTER(C.c_int32)
+        mels = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
+        n = len(mels)
+        for m in mels:
+            if m.ndim != 2 or m.shape[0] != self.info.n_mels:
+                raise ValueError(f"mel arrays must be [{self.info.n_mels}][n_len]")
+        if out is None:
+            out = np.zeros((n,) + self.out_shape, dtype=np.float32)
+        ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in mels])
+        nl = np.array([m.shape[1] for m in mels], dtype=np.int32)
+        _sk, skp = self._i32(seek, n, "seek")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        rc = lib().q2a_encode_host_mel(self.h, kind, ptrs, nl.ctypes.data_as(i32p), skp, klp, n, C.c_void_p(out.ctypes.data),
+                                       ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p))
+        if not raise_on_error:
+            return out, ol, st, rc
+        _check(rc)
+        return out, ol, st
+
+    def test_frontend_mel(self, mel_ptr, clip_stride, ld, n_len, x_ptr, seek=None, stream=None):
+        nl = np.ascontiguousarray(n_len, dtype=np.int32)
+        _sk, skp = self._i32(seek, len(nl), "seek")
+        _check(lib().q2a_test_frontend_mel(self.h, C.c_void_p(mel_ptr), C.c_int64(clip_stride), C.c_int64(ld),
+                                           nl.ctypes.data_as(C.POINTER(C.c_int32)), skp, len(nl), C.c_void_p(x_ptr),
+                                           C.c_void_p(stream) if stream else None))
+
+    def encode_features(self, input_features, feature_attention_mask=None, kind: str = "varlen"):
+        """Encode what transformers' Qwen2AudioProcessor hands the model: input_features [B][n_mels][L] f32 (a torch
+        CUDA tensor: device entry point on torch's current stream, the result a tensor on that device; or a numpy
+        array: host entry point) and optionally feature_attention_mask [B][L]. With a mask the key lengths are
+        features_key_len(mask.sum(-1)); without one mel_valid_lengths' enc_len of L frames. kind "plain", "padded" or
+        "varlen". Returns (out [B][n_out][n_audio_state], out_len [B]): rows >= out_len[c] are zeros for the
+        key-length kinds, for "plain" every row is computed and out_len is n_out."""
+        k = _KINDS[kind]
+        shape = tuple(input_features.shape)
+        if len(shape) != 3 or shape[1] != self.info.n_mels:
+            raise ValueError(f"input_features must be [B][{self.info.n_mels}][L]")
+        B, _, L = shape
+        kl = None
+        if feature_attention_mask is not None and k != ENCODE_PLAIN:
+            m = feature_attention_mask
+            m = m.detach().cpu().numpy() if hasattr(m, "detach") else np.asarray(m)
+            if m.shape != (B, L):
+                raise ValueError(f"feature_attention_mask must be [{B}][{L}]")
+            kl = features_key_len(m.astype(np.int64).sum(-1))
+        if hasattr(input_features, "is_cuda"):
+            import torch
+            if not input_features.is_cuda or input_features.dtype != torch.float32:
+                raise ValueError("input_features: a float32 CUDA tensor (or a numpy array)")
+            x = input_features.contiguous()
+            out = torch.empty((B,) + self.out_shape, dtype=torch.float32, device=x.device)
+            ol, _ = self.encode_device_mel(x.data_ptr(), self.info.n_mels * L, L, [L] * B, out.data_ptr(), kind=k, key_len=kl,
+                                           stream=torch.cuda.current_stream(x.device).cuda_stream)
+        else:
+            x = np.ascontiguousarray(input_features, dtype=np.float32)
+            out, ol, _ = self.encode_host_mel(list(x), kind=k, key_len=kl)
+        if k == ENCODE_PLAIN:
+            ol = np.full(B, self.info.n_out, dtype=np.int32)
+        return out, ol
+
     def pcm_to_mel(self, pcm: np.ndarray) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         n_len = (len(pcm) + 480000) // 160
@@ -380,6 +485,7 @@ def _host() -> C.CDLL:
             raise Q2AError(f"{HOST_LIB_PATH} not built; run `make -C {PKG_DIR} host`")
         _host_lib = C.CDLL(HOST_LIB_PATH)
         _host_lib.q2a_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        _host_lib.q2a_mel_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _host_lib.q2a_varlen_rows.restype = C.c_int64
         _host_lib.q2a_varlen_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
     return _host_lib
@@ -410,6 +516,24 @@ def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -
         err.rc = rc
         raise err
     return a.value, b.value
+
+
+def mel_valid_lengths(n_len: int, seek: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
+    """(enc_len, out_len) of n_len log-mel frames encoded from frame seek (q2a_mel_valid_lengths). Host arithmetic
+    through lib/libq2a_host.so: needs no GPU."""
+    a, b = C.c_int32(), C.c_int32()
+    rc = _host().q2a_mel_valid_lengths(n_len, seek, n_audio_ctx, C.byref(a), C.byref(b))
+    if rc != 0:
+        err = Q2AError(f"q2a error {rc}: invalid arguments to q2a_mel_valid_lengths")
+        err.rc = rc
+        raise err
+    return a.value, b.value
+
+
+def features_key_len(n_frames) -> np.ndarray:
+    """Engine.encode_features' key lengths from the valid mel frames of each clip (feature_attention_mask.sum(-1)):
+    (n - 1) // 2 + 1, the encoder positions transformers' _get_feat_extract_output_lengths keeps after conv2."""
+    return ((np.asarray(n_frames, dtype=np.int64) - 1) // 2 + 1).astype(np.int32)
 
 
 def group_split(n_clips: int, n_devices: int) -> list[range]:

@@ -4,6 +4,7 @@
 // recordings as consecutive 30 s windows, and a raw dump of embd_enc.
 //
 //   q2a_main -m MODEL [options] file0.wav [file1.wav ...]
+//   q2a_main -m MODEL -mel FILE [-ot MS] [-oemb OUT]     (log-mel in: whisper_set_mel + whisper_encode)
 #include "q2a_encoder.h"
 #include "q2a_whisper.h"
 
@@ -21,7 +22,7 @@ struct cli {
     std::vector<std::string> files;
     int threads = 4, offset_ms = 0, duration_ms = 0, reps = 1, device = 0, processors = 1, gpus = 0;
     bool no_prints = false, batch = false, long_audio = false, bf16 = false, device_set = false;
-    std::string dump;
+    std::string dump, mel;
 };
 
 void usage(const char * argv0) {
@@ -35,6 +36,9 @@ void usage(const char * argv0) {
             "  -p N,      --processors N   whisper_full_parallel: N contiguous chunks per file, one batch\n"
             "  -b,        --batch          encode all files as one batch (one clip each)\n"
             "  -la,       --long-audio     encode every 30 s window of each file in one batch\n"
+            "  -mel F,    --mel-file F     encode from log-mel instead of a WAV file: F is raw f32 [n_mels][n_len]\n"
+            "                              (q2a_tool mel; n_len from the file size), through whisper_set_mel +\n"
+            "                              whisper_encode at -ot / 10 frames; honours -oemb\n"
             "  -oemb F,   --output-emb F   write embd_enc (f32, [windows/files][750][1280]) to F\n"
             "  -dev N,    --device N       HIP device\n"
             "  -ng N,     --gpus N         -b: spread the batch over N devices, the -dev device first (default: every\n"
@@ -62,6 +66,7 @@ bool parse(int argc, char ** argv, cli & c) {
         else if (a == "-p" || a == "--processors") { if (!(v = next())) return false; c.processors = atoi(v); }
         else if (a == "-ng" || a == "--gpus") { if (!(v = next())) return false; c.gpus = atoi(v); }
         else if (a == "-oemb" || a == "--output-emb") { if (!(v = next())) return false; c.dump = v; }
+        else if (a == "-mel" || a == "--mel-file") { if (!(v = next())) return false; c.mel = v; }
         else if (a == "-b" || a == "--batch") c.batch = true;
         else if (a == "-bf16" || a == "--bf16-act") c.bf16 = true;
         else if (a == "-la" || a == "--long-audio") c.long_audio = true;
@@ -69,7 +74,35 @@ bool parse(int argc, char ** argv, cli & c) {
         else if (a[0] == '-' && a != "-") { fprintf(stderr, "error: unknown argument: %s\n", a.c_str()); return false; }
         else c.files.push_back(a);
     }
-    return !c.files.empty();
+    return !c.files.empty() || !c.mel.empty();
+}
+
+// -mel: the file's log-mel through whisper_set_mel + whisper_encode
+int encode_mel_file(whisper_context * ctx, const cli & c, FILE * dump, int n_out, int n_state) {
+    const int n_mels = whisper_model_n_mels(ctx);
+    std::vector<float> mel;
+    FILE * f = fopen(c.mel.c_str(), "rb");
+    if (f) {
+        fseek(f, 0, SEEK_END);
+        const long bytes = ftell(f);
+        fseek(f, 0, SEEK_SET);
+        if (bytes > 0) mel.resize((size_t) bytes / 4);
+        if (fread(mel.data(), 4, mel.size(), f) != mel.size()) mel.clear();
+        fclose(f);
+    }
+    if (mel.empty() || mel.size() % n_mels) {
+        fprintf(stderr, "error: '%s' is not a raw f32 [%d][n_len] log-mel file\n", c.mel.c_str(), n_mels);
+        return 2;
+    }
+    if (whisper_set_mel(ctx, mel.data(), (int) (mel.size() / n_mels), n_mels) != 0 ||
+        whisper_encode(ctx, c.offset_ms / 10, c.threads) != 0) {
+        fprintf(stderr, "error: failed to encode '%s'\n", c.mel.c_str());
+        return 10;
+    }
+    whisper_print_emb_enc(ctx);
+    const float * emb = whisper_get_embd_enc(ctx, nullptr, nullptr);
+    if (dump && emb) fwrite(emb, 4, (size_t) n_out * n_state, dump);
+    return 0;
 }
 
 void print20(const float * e) {
@@ -111,7 +144,9 @@ int main(int argc, char ** argv) {
 
     int rc = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    if (c.batch) {
+    if (!c.mel.empty()) {
+        rc = encode_mel_file(ctx, c, dump, n_out, n_state);
+    } else if (c.batch) {
         // one batch: clip i = file i (the engine's native batched entry point)
         std::vector<const float *> ptr;
         std::vector<int32_t> ns;
