@@ -177,7 +177,8 @@ int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int3
  * through the layers) travel with the clip — at most 15 rows, computed as queries, never read as keys.
  *
  * Not covered: the whisper_* API, q2a_group_*, the ggml backend and the bf16 activation contract
- * (Q2A_ERR_UNSUPPORTED); the output is not packed; the front end is not restricted to the valid frames. */
+ * (Q2A_ERR_UNSUPPORTED); the front end is not restricted to the valid frames. The output of these entry points is not
+ * packed: q2a_audio_features_* below return the valid rows alone, one clip after the other. */
 int64_t q2a_varlen_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * row_start);
 
 /* q2a_encode_device_padded / q2a_encode_host_padded on the packed rows: the same arguments, checks, out_len, status
@@ -386,6 +387,61 @@ int q2a_projector_get_dims(const q2a_projector * p, int * d_in, int * d_out, int
  * A projector handle owns ONE workspace (the quantized activation operand): calls on one handle must be ordered on one
  * stream (or the caller synchronises between streams); use one handle per stream for concurrent projections. */
 int q2a_projector_apply(q2a_projector * p, const float * x_dev, int64_t rows, float * y_dev, void * stream);
+
+/* ---- audio features in one call: the valid output rows of every clip, packed, through the projector ----------------
+ * What Qwen2AudioForConditionalGeneration scatters into the text embeddings: audio_features = the projector applied to
+ * the valid rows of embd_enc only, one clip after the other. These entry points are q2a_encode_device_varlen /
+ * q2a_encode_device_mel(kind = Q2A_ENCODE_VARLEN) up to and including the encoder blocks; one kernel then pools and
+ * normalises the valid rows of the packed stream and writes them packed — as f32 (embd) and / or straight as the
+ * projector GEMM's activation operand — and the projector's GEMM writes feat. No padded [n_clips][n_out][D] buffer, no
+ * gather, no second pass over the f32 rows. The bytes are those of the composition: feat = q2a_projector_apply of the
+ * concatenated rows out[c][0 .. out_len[c]-1] of q2a_encode_device_varlen, embd those rows themselves.
+ *
+ * q2a_packed_out_rows: where clip c's rows lie (host arithmetic; also exported from libq2a_host.so):
+ *   out_start[0] = 0, out_start[c+1] = out_start[c] + key_len[c] / 2          (out_start has n_clips + 1 entries)
+ * key_len[c] in 0 .. n_audio_ctx (0: a clip that is not encoded). Returns N_tot = out_start[n_clips], Q2A_ERR_ARG for a
+ * length outside the range, n_clips < 0 or n_audio_ctx <= 0. */
+int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * out_start);
+
+/*   p           the projector, or NULL: feat_dev must then be NULL and only the packed embd_enc is written
+ *   feat_dev    [rows_cap][d_out] f32, required with p (Q2A_ERR_ARG without it)
+ *   embd_dev    [rows_cap][n_audio_state] f32, or NULL (both outputs NULL: Q2A_ERR_ARG)
+ *   rows_cap    rows the output arrays hold; N_tot <= rows_cap or Q2A_ERR_ARG (n_clips * n_out always suffices)
+ *   out_len     host [n_clips], may be NULL: clip c has out_len[c] = key_len[c] / 2 rows (0 for a skipped clip), rows
+ *               out_start[c] .. out_start[c+1]-1 of feat_dev / embd_dev; rebuild out_start as the prefix sum of out_len,
+ *               or with q2a_packed_out_rows from the key lengths passed in
+ * pcm_dev / mel_dev and their arguments, key_len (NULL: the derived lengths), status, the 1 s rule (PCM only) and stream
+ * are those of q2a_encode_device_varlen / q2a_encode_device_mel. Every check — theirs, the output arguments above, p on
+ * the engine's device with d_in = n_audio_state (Q2A_ERR_ARG), the reference activation contract (Q2A_ERR_UNSUPPORTED) —
+ * is made before anything is launched or written. Rows at or past N_tot are never written; with no valid row at all
+ * (every clip skipped, or every key length 1) the call returns Q2A_OK and launches nothing behind the metadata upload.
+ * The activation operand lives in p's workspace: q2a_projector_apply's one-stream rule covers these calls too.
+ * Not covered: the whisper_* API, q2a_group_*, the ggml backend, fp16 / bf16 feature output. */
+int q2a_audio_features_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                              const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                              float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                              void * stream);
+int q2a_audio_features_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                  float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                                  void * stream);
+/* Same with host buffers in and out (synchronous): pcm as in q2a_encode_host_varlen, mel as in q2a_encode_host_mel;
+ * feat_host / embd_host [rows_cap][...] receive the rows of all clips in clip order. Clips go through the device path in
+ * chunks of up to 64; on an error, clips whose rows did not reach the caller report Q2A_CLIP_FAILED and out_len 0. */
+int q2a_audio_features_host(q2a_engine * e, q2a_projector * p, const float * const * pcm, const int32_t * n_samples,
+                            const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
+                            int64_t rows_cap, int32_t * out_len, int32_t * status);
+int q2a_audio_features_host_mel(q2a_engine * e, q2a_projector * p, const float * const * mel, const int32_t * n_len,
+                                const int32_t * seek, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
+                                int64_t rows_cap, int32_t * out_len, int32_t * status);
+/* Test hook: the pool kernel of these calls alone, with the engine's final-LayerNorm weights, on caller rows.
+ *   x_dev      packed [M_tot][n_audio_state] f32 (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx)
+ *   embd_dev   [N_tot][n_audio_state] f32 (q2a_packed_out_rows over key_len), or NULL
+ *   codes_dev, dy_dev, aext_dev, ld   the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0) for those N_tot rows in
+ *              q2a_test_operand's layouts, ld >= N_tot; codes_dev NULL: no operand is written
+ * The checks of q2a_test_block_varlen; nothing outside rows 0 .. N_tot-1 of any output is written. */
+int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
+                          void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream);
 
 #ifdef __cplusplus
 }

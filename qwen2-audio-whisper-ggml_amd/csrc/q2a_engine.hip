@@ -867,6 +867,20 @@ struct q2a_engine {
     const uint64_t * mat(int l, int w) const { return h.loff[l] + L_MAT0 + w * A_COUNT; }
 };
 
+// the multi-modal projector (q2a_projector_*, below): one linear weight in q2a_pack_linear's layout, its bias, and one
+// workspace for the activation operand of a call
+struct q2a_projector {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int d_in = 0, d_out = 0, wtype = 0, blk = 0, gblk = 0;   // blk: activation block, gblk: the GEMM's block mode
+    void * wdev = nullptr;          // q2a_pack_linear layout
+    uint64_t off[A_COUNT] = {};
+    float * bias = nullptr;
+    void * ws = nullptr;            // A operand [rows][d_in] fp16 | dy [d_in/blk][MP] | aext [d_in/256][MP][16]
+    size_t ws_bytes = 0;
+    const uint16_t * gelu = nullptr;   // the GEMM's table argument (unused by STORE_F, kept valid)
+};
+
 namespace {
 
 // A NULL `stream` argument of the device-pointer entry points (q2a_encode_device*, q2a_test_*, q2a_projector_apply)
@@ -877,14 +891,15 @@ namespace {
 inline hipStream_t call_stream(const void * stream) { return (hipStream_t) stream; }
 
 // The per-clip metadata of a call, on the device (e->meta) and pinned on the host (e->meta_host): five rows of the
-// call's B entries, then row_start with B + 1 entries (the packed layout of the variable-length encode). clip_max is
+// call's B entries, then row_start with B + 1 entries (the packed layout of the variable-length encode) and out_start
+// with B + 1 entries (the packed output layout of the audio-feature calls, which alone upload it). clip_max is
 // written on the device (the mel kernel's running maximum); every other row comes from the host through upload_meta.
-constexpr size_t meta_words(int B) { return (size_t) B * 6 + 1; }
+constexpr size_t meta_words(int B) { return (size_t) B * 7 + 2; }
 struct meta_rows {
-    int32_t *nsamp, *seek, *clip_ok, *clip_max, *key_len, *row_start, *end;
+    int32_t *nsamp, *seek, *clip_ok, *clip_max, *key_len, *row_start, *out_start, *end;
     meta_rows(int32_t * p, int B)
         : nsamp(p), seek(p + B), clip_ok(p + 2 * B), clip_max(p + 3 * B), key_len(p + 4 * B), row_start(p + 5 * B),
-          end(p + meta_words(B)) {}
+          out_start(p + 6 * B + 1), end(p + meta_words(B)) {}
 };
 
 // The one writer of meta_host. It waits until the previous upload has left the pinned buffer (a queued copy may still
@@ -1127,6 +1142,7 @@ struct block_rows {
     const int32_t * key_len;     // device [B]: per-clip key lengths of the attention, NULL = all T keys
     const int32_t * row_start;   // device [B + 1], NULL = windows
     int r_max;                   // the longest packed segment (host)
+    int N_out;                   // packed output rows (q2a_packed_out_rows), where the call lays them out (host)
 };
 
 // the attention of `rows`: packed rows take the packed kernel, key lengths alone the key-length one, neither the plain one
@@ -1352,19 +1368,36 @@ struct encode_call {
     const float * mel;          // device, clip c: [n_mels][ld] at mel + c * stride
     int64_t ld;
     const int32_t * seek;
+    // the audio-feature tail (ENC_PACKED with `features`; `out` is then not read): the valid output rows of all clips
+    // packed (q2a_packed_out_rows) into embd [rows_cap][D] and / or, through proj, into feat [rows_cap][d_out]
+    bool features;
+    q2a_projector * proj;       // NULL: no projection (feat NULL)
+    float * feat;
+    float * embd;               // NULL: not written
+    int64_t rows_cap;
     frontend_src src() const { return {pcm, stride, mel, ld}; }
 };
 
+// whisper_encoder_output_with_state's too-short rule (:2356-2365) for a clip of n samples encoded from frame seek
+bool clip_has_window(const q2a_engine * e, int n, int seek) {
+    const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
+    return n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+}
+
 // the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
 // clip_ok entry is 0 (clip_ok NULL: every clip has rows). Writes row_start (rows.B + 1 entries), rows.M (0: no clip is
-// encoded) and rows.r_max
-int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_t * clip_ok, int32_t * row_start, block_rows & rows) {
+// encoded) and rows.r_max; with out_start (rows.B + 1 entries) also the packed output layout of the same lengths
+// (q2a_packed_out_rows) and rows.N_out
+int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_t * clip_ok, int32_t * row_start, block_rows & rows,
+                     int32_t * out_start = nullptr) {
     const int B = rows.B;
     std::vector<int32_t> kl(key_len, key_len + B);
     if (clip_ok)
         for (int c = 0; c < B; ++c) if (!clip_ok[c]) kl[c] = 0;
     const int64_t m = q2a_varlen_rows(kl.data(), B, e->d.T, row_start);
-    if (m < 0) { set_err("key lengths outside 0..%d", e->d.T); return Q2A_ERR_ARG; }
+    const int64_t n = out_start ? q2a_packed_out_rows(kl.data(), B, e->d.T, out_start) : 0;
+    if (m < 0 || n < 0) { set_err("key lengths outside 0..%d", e->d.T); return Q2A_ERR_ARG; }
+    rows.N_out = (int) n;
     rows.M = (int) m;
     rows.r_max = 0;
     for (int c = 0; c < B; ++c) rows.r_max = std::max(rows.r_max, row_start[c + 1] - row_start[c]);
@@ -1373,14 +1406,16 @@ int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_
 
 // per-clip metadata (host): whisper_encoder_output_with_state's seek / too-short logic (:2356-2365), uploaded in one
 // copy with what the kind adds: 3 B words (plain), 5 B with the key lengths (padded), 6 B + 1 with their packed layout
-// (packed). `rows` receives what the blocks of the call run on.
+// (packed), 7 B + 2 with the packed output layout behind it (the audio-feature tail). `rows` receives what the blocks
+// of the call run on.
 int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s, int & max_frames, block_rows & rows) {
     const int B = c.B;
     const int64_t max_valid = c.stride > 0 ? c.stride : -1;   // stride 0: shared PCM
     const meta_rows dev(e->meta, B);
     rows = block_rows{B, B * e->d.T, e->X, kind == ENC_PLAIN ? nullptr : dev.key_len, nullptr, 0};
     max_frames = 0;
-    const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start : &meta_rows::end;
+    const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start
+                      : c.features ? &meta_rows::end : &meta_rows::out_start;
     return upload_meta(e, B, &meta_rows::nsamp, last, s, [&](const meta_rows & mh) -> int {
         if (c.mel && c.stride != 0 && c.stride < e->d.M * c.ld) { set_err("clip_stride %lld below n_mels * ld", (long long) c.stride); return Q2A_ERR_ARG; }
         for (int i = 0; i < B; ++i) {
@@ -1392,8 +1427,7 @@ int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStr
                 if (n < 1 || n > c.ld) { set_err("clip %d: n_len %d outside 1..ld", i, n); return Q2A_ERR_ARG; }
             } else {
                 if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", i, n); return Q2A_ERR_ARG; }
-                const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
-                ok = n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+                ok = clip_has_window(e, n, seek);
             }
             mh.nsamp[i] = ok ? n : 0;
             mh.seek[i] = seek;
@@ -1407,14 +1441,16 @@ int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStr
         if (kind != ENC_PACKED) return Q2A_OK;
         rows.X = e->Xp;
         rows.row_start = dev.row_start;
-        return packed_layout_of(e, mh.key_len, mh.clip_ok, mh.row_start, rows);   // a clip that is not encoded has no rows
+        // a clip that is not encoded has no rows
+        return packed_layout_of(e, mh.key_len, mh.clip_ok, mh.row_start, rows, c.features ? mh.out_start : nullptr);
     });
 }
 
 // the rows of a test hook: the windows, for ENC_PADDED with key lengths (host array, checked) uploaded into the key_len
 // row, for ENC_PACKED with their packed layout behind them in the same copy (every clip has rows; rows.X is left to the
 // caller, the attention hook has no residual stream)
-int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, hipStream_t s, block_rows & rows) {
+int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, hipStream_t s, block_rows & rows,
+              bool out_layout = false /* ENC_PACKED: the packed output layout too */) {
     const meta_rows dev(e->meta, B);
     rows = block_rows{B, B * e->d.T, e->X, nullptr, nullptr, 0};
     if (kind == ENC_PLAIN) return Q2A_OK;
@@ -1424,9 +1460,10 @@ int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, 
     const bool packed = kind == ENC_PACKED;
     rows.key_len = dev.key_len;
     if (packed) { rows.X = nullptr; rows.row_start = dev.row_start; }
-    return upload_meta(e, B, &meta_rows::key_len, packed ? &meta_rows::end : &meta_rows::row_start, s, [&](const meta_rows & mh) -> int {
+    const auto last = !packed ? &meta_rows::row_start : out_layout ? &meta_rows::end : &meta_rows::out_start;
+    return upload_meta(e, B, &meta_rows::key_len, last, s, [&](const meta_rows & mh) -> int {
         memcpy(mh.key_len, key_len, (size_t) B * 4);
-        return packed ? packed_layout_of(e, key_len, nullptr, mh.row_start, rows) : Q2A_OK;
+        return packed ? packed_layout_of(e, key_len, nullptr, mh.row_start, rows, out_layout ? mh.out_start : nullptr) : Q2A_OK;
     });
 }
 
@@ -1500,6 +1537,87 @@ int lens_supported(const q2a_engine * e, encode_kind kind) {
     return Q2A_ERR_UNSUPPORTED;
 }
 
+// ---- the projector's GEMM: q2a_projector_apply and the audio-feature tail of encode() build it here ---------------
+// the activation operand of a call of `rows` rows, in the handle's one workspace: A [rows][d_in] 2-byte elements, and for
+// the block-quantized weights d [d_in/blk][ld] and (Q8_K) the block sums [d_in/256][ld][16], ld = rows rounded up to 256
+struct proj_operand {
+    q2a_half * A;
+    float * dy;
+    q2a_half * aext;
+    int ld;
+};
+// the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0 (q2a_ln_args' modes)
+int proj_mode(const q2a_projector * p) { return p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
+
+// grows the workspace (after everything queued on s: calls on one handle are ordered on one stream) and cuts it up
+int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o) {
+    const int K = p->d_in, blk = p->blk;
+    const int64_t MP = (rows + 255) / 256 * 256;
+    const size_t a_bytes = ((size_t) rows * K * 2 + 255) & ~size_t(255);
+    const size_t dy_bytes = blk ? ((size_t) (K / blk) * MP * 4 + 255) & ~size_t(255) : 0;
+    const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;   // (Q6_K: written by the quantizer, unread)
+    const size_t need = a_bytes + dy_bytes + ae_bytes;
+    if (need > p->ws_bytes) {
+        HIP_TRY(hipStreamSynchronize(s));
+        if (p->ws) (void) hipFree(p->ws);
+        p->ws = nullptr; p->ws_bytes = 0;
+        if (hipMalloc(&p->ws, need) != hipSuccess) { (void) hipGetLastError(); set_err("projector workspace of %zu bytes", need); return Q2A_ERR_OOM; }
+        p->ws_bytes = need;
+    }
+    o.A = (q2a_half *) p->ws;
+    o.dy = (float *) ((char *) p->ws + a_bytes);
+    o.aext = (q2a_half *) ((char *) p->ws + a_bytes + dy_bytes);
+    o.ld = (int) MP;
+    return Q2A_OK;
+}
+
+// y [M][d_out] f32 = operand o (M rows) . W^T + bias
+q2a_gemm_args proj_gemm(const q2a_projector * p, int M, const proj_operand & o, float * y) {
+    const int K = p->d_in, N = p->d_out, blk = p->blk;
+    q2a_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    const char * w = (const char *) p->wdev;
+    a.A = o.A; a.lda = K; a.a_rpg = M; a.a_gstride = 0; a.a_step = 1;
+    a.W = (const q2a_half *) (w + p->off[A_W]); a.ldw = K;
+    a.M = M; a.N = N; a.K = K;
+    a.outF = y; a.ldo = N;
+    a.bias = p->bias; a.store_bias = 1;
+    a.gelu_tab = p->gelu;
+    if (blk) {
+        a.nblk = K / blk;
+        a.dx = (const float *) (w + p->off[A_DX]);
+        a.dy = o.dy; a.dy_ld = o.ld;
+        if (p->gblk == Q2A_BLK_Q6K) {
+            a.sc = (const float *) (w + p->off[A_SC]);
+        } else if (blk == 256) {
+            a.dmin = (const float *) (w + p->off[A_DMIN]);
+            a.wext = (const q2a_half *) (w + p->off[A_WEXT]);
+            a.beta = (const float *) (w + p->off[A_BETA]);
+            a.gamma = (const float *) (w + p->off[A_GAMMA]);
+            a.aext = o.aext;
+        }
+    }
+    return a;
+}
+
+// the checks of the audio-feature tail, made before anything is launched or written: the outputs, the projector, and the
+// packed rows against rows_cap (the clips the too-short rule skips have none)
+int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
+    if (!c.feat && !c.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
+    if (c.proj ? !c.feat : c.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
+    if (c.proj && (c.proj->device != e->device || c.proj->d_in != e->d.D)) {
+        set_err("audio features: projector on device %d with d_in %d, engine on device %d with n_audio_state %d", c.proj->device,
+                c.proj->d_in, e->device, e->d.D);
+        return Q2A_ERR_ARG;
+    }
+    int64_t n_tot = 0;
+    for (int i = 0; i < c.B; ++i) {
+        if (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) n_tot += c.kl[i] / 2;
+    }
+    if (n_tot > c.rows_cap) { set_err("audio features: %lld output rows, rows_cap %lld", (long long) n_tot, (long long) c.rows_cap); return Q2A_ERR_ARG; }
+    return Q2A_OK;
+}
+
 // One encode of any kind: metadata, front end, the L blocks, pool + final LayerNorm into out [B][TO][D].
 // ENC_PADDED: the attention of every block masks keys >= kl[c] and output rows >= kl[c] / 2 (every row of a skipped
 // clip) are zeros; everything else runs over all B*T rows as in ENC_PLAIN, which leaves a skipped clip's rows alone.
@@ -1507,13 +1625,18 @@ int lens_supported(const q2a_engine * e, encode_kind kind) {
 // attention's 16-query block) are gathered into one [M_tot][D] stream, the blocks run on those M_tot rows, and the pool
 // reads them back into out, zeros past each clip's valid length. Row for row the padded encode's operations: the same
 // bytes.
+// ENC_PACKED with c.features (q2a_audio_features_*): the same up to and including the blocks; then the pool kernel
+// writes the valid output rows alone, packed (q2a_packed_out_rows), as f32 and / or as the projector GEMM's A operand,
+// and that GEMM writes the features. c.out is not read.
 int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s) {
     const dims & d = e->d;
     const int B = c.B;
-    if (B <= 0 || !(c.pcm || c.mel) || !c.n_samples || !c.out || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    const bool feats = kind == ENC_PACKED && c.features;
+    if (B <= 0 || !(c.pcm || c.mel) || !c.n_samples || !(c.out || feats) || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     if (c.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
     int rc = lens_supported(e, kind);
     if (rc) return rc;
+    if (feats && (rc = features_check(e, c, c.mel != nullptr))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     if ((rc = reserve(e, B))) return rc;
     if (kind == ENC_PACKED && (rc = ensure_packed(e))) return rc;
@@ -1523,8 +1646,12 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
     const meta_rows dev(e->meta, B), host(e->meta_host, B);
     if (kind != ENC_PLAIN && c.out_len)
         for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
-    // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros)
-    if (kind != ENC_PACKED || rows.M > 0) {
+    // the projector's operand buffers, before the first launch (growing them waits for the stream)
+    proj_operand po{nullptr, nullptr, nullptr, 0};
+    if (feats && c.proj && rows.N_out > 0 && (rc = proj_workspace(c.proj, rows.N_out, s, po))) return rc;
+    // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros. The
+    // audio-feature tail writes valid rows only: without any, nothing is launched behind the metadata)
+    if (feats ? rows.N_out > 0 : kind != ENC_PACKED || rows.M > 0) {
         if ((rc = run_frontend(e, c.src(), B, max_frames, s))) return rc;
         if (kind == ENC_PACKED)
             PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, dev.row_start, B, d.T, d.D, rows.r_max, s));
@@ -1532,7 +1659,15 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
             if ((rc = run_block(e, l, rows, s))) return rc;
     }
     const float * lnw = e->g<const float *>(G_LNP_W), * lnb = e->g<const float *>(G_LNP_B);
-    if (kind == ENC_PACKED) {
+    if (feats) {
+        // the valid rows alone, packed: f32 into embd and / or the projector GEMM's A operand straight from the pool
+        // kernel's registers, then that GEMM with its bias epilogue into feat
+        if (rows.N_out == 0) return Q2A_OK;
+        q2a_pool_pack_args pa{e->Xp, B, d.D, rows.N_out, lnw, lnb, dev.row_start, dev.out_start, c.embd,
+                              c.proj ? proj_mode(c.proj) : -1, po.A, po.dy, po.aext, po.ld};
+        PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_pack(pa, s));
+        if (c.proj) LAUNCH(q2a_launch_gemm(proj_gemm(c.proj, rows.N_out, po, c.feat), Q2A_EPI_STORE_F, c.proj->gblk, s));
+    } else if (kind == ENC_PACKED) {
         q2a_pool_varlen_args pa{e->Xp, B, d.T, d.D, lnw, lnb, c.out, dev.key_len, dev.row_start};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
     } else {
@@ -1739,6 +1874,15 @@ struct host_mel {
     const int32_t * n_len;
     const int32_t * seek;       // NULL: 0
 };
+// one clip's window columns of every mel row -> dst [M][TM], and the window as the encode then sees it: win_len frames
+// read from frame win_seek (preset by the caller to 1 and 0)
+static void stage_mel_window(float * dst, const float * mel, int64_t n_len, int64_t seek, int M, int TM, int32_t & win_len,
+                             int32_t & win_seek) {
+    const int w = (int) std::max<int64_t>(0, std::min<int64_t>(n_len - seek, TM));
+    // a window behind the last frame has no columns: one (unread) frame at seek 1 makes it all zeros
+    if (w > 0) win_len = w; else win_seek = 1;
+    for (int j = 0; j < M && w > 0; ++j) memcpy(dst + (int64_t) j * TM, mel + j * n_len + seek, (size_t) w * 4);
+}
 static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * const * pcm, const int32_t * n_samples,
                             const int32_t * offsets_ms, int n_clips, int offset_ms, float * out_host, int32_t * status,
                             const int32_t * kl, int32_t * out_len, const host_mel * hm = nullptr) {
@@ -1795,14 +1939,9 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
             memcpy(b.pin_in + c * maxn, pcm[c0 + c], (size_t) n_samples[c0 + c] * 4);
         }
         if (hm) { win_len.assign(n, 1); win_seek.assign(n, 0); }
-        for (int c = 0; hm && c < n; ++c) {
-            const int64_t n_len = hm->n_len[c0 + c], seek = hm->seek ? hm->seek[c0 + c] : 0;
-            const int w = (int) std::max<int64_t>(0, std::min<int64_t>(n_len - seek, TM));
-            // a window behind the last frame has no columns: one (unread) frame at seek 1 makes it all zeros
-            if (w > 0) win_len[c] = w; else win_seek[c] = 1;
-            for (int j = 0; j < M && w > 0; ++j)
-                memcpy(b.pin_in + c * maxn + (int64_t) j * TM, hm->mel[c0 + c] + j * n_len + seek, (size_t) w * 4);
-        }
+        for (int c = 0; hm && c < n; ++c)
+            stage_mel_window(b.pin_in + c * maxn, hm->mel[c0 + c], hm->n_len[c0 + c], hm->seek ? hm->seek[c0 + c] : 0, M, TM,
+                             win_len[c], win_seek[c]);
         if (hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||   // chunk k-2's encode no longer reads d_in
             hipMemcpyAsync(b.d_in, b.pin_in, (size_t) n * maxn * 4, hipMemcpyHostToDevice, cs) != hipSuccess ||
             hipEventRecord(b.h2d, cs) != hipSuccess ||
@@ -1920,6 +2059,143 @@ int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, con
     const host_mel hm{mel, n_len, seek};
     return encode_host_impl(e, ek, nullptr, nullptr, nullptr, n_clips, 0, out_host, status, ek == ENC_PLAIN ? nullptr : kl.data(),
                             out_len, &hm);
+}
+
+// ---- audio features: the variable-length encode with its valid output rows packed and projected -------------------
+static encode_call features_call(encode_call c, q2a_projector * p, float * feat, float * embd, int64_t rows_cap) {
+    c.out = nullptr;
+    c.features = true;
+    c.proj = p; c.feat = feat; c.embd = embd; c.rows_cap = rows_cap;
+    return c;
+}
+
+int q2a_audio_features_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                              const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                              float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                              void * stream) {
+    std::vector<int32_t> kl;
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    const encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
+    return encode(e, ENC_PACKED, features_call(c, p, feat_dev, embd_dev, rows_cap), call_stream(stream));
+}
+
+int q2a_audio_features_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                  float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                                  void * stream) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    const encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
+    return encode(e, ENC_PACKED, features_call(c, p, feat_dev, embd_dev, rows_cap), call_stream(stream));
+}
+
+// The host variants, plain: chunks of up to 64 clips, each staged into device buffers of its own, run through the device
+// path on the engine's stream and waited for; a chunk's rows follow the previous chunk's in the caller's arrays. kl: the
+// checked key lengths. A clip's status is published once its chunk's rows reached the caller (Q2A_CLIP_FAILED before).
+static int features_host_impl(q2a_engine * e, q2a_projector * p, const float * const * pcm, const int32_t * n_samples,
+                              const int32_t * offsets_ms, const host_mel * hm, const int32_t * kl, int n_clips, float * feat,
+                              float * embd, int64_t rows_cap, int32_t * out_len, int32_t * status) {
+    auto fail_all = [&](int rc) {
+        if (status) for (int k = 0; k < n_clips; ++k) status[k] = Q2A_CLIP_FAILED;
+        return rc;
+    };
+    for (int c = 0; c < n_clips; ++c) {   // (checked before any copy: a negative count would be a huge memcpy)
+        const bool bad = hm ? hm->n_len[c] < 1 || !hm->mel[c] || (hm->seek && hm->seek[c] < 0)
+                            : n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c]);
+        if (bad) { set_err("clip %d: bad input", c); return fail_all(Q2A_ERR_ARG); }
+    }
+    const int32_t * lens = hm ? hm->n_len : n_samples;
+    encode_call all{};   // the whole batch against rows_cap, before anything is written
+    all.n_samples = lens; all.B = n_clips; all.offs = offsets_ms; all.kl = kl;
+    all = features_call(all, p, feat, embd, rows_cap);
+    if (int rc = features_check(e, all, hm != nullptr)) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    const int M = e->d.M, TM = e->d.TM, D = e->d.D, d_out = p ? p->d_out : 0;
+    const int C = std::min(n_clips, 64);
+    std::vector<int32_t> st(n_clips, Q2A_CLIP_FAILED), ol(n_clips, 0), win_len, win_seek;
+    std::vector<float> stage;
+    float * d_in = nullptr, * d_feat = nullptr, * d_embd = nullptr;
+    auto release = [&]() {
+        for (float ** b : {&d_in, &d_feat, &d_embd}) { if (*b) (void) hipFree(*b); *b = nullptr; }
+    };
+    hipStream_t s = e->stream;
+    int64_t row0 = 0;
+    int rc = Q2A_OK;
+    for (int c0 = 0; c0 < n_clips && rc == Q2A_OK; c0 += C) {
+        const int n = std::min(C, n_clips - c0);
+        int64_t maxn = 64, cap = 1;
+        for (int c = 0; c < n; ++c) {
+            if (!hm) maxn = std::max<int64_t>(maxn, (n_samples[c0 + c] + 63) & ~63);
+            cap += kl[c0 + c] / 2;
+        }
+        if (hm) maxn = (int64_t) M * TM;   // one staged window per clip
+        stage.assign((size_t) n * maxn, 0.f);
+        if (hm) { win_len.assign(n, 1); win_seek.assign(n, 0); }
+        for (int c = 0; c < n; ++c) {
+            if (hm) stage_mel_window(stage.data() + c * maxn, hm->mel[c0 + c], hm->n_len[c0 + c], hm->seek ? hm->seek[c0 + c] : 0, M, TM,
+                                     win_len[c], win_seek[c]);
+            else if (n_samples[c0 + c] > 0) memcpy(stage.data() + c * maxn, pcm[c0 + c], (size_t) n_samples[c0 + c] * 4);
+        }
+        if (hipMalloc((void **) &d_in, stage.size() * 4) != hipSuccess || (p && hipMalloc((void **) &d_feat, (size_t) cap * d_out * 4) != hipSuccess) ||
+            (embd && hipMalloc((void **) &d_embd, (size_t) cap * D * 4) != hipSuccess)) {
+            (void) hipGetLastError();
+            set_err("audio features: staging allocation failed");
+            rc = Q2A_ERR_OOM;
+            break;
+        }
+        if (hipMemcpyAsync(d_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
+        encode_call c = hm ? encode_call{nullptr, maxn, win_len.data(), n, 0, nullptr, kl + c0, nullptr, ol.data() + c0, st.data() + c0,
+                                         d_in, TM, win_seek.data()}
+                           : encode_call{d_in, maxn, n_samples + c0, n, 0, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, nullptr,
+                                         ol.data() + c0, st.data() + c0};
+        if ((rc = encode(e, ENC_PACKED, features_call(c, p, d_feat, d_embd, cap), s))) break;
+        int64_t rows = 0;
+        for (int c = 0; c < n; ++c) rows += ol[c0 + c];
+        if ((p && rows && hipMemcpyAsync(feat + row0 * d_out, d_feat, (size_t) rows * d_out * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            (embd && rows && hipMemcpyAsync(embd + row0 * D, d_embd, (size_t) rows * D * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            rc = Q2A_ERR_HIP;
+            break;
+        }
+        release();
+        row0 += rows;
+        for (int c = 0; c < n; ++c) {
+            if (status) status[c0 + c] = st[c0 + c];
+            if (out_len) out_len[c0 + c] = ol[c0 + c];
+            st[c0 + c] = -1;   // published
+        }
+    }
+    if (rc != Q2A_OK) {
+        (void) hipStreamSynchronize(s);
+        (void) hipGetLastError();
+        if (rc == Q2A_ERR_HIP && g_err.empty()) set_err("audio features: host-path copy failed");
+        for (int c = 0; c < n_clips; ++c)
+            if (st[c] != -1) { if (status) status[c] = Q2A_CLIP_FAILED; if (out_len) out_len[c] = 0; }
+    }
+    release();
+    return rc;
+}
+
+int q2a_audio_features_host(q2a_engine * e, q2a_projector * p, const float * const * pcm, const int32_t * n_samples,
+                            const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
+                            int64_t rows_cap, int32_t * out_len, int32_t * status) {
+    std::vector<int32_t> kl;
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    if (!pcm) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    return features_host_impl(e, p, pcm, n_samples, offsets_ms, nullptr, kl.data(), n_clips, feat_host, embd_host, rows_cap, out_len, status);
+}
+
+int q2a_audio_features_host_mel(q2a_engine * e, q2a_projector * p, const float * const * mel, const int32_t * n_len,
+                                const int32_t * seek, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
+                                int64_t rows_cap, int32_t * out_len, int32_t * status) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    if (!mel) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    const host_mel hm{mel, n_len, seek};
+    return features_host_impl(e, p, nullptr, nullptr, nullptr, &hm, kl.data(), n_clips, feat_host, embd_host, rows_cap, out_len, status);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -2205,6 +2481,28 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
     return Q2A_OK;
 }
 
+// the audio-feature tail's pool kernel alone, straight from the caller's packed rows into the caller's buffers
+int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
+                          void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream) {
+    if (!e || !x_dev || n_clips <= 0 || !key_len || mode < 0 || mode > 2) return Q2A_ERR_ARG;
+    if (!codes_dev) mode = -1;   // no operand: the f32 rows alone
+    if (mode < 0 && !embd_dev) return Q2A_ERR_ARG;
+    if ((mode == 1 && (!dy_dev || !aext_dev || e->d.D % 256)) || (mode == 2 && (!dy_dev || e->d.D % 32))) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    int rc = reserve(e, n_clips);
+    if (rc) return rc;
+    block_rows rows;
+    if ((rc = hook_rows(e, ENC_PACKED, key_len, n_clips, s, rows, true))) return rc;
+    if (rows.N_out == 0) return Q2A_OK;
+    if (mode > 0 && ld < rows.N_out) { set_err("ld %d below the %d output rows", ld, rows.N_out); return Q2A_ERR_ARG; }
+    const meta_rows dev(e->meta, n_clips);
+    q2a_pool_pack_args pa{x_dev, n_clips, e->d.D, rows.N_out, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B),
+                          dev.row_start, dev.out_start, embd_dev, mode, (q2a_half *) codes_dev, dy_dev, (q2a_half *) aext_dev, ld};
+    LAUNCH(q2a_launch_pool_pack(pa, s));
+    return Q2A_OK;
+}
+
 int q2a_test_fc1_path(q2a_engine * e, int path) {
     if (!e || path < 0 || path > 2) return Q2A_ERR_ARG;
     e->fc1_path = path;
@@ -2288,18 +2586,7 @@ int q2a_test_attention_varlen(q2a_engine * e, const float * q, const float * k, 
 // file in the ggml container (q2a_write_synthetic_projector layout), run with the encoder's numerics contract for a
 // ggml MUL_MAT of that weight type: activations converted per vec_dot_type (fp16 RNE for F16, Q8_K for Q4_K, Q8_0 for
 // Q8_0 / Q4_0), exact products, fp32 accumulation in the canonical K order, then + bias in f32 — on the same GEMM.
-struct q2a_projector {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int d_in = 0, d_out = 0, wtype = 0, blk = 0, gblk = 0;   // blk: activation block, gblk: the GEMM's block mode
-    void * wdev = nullptr;          // q2a_pack_linear layout
-    uint64_t off[A_COUNT] = {};
-    float * bias = nullptr;
-    void * ws = nullptr;            // A operand [rows][d_in] fp16 | dy [d_in/blk][MP] | aext [d_in/256][MP][16]
-    size_t ws_bytes = 0;
-    const uint16_t * gelu = nullptr;   // the GEMM's table argument (unused by STORE_F, kept valid)
-};
-
+// (struct q2a_projector and the GEMM arguments: with the engine above, the audio-feature tail of encode() runs them too)
 q2a_projector * q2a_projector_open(const char * path, int device) {
     char err[256] = {0};
     q2a_model_file * mf = q2a_model_file_read(path, err, sizeof(err));
@@ -2366,54 +2653,18 @@ int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float 
     if (!p || !x || !y || rows <= 0 || rows > (1 << 30) / 4) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = call_stream(stream);
-    const int M = (int) rows, K = p->d_in, N = p->d_out, blk = p->blk;
-    const int64_t MP = (rows + 255) / 256 * 256;
-    const size_t a_bytes = ((size_t) M * K * 2 + 255) & ~size_t(255);
-    const size_t dy_bytes = blk ? ((size_t) (K / blk) * MP * 4 + 255) & ~size_t(255) : 0;
-    const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;   // (Q6_K: written by the quantizer, unread)
-    const size_t need = a_bytes + dy_bytes + ae_bytes;
-    if (need > p->ws_bytes) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (p->ws) (void) hipFree(p->ws);
-        p->ws = nullptr; p->ws_bytes = 0;
-        if (hipMalloc(&p->ws, need) != hipSuccess) { (void) hipGetLastError(); set_err("projector workspace of %zu bytes", need); return Q2A_ERR_OOM; }
-        p->ws_bytes = need;
-    }
-    q2a_half * A = (q2a_half *) p->ws;
-    float * dy = (float *) ((char *) p->ws + a_bytes);
-    q2a_half * aext = (q2a_half *) ((char *) p->ws + a_bytes + dy_bytes);
-    if (blk == 0) {
+    const int M = (int) rows, K = p->d_in;
+    proj_operand o;
+    if (int rc = proj_workspace(p, rows, s, o)) return rc;
+    if (p->blk == 0) {
         const int64_t n = (int64_t) M * K;
-        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, A, n);
+        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
         LAUNCH(hipGetLastError());
     } else {
-        q2a_quant_args qa{x, nullptr, M, K, blk == 256 ? 1 : 2, A, dy, aext, (int) MP};
+        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
         LAUNCH(q2a_launch_quant_act(qa, s));
     }
-    q2a_gemm_args a;
-    memset(&a, 0, sizeof(a));
-    const char * w = (const char *) p->wdev;
-    a.A = A; a.lda = K; a.a_rpg = M; a.a_gstride = 0; a.a_step = 1;
-    a.W = (const q2a_half *) (w + p->off[A_W]); a.ldw = K;
-    a.M = M; a.N = N; a.K = K;
-    a.outF = y; a.ldo = N;
-    a.bias = p->bias; a.store_bias = 1;
-    a.gelu_tab = p->gelu;
-    if (blk) {
-        a.nblk = K / blk;
-        a.dx = (const float *) (w + p->off[A_DX]);
-        a.dy = dy; a.dy_ld = (int) MP;
-        if (p->gblk == Q2A_BLK_Q6K) {
-            a.sc = (const float *) (w + p->off[A_SC]);
-        } else if (blk == 256) {
-            a.dmin = (const float *) (w + p->off[A_DMIN]);
-            a.wext = (const q2a_half *) (w + p->off[A_WEXT]);
-            a.beta = (const float *) (w + p->off[A_BETA]);
-            a.gamma = (const float *) (w + p->off[A_GAMMA]);
-            a.aext = aext;
-        }
-    }
-    LAUNCH(q2a_launch_gemm(a, Q2A_EPI_STORE_F, p->gblk, s));
+    LAUNCH(q2a_launch_gemm(proj_gemm(p, M, o, y), Q2A_EPI_STORE_F, p->gblk, s));
     return Q2A_OK;
 }
 

@@ -271,6 +271,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     return v;
 }
 
+// The NBQ Q8_K blocks of this wave's row (one of the 8 rows row0 .. row0 + 7 of a 512-thread workgroup, y[u] = the lane's
+// float4 of block u) quantized together: codes to `codes` (+ 256 u), the rows' d and bsum operands staged in LDS and
+// stored by the workgroup as whole sectors. Every wave of the workgroup calls it (a barrier); rows >= M store neither.
+template <int NBQ>
+__device__ __forceinline__ void quant_q8k_rows8(const float4 (&y)[NBQ], int lane, q2a_half * codes, int row0, int M,
+                                                float * dy, q2a_half * aext, int ld) {
+    __shared__ float sd[8][NBQ];
+    __shared__ __attribute__((aligned(16))) q2a_half sa[8][NBQ][16];
+    const int r = threadIdx.x >> 6;
+    quant_q8k_blocks<NBQ>(y, lane, codes, 256, &sd[r][0], 1, &sa[r][0][0], 16);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < NBQ * 8) {     // d: block column u, rows row0 .. row0 + 7 (32 B)
+        const int u = t >> 3, rr = t & 7;
+        if (row0 + rr < M) dy[(int64_t) u * ld + row0 + rr] = sd[rr][u];
+    }
+    if (t < NBQ * 64) {    // bsum operand: block column u, 8 rows x 32 B contiguous, 4 B per thread
+        const int u = t >> 6, w = t & 63, rr = w >> 3, j2 = w & 7;
+        if (row0 + rr < M) *(uint32_t *) (aext + ((int64_t) u * ld + row0 + rr) * 16 + 2 * j2) = *(const uint32_t *) &sa[rr][u][2 * j2];
+    }
+}
+
 // NBQ > 0 (D = 256 NBQ, compile-time): 8 rows per workgroup (512 threads), the LayerNorm weight and bias staged in LDS
 // once per workgroup. Q8_K (MODE 1): the NBQ blocks of a row quantized together; the rows' d and bsum operands are
 // staged in LDS and stored by the workgroup as whole sectors (32 B of d, 256 B of bsums per block column) — one row's
@@ -363,21 +385,8 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
                 y[u] = v[u];
             }
         }
-        __shared__ float sd[8][NBQ];
-        __shared__ __attribute__((aligned(16))) q2a_half sa[8][NBQ][16];
-        const int r = threadIdx.x >> 6;
         // codes of a clamped duplicate row (past M) are the real last row's: rewriting them changes nothing
-        quant_q8k_blocks<NBQ>(y, lane, outH + (int64_t) row * D + 4 * lane, 256, &sd[r][0], 1, &sa[r][0][0], 16);
-        __syncthreads();
-        const int t = threadIdx.x;
-        if (t < NBQ * 8) {     // d: block column u, rows row0 .. row0 + 7 (32 B)
-            const int u = t >> 3, rr = t & 7;
-            if (row0 + rr < M) dy[(int64_t) u * ld + row0 + rr] = sd[rr][u];
-        }
-        if (t < NBQ * 64) {    // bsum operand: block column u, 8 rows x 32 B contiguous, 4 B per thread
-            const int u = t >> 6, w = t & 63, rr = w >> 3, j2 = w & 7;
-            if (row0 + rr < M) *(uint32_t *) (aext + ((int64_t) u * ld + row0 + rr) * 16 + 2 * j2) = *(const uint32_t *) &sa[rr][u][2 * j2];
-        }
+        quant_q8k_rows8<NBQ>(y, lane, outH + (int64_t) row * D + 4 * lane, row0, M, dy, aext, ld);
         return;
     }
     if (NBQ && row_raw >= M) return;   // (after the workgroup's barrier)
@@ -596,13 +605,15 @@ __global__ __launch_bounds__(GQ_THREADS) void k_gelu_quant_q8k_h16(const q2a_hal
 }
 
 // AvgPool1d(k=2,s=2) over time (ggml.c:15077-15125: drow = 0; += a; += b; /= 2) + final LayerNorm -> f32
-// One output row by one wave: rows a4 / b4 of D floats pooled, normalised (lng, lnb) -> o4. Shared by the full-window
-// and the packed kernel, so both run the same operations in the same order.
-__device__ __forceinline__ void pool_ln_row(const float4 * a4, const float4 * b4, float4 * o4, int D, const float * lng,
-                                            const float * lnb, int lane) {
+// One output row by one wave: rows a4 / b4 of D floats pooled and normalised (lng, lnb) into v — lane l holds float4
+// chunks l, l + 64, ... (chunks at or past D / 4 hold a clamped duplicate). The one statement of this arithmetic: the
+// full-window, the packed and the operand-writing kernels all run it, the same operations in the same order.
+// MAXC: chunks per lane, D <= 256 MAXC.
+template <int MAXC>
+__device__ __forceinline__ void pool_ln_regs(const float4 * a4, const float4 * b4, float4 (&v)[MAXC], int D, const float * lng,
+                                             const float * lnb, int lane) {
     const int nch = D / 4;
-    constexpr int MAXC = 8;
-    float4 v[MAXC], bv[MAXC];
+    float4 bv[MAXC];
     // the rows' loads at clamped chunk indices (always readable) before any arithmetic: under the `ch < nch` branches
     // each chunk's loads waited alone
 #pragma unroll
@@ -648,6 +659,15 @@ __device__ __forceinline__ void pool_ln_row(const float4 * a4, const float4 * b4
         y.w = (v[u].w * scale) * gg.w + bb.w;
         v[u] = y;
     }
+}
+
+// ... -> o4 (f32)
+__device__ __forceinline__ void pool_ln_row(const float4 * a4, const float4 * b4, float4 * o4, int D, const float * lng,
+                                            const float * lnb, int lane) {
+    constexpr int MAXC = 8;
+    float4 v[MAXC];
+    pool_ln_regs<MAXC>(a4, b4, v, D, lng, lnb, lane);
+    const int nch = D / 4;
 #pragma unroll
     for (int u = 0; u < MAXC; ++u) {
         const int ch = lane + 64 * u;
@@ -684,6 +704,77 @@ __global__ __launch_bounds__(256) void k_pool_ln_varlen(const q2a_pool_varlen_ar
     const float4 * a4 = (const float4 *) (p.X + ((int64_t) r0 + 2 * t) * p.D);
     const float4 * b4 = (const float4 *) (p.X + ((int64_t) r0 + 2 * t + 1) * p.D);
     pool_ln_row(a4, b4, o4, p.D, p.g, p.b, lane);
+}
+
+// k_pool_ln_varlen's valid rows packed one clip after the other, each written as f32 and / or as the A operand of the
+// GEMM that follows (q2a_pool_pack_args): the f32 row is pool_ln_regs', the operand the LayerNorm kernels' conversion of
+// it (k_to_half's cast, quant_q8k_block(s), quant_q80_block), so both equal what k_pool_ln_varlen, a gather of the valid
+// rows and the quantizer launch give. One wave per destination row n. Its clip c is the number of entries
+// out_start[1 .. n_clips] at or below n (out_start never decreases; a clip without rows is stepped over), counted 64
+// entries at a time with one load and a ballot; the row's loads are all issued before its arithmetic.
+// NBQ = 0: any D, 4 rows per workgroup. NBQ > 0 (D = 256 NBQ, Q8_K): rownorm_rows' 8-row form, d and the block sums
+// stored as whole sectors from LDS; a wave past N_tot repeats the last row (the workgroup's barrier) and stores nothing
+// of its own.
+template <int MODE, int NBQ>
+__device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
+    const int lane = threadIdx.x & 63;
+    constexpr int RPB = NBQ ? 8 : 4;
+    const int row0 = blockIdx.x * RPB;
+    const int n_raw = row0 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if constexpr (!NBQ) {
+        if (n_raw >= p.N_tot) return;
+    }
+    const int n = min(n_raw, p.N_tot - 1);
+    int c = 0;
+    for (int base = 0; base < p.n_clips; base += 64) {
+        const int i = base + lane + 1;
+        const int os = p.out_start[min(i, p.n_clips)];
+        c += __popcll(__ballot(i <= p.n_clips && os <= n));
+    }
+    c = __builtin_amdgcn_readfirstlane(c);   // < n_clips: n < N_tot = out_start[n_clips]
+    const int j = n - p.out_start[c];
+    const int D = NBQ ? 256 * NBQ : p.D, nch = D / 4;
+    const float4 * a4 = (const float4 *) (p.X + ((int64_t) p.row_start[c] + 2 * j) * D);
+    constexpr int MAXC = NBQ ? NBQ : 8;
+    float4 v[MAXC];
+    pool_ln_regs<MAXC>(a4, a4 + nch, v, D, p.g, p.b, lane);
+    if (p.embd && n_raw < p.N_tot) {
+        float4 * o4 = (float4 *) (p.embd + (int64_t) n * D);
+#pragma unroll
+        for (int u = 0; u < MAXC; ++u) {
+            const int ch = lane + 64 * u;
+            if (NBQ || ch < nch) o4[ch] = v[u];
+        }
+    }
+    if constexpr (MODE == 1 && NBQ > 0) {
+        // codes of a repeated last row are that row's own: rewriting them changes nothing
+        quant_q8k_rows8<NBQ>(v, lane, p.outH + (int64_t) n * D + 4 * lane, row0, p.N_tot, p.dy, p.aext, p.dy_ld);
+    } else if constexpr (MODE >= 0) {
+#pragma unroll
+        for (int u = 0; u < MAXC; ++u) {
+            const int ch = lane + 64 * u;
+            if (ch >= nch) continue;   // (Q8_K: whole waves, D % 256 == 0; Q8_0: whole 8-lane groups, D % 32 == 0)
+            q2a_half * o = p.outH + (int64_t) n * D + 4 * ch;
+            if (MODE == 0) {
+                typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+                *(h4_t *) o = h4_t{(_Float16) v[u].x, (_Float16) v[u].y, (_Float16) v[u].z, (_Float16) v[u].w};
+            } else if (MODE == 1) {
+                quant_q8k_block(v[u], lane, o, p.dy + (int64_t) u * p.dy_ld + n, p.aext + ((int64_t) u * p.dy_ld + n) * 16);
+            } else {
+                quant_q80_block(v[u], lane, o, p.dy + (int64_t) (ch / 8) * p.dy_ld + n);
+            }
+        }
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_poolnorm_pack(const q2a_pool_pack_args p) {
+    pool_pack_rows<MODE, 0>(p);
+}
+
+// rows of D = 1280 (the model width) into a Q8_K operand: 8 rows per 512-thread workgroup
+__global__ __launch_bounds__(512) void k_poolnorm_pack5(const q2a_pool_pack_args p) {
+    pool_pack_rows<1, 5>(p);
 }
 
 }  // namespace
@@ -791,5 +882,19 @@ hipError_t q2a_launch_pool_ln(const q2a_pool_args & a, hipStream_t s) {
 hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048 || !a.key_len || !a.row_start) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_pool_ln_varlen, dim3((a.n_clips * (a.T / 2) + 3) / 4), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s) {
+    if (a.D % 4 != 0 || a.D > 2048 || a.n_clips < 1 || a.N_tot < 1 || !a.X || !a.row_start || !a.out_start) return hipErrorInvalidValue;
+    if (a.mode < -1 || a.mode > 2 || (a.mode < 0 ? !a.embd : !a.outH)) return hipErrorInvalidValue;
+    if (a.mode == 1 && (a.D % 256 || !a.dy || !a.aext || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
+    if (a.mode == 2 && (a.D % 32 || !a.dy || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
+    const dim3 grid((a.N_tot + 3) / 4), blk(256);
+    if (a.mode == 1 && a.D == 1280) hipLaunchKernelGGL(k_poolnorm_pack5, dim3((a.N_tot + 7) / 8), dim3(512), 0, s, a);
+    else if (a.mode == 1) hipLaunchKernelGGL(k_poolnorm_pack<1>, grid, blk, 0, s, a);
+    else if (a.mode == 2) hipLaunchKernelGGL(k_poolnorm_pack<2>, grid, blk, 0, s, a);
+    else if (a.mode == 0) hipLaunchKernelGGL(k_poolnorm_pack<0>, grid, blk, 0, s, a);
+    else hipLaunchKernelGGL(k_poolnorm_pack<-1>, grid, blk, 0, s, a);
     return hipGetLastError();
 }

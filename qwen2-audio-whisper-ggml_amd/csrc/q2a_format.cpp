@@ -146,6 +146,22 @@ extern "C" int64_t q2a_varlen_rows(const int32_t * key_len, int n_clips, int n_a
     return rows;
 }
 
+// the packed output layout of the audio-feature entry points (include/q2a_encoder.h); here for the same reason
+extern "C" int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * out_start) {
+    if (!out_start || n_clips < 0 || (n_clips > 0 && !key_len) || n_audio_ctx <= 0) return Q2A_ERR_ARG;
+    for (int c = 0; c < n_clips; ++c)   // (checked first: nothing is written on an error)
+        if (key_len[c] < 0 || key_len[c] > n_audio_ctx) return Q2A_ERR_ARG;
+    int64_t rows = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        if (rows > INT32_MAX) return Q2A_ERR_ARG;
+        out_start[c] = (int32_t) rows;
+        rows += key_len[c] / 2;   // AvgPool1d(2)
+    }
+    if (rows > INT32_MAX) return Q2A_ERR_ARG;
+    out_start[n_clips] = (int32_t) rows;
+    return rows;
+}
+
 static double hz_to_mel_slaney(double f) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
     const double logstep = std::log(6.4) / 27.0;

@@ -296,3 +296,23 @@ struct q2a_pool_varlen_args {
     const int32_t * row_start;   // device [clips + 1]
 };
 hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t s);
+// The same rows packed, and the next GEMM's A operand with them: destination row n = out_start[c] + j (j < key_len[c] / 2)
+// pools packed rows row_start[c] + 2j, + 1 with k_pool_ln's operations in its order and writes the f32 row to embd[n]
+// (NULL: not written) and its conversion (mode 0 fp16, 1 Q8_K, 2 Q8_0: q2a_ln_args' layouts, computed from that f32
+// value) to outH / dy / aext (mode -1: none). N_tot = out_start[n_clips] (q2a_packed_out_rows); nothing outside rows
+// 0 .. N_tot-1 of any output is written.
+struct q2a_pool_pack_args {
+    const float * X;             // [M_tot][D] packed
+    int n_clips, D, N_tot;
+    const float * g;
+    const float * b;
+    const int32_t * row_start;   // device [clips + 1]
+    const int32_t * out_start;   // device [clips + 1]
+    float * embd;                // [N_tot][D] f32, or NULL
+    int mode;
+    q2a_half * outH;             // [N_tot][D]
+    float * dy;                  // block-major [D/blk][dy_ld]
+    q2a_half * aext;             // block-major [D/256][dy_ld][16]
+    int dy_ld;
+};
+hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s);

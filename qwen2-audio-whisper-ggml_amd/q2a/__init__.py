@@ -30,6 +30,8 @@ EXPORTS = (
     "q2a_test_block_varlen", "q2a_test_operand", "q2a_test_gemm_epi", "q2a_test_gemm_regime",
     "q2a_mel_valid_lengths", "q2a_encode_device_mel", "q2a_encode_host_mel", "q2a_test_frontend_mel",
     "whisper_set_mel", "whisper_set_mel_with_state",
+    "q2a_packed_out_rows", "q2a_audio_features_device", "q2a_audio_features_device_mel", "q2a_audio_features_host",
+    "q2a_audio_features_host_mel", "q2a_test_pool_operand",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -149,6 +151,17 @@ def lib() -> C.CDLL:
         if hasattr(L, "q2a_varlen_rows"):
             L.q2a_varlen_rows.restype = C.c_int64
             L.q2a_varlen_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
+        if hasattr(L, "q2a_audio_features_device"):   # packed audio features (optional like the hooks above)
+            L.q2a_packed_out_rows.restype = C.c_int64
+            L.q2a_packed_out_rows.argtypes = [i32p, C.c_int, C.c_int, i32p]
+            L.q2a_audio_features_device.argtypes = [vp, vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, vp, vp, C.c_int64,
+                                                    i32p, i32p, vp]
+            L.q2a_audio_features_device_mel.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, vp, vp,
+                                                        C.c_int64, i32p, i32p, vp]
+            L.q2a_audio_features_host.argtypes = [vp, vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, vp, C.c_int64, i32p, i32p]
+            L.q2a_audio_features_host_mel.argtypes = [vp, vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, vp, C.c_int64, i32p,
+                                                      i32p]
+            L.q2a_test_pool_operand.argtypes = [vp, C.c_int, vp, C.c_int, i32p, vp, vp, vp, vp, C.c_int, vp]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -385,6 +398,139 @@ class Engine:
             ol = np.full(B, self.info.n_out, dtype=np.int32)
         return out, ol
 
+    # ---- audio features (q2a_audio_features_*): the valid output rows of all clips packed, through the projector
+    def audio_features_device(self, pcm_ptr: int, pcm_stride: int, n_samples, feat_ptr: int, embd_ptr: int, rows_cap: int,
+                              projector=None, offsets_ms=None, key_len=None, stream: int | None = None):
+        """q2a_audio_features_device: encode_device_varlen's inputs; feat_ptr [rows_cap][d_out] (0 without a projector)
+        and embd_ptr [rows_cap][n_audio_state] (0: not written) receive clip c's out_len[c] rows at the prefix sum of
+        out_len (packed_out_rows). Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        n = len(ns)
+        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_audio_features_device(self.h, projector.h if projector is not None else None, p(pcm_ptr),
+                                               C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n, p(feat_ptr),
+                                               p(embd_ptr), C.c_int64(rows_cap), ol.ctypes.data_as(i32p),
+                                               st.ctypes.data_as(i32p), p(stream)))
+        return ol, st
+
+    def audio_features_device_mel(self, mel_ptr: int, clip_stride: int, ld: int, n_len, feat_ptr: int, embd_ptr: int,
+                                  rows_cap: int, projector=None, seek=None, key_len=None, stream: int | None = None):
+        """q2a_audio_features_device_mel: encode_device_mel's inputs (kind ENCODE_VARLEN), audio_features_device's
+        outputs. Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        nl = np.ascontiguousarray(n_len, dtype=np.int32)
+        n = len(nl)
+        _sk, skp = self._i32(seek, n, "seek")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_audio_features_device_mel(self.h, projector.h if projector is not None else None, p(mel_ptr),
+                                                   C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp, n,
+                                                   p(feat_ptr), p(embd_ptr), C.c_int64(rows_cap), ol.ctypes.data_as(i32p),
+                                                   st.ctypes.data_as(i32p), p(stream)))
+        return ol, st
+
+    def _features_host(self, fn, ptrs, lens, n, second, key_len, projector, embd, rows_cap, raise_on_error):
+        i32p = C.POINTER(C.c_int32)
+        _kl, klp = self._i32(key_len, n, "key_len")
+        if rows_cap is None:   # the key lengths bound the rows; without them a full window per clip
+            rows_cap = int((_kl // 2).sum()) if _kl is not None else n * self.info.n_out
+        feat = np.zeros((rows_cap, projector.d_out), dtype=np.float32) if projector is not None else None
+        emb = np.zeros((rows_cap, self.info.n_audio_state), dtype=np.float32) if embd else None
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        rc = fn(self.h, projector.h if projector is not None else None, ptrs, lens.ctypes.data_as(i32p), second, klp, n,
+                C.c_void_p(feat.ctypes.data) if feat is not None else None,
+                C.c_void_p(emb.ctypes.data) if emb is not None else None, C.c_int64(rows_cap), ol.ctypes.data_as(i32p),
+                st.ctypes.data_as(i32p))
+        if raise_on_error:
+            _check(rc)
+        n_tot = int(ol.sum())
+        res = (feat[:n_tot] if feat is not None else None, emb[:n_tot] if emb is not None else None, ol, st)
+        return res if raise_on_error else res + (rc,)
+
+    def audio_features_host(self, clips, projector=None, offsets_ms=None, key_len=None, embd: bool = True,
+                            rows_cap: int | None = None, raise_on_error: bool = True):
+        """q2a_audio_features_host over host PCM clips -> (feat [N_tot][d_out] or None without a projector, embd
+        [N_tot][n_audio_state] or None with embd=False, out_len, status); with raise_on_error=False also rc."""
+        clips = [np.ascontiguousarray(c, dtype=np.float32) for c in clips]
+        n = len(clips)
+        ptrs = (C.c_void_p * n)(*[c.ctypes.data for c in clips])
+        ns = np.array([len(c) for c in clips], dtype=np.int32)
+        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
+        return self._features_host(lib().q2a_audio_features_host, ptrs, ns, n, ofp, key_len, projector, embd, rows_cap,
+                                   raise_on_error)
+
+    def audio_features_host_mel(self, mels, projector=None, seek=None, key_len=None, embd: bool = True,
+                                rows_cap: int | None = None, raise_on_error: bool = True):
+        """q2a_audio_features_host_mel over host arrays mels[c] = [n_mels][n_len[c]] f32; results as audio_features_host."""
+        mels = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
+        n = len(mels)
+        for m in mels:
+            if m.ndim != 2 or m.shape[0] != self.info.n_mels:
+                raise ValueError(f"mel arrays must be [{self.info.n_mels}][n_len]")
+        ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in mels])
+        nl = np.array([m.shape[1] for m in mels], dtype=np.int32)
+        _sk, skp = self._i32(seek, n, "seek")
+        return self._features_host(lib().q2a_audio_features_host_mel, ptrs, nl, n, skp, key_len, projector, embd, rows_cap,
+                                   raise_on_error)
+
+    def audio_features(self, input_features, feature_attention_mask=None, projector=None, return_embd: bool = False):
+        """What Qwen2AudioForConditionalGeneration scatters into the text embeddings, from what its processor hands the
+        model: input_features [B][n_mels][L] f32 (a torch CUDA tensor: device entry point on torch's current stream, the
+        results tensors on that device; or a numpy array: host entry point) and optionally feature_attention_mask [B][L]
+        — encode_features' argument handling. Returns (features [N_tot][d_out], out_len [B]): the projector applied to
+        the valid rows of embd_enc alone, clip c's out_len[c] rows at the prefix sum of out_len; with return_embd also
+        the packed embd_enc [N_tot][n_audio_state]. projector=None (return_embd required): features is None."""
+        if projector is None and not return_embd:
+            raise ValueError("audio_features: a projector, or return_embd=True")
+        shape = tuple(input_features.shape)
+        if len(shape) != 3 or shape[1] != self.info.n_mels:
+            raise ValueError(f"input_features must be [B][{self.info.n_mels}][L]")
+        B, _, L = shape
+        if feature_attention_mask is not None:
+            m = feature_attention_mask
+            m = m.detach().cpu().numpy() if hasattr(m, "detach") else np.asarray(m)
+            if m.shape != (B, L):
+                raise ValueError(f"feature_attention_mask must be [{B}][{L}]")
+            kl = features_key_len(m.astype(np.int64).sum(-1))
+        else:
+            kl = np.full(B, mel_valid_lengths(L, 0, self.info.n_audio_ctx)[0], dtype=np.int32)
+        n_tot, _ = packed_out_rows(kl, self.info.n_audio_ctx)   # (log-mel input: no clip is skipped)
+        if hasattr(input_features, "is_cuda"):
+            import torch
+            if not input_features.is_cuda or input_features.dtype != torch.float32:
+                raise ValueError("input_features: a float32 CUDA tensor (or a numpy array)")
+            x = input_features.contiguous()
+            feat = torch.empty((n_tot, projector.d_out), dtype=torch.float32, device=x.device) if projector is not None else None
+            emb = torch.empty((n_tot, self.info.n_audio_state), dtype=torch.float32, device=x.device) if return_embd else None
+            ol = np.zeros(B, dtype=np.int32)
+            if n_tot:   # (an empty tensor has no pointer to pass)
+                ol, _ = self.audio_features_device_mel(x.data_ptr(), self.info.n_mels * L, L, [L] * B,
+                                                       feat.data_ptr() if feat is not None else 0,
+                                                       emb.data_ptr() if emb is not None else 0, n_tot, projector=projector,
+                                                       key_len=kl, stream=torch.cuda.current_stream(x.device).cuda_stream)
+        else:
+            x = np.ascontiguousarray(input_features, dtype=np.float32)
+            feat, emb, ol, _ = self.audio_features_host_mel(list(x), projector=projector, key_len=kl, embd=return_embd,
+                                                            rows_cap=n_tot)
+        return (feat, ol, emb) if return_embd else (feat, ol)
+
+    def test_pool_operand(self, mode, x_ptr, n_clips, key_len, embd_ptr=0, codes_ptr=0, dy_ptr=0, aext_ptr=0, ld=0, stream=None):
+        """q2a_test_pool_operand: the audio-feature calls' pool kernel alone on packed caller rows x [M_tot][D] ->
+        embd [N_tot][D] f32 and / or the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0) in test_operand's layouts."""
+        kl = np.ascontiguousarray(key_len, dtype=np.int32)
+        assert len(kl) == n_clips
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_test_pool_operand(self.h, mode, p(x_ptr), n_clips, kl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           p(embd_ptr), p(codes_ptr), p(dy_ptr), p(aext_ptr), ld, p(stream)))
+
     def pcm_to_mel(self, pcm: np.ndarray) -> np.ndarray:
         pcm = np.ascontiguousarray(pcm, dtype=np.float32)
         n_len = (len(pcm) + 480000) // 160
@@ -488,6 +634,8 @@ def _host() -> C.CDLL:
         _host_lib.q2a_mel_valid_lengths.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _host_lib.q2a_varlen_rows.restype = C.c_int64
         _host_lib.q2a_varlen_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        _host_lib.q2a_packed_out_rows.restype = C.c_int64
+        _host_lib.q2a_packed_out_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
     return _host_lib
 
 
@@ -504,6 +652,21 @@ def varlen_rows(key_len, n_audio_ctx: int = 1500) -> tuple[int, np.ndarray]:
         err.rc = int(m)
         raise err
     return int(m), rs
+
+
+def packed_out_rows(key_len, n_audio_ctx: int = 1500) -> tuple[int, np.ndarray]:
+    """(N_tot, out_start): the packed output layout of the audio-feature calls (q2a_packed_out_rows) — clip c's
+    key_len[c] // 2 output rows are rows out_start[c] .. out_start[c+1]-1 of N_tot = out_start[-1]. Host arithmetic
+    through lib/libq2a_host.so: needs no GPU."""
+    kl = np.ascontiguousarray(key_len, dtype=np.int32).reshape(-1)
+    os_ = np.zeros(len(kl) + 1, dtype=np.int32)
+    i32p = C.POINTER(C.c_int32)
+    n = _host().q2a_packed_out_rows(kl.ctypes.data_as(i32p), len(kl), n_audio_ctx, os_.ctypes.data_as(i32p))
+    if n < 0:
+        err = Q2AError(f"q2a error {n}: invalid arguments to q2a_packed_out_rows")
+        err.rc = int(n)
+        raise err
+    return int(n), os_
 
 
 def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
