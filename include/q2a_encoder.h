@@ -378,7 +378,8 @@ int q2a_test_block_varlen(q2a_engine * e, int layer, float * x_dev, int n_clips,
  * (modeling_qwen2_audio.py), the step after the reference's path ends at embd_enc (qwen2-whisper.cpp:2185; the
  * reference has no projector). Weights: a projector file in the ggml container (multi_modal_projector.linear.weight
  * [d_out][d_in] F16 / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0, .bias [d_out] F32; bin/q2a_tool gen-projector + quantize). Numerics: a ggml
- * MUL_MAT of that weight type (activations per vec_dot_type, exact products, fp32 accumulation) + bias in f32. */
+ * MUL_MAT of that weight type (activations per vec_dot_type, exact products, fp32 accumulation) + bias in f32.
+ * d_out % 128 == 0; d_in % 256 == 0 (F16 weights: % 64), else q2a_projector_open fails. */
 typedef struct q2a_projector q2a_projector;
 q2a_projector * q2a_projector_open(const char * path, int device);
 void q2a_projector_close(q2a_projector * p);
@@ -416,7 +417,8 @@ int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int n_audio_ct
  * is made before anything is launched or written. Rows at or past N_tot are never written; with no valid row at all
  * (every clip skipped, or every key length 1) the call returns Q2A_OK and launches nothing behind the metadata upload.
  * The activation operand lives in p's workspace: q2a_projector_apply's one-stream rule covers these calls too.
- * Not covered: the whisper_* API, q2a_group_*, the ggml backend, fp16 / bf16 feature output. */
+ * Not covered: the whisper_* API, q2a_group_*, the ggml backend. (fp16 / bf16 output, and rows placed where the caller
+ * wants them: the q2a_*_to calls below.) */
 int q2a_audio_features_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
                               const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
                               float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
@@ -434,6 +436,53 @@ int q2a_audio_features_host(q2a_engine * e, q2a_projector * p, const float * con
 int q2a_audio_features_host_mel(q2a_engine * e, q2a_projector * p, const float * const * mel, const int32_t * n_len,
                                 const int32_t * seek, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
                                 int64_t rows_cap, int32_t * out_len, int32_t * status);
+/* ---- audio features as f32 / fp16 / bf16, stored in place into the consumer's rows --------------------------------------
+ * Qwen2AudioForConditionalGeneration casts audio_features to the language model's dtype and masked_scatters them into
+ * inputs_embeds at the audio-token positions. The _to calls do both in the projector GEMM's epilogue: every value is the
+ * f32 call's value fl32(acc + bias[n]) — same tile regime, same K order, same accumulators — rounded once more, to
+ * nearest even, for the 16-bit types, and stored at row row_map[m] of the destination. No cast pass, no indexed copy,
+ * no f32 temporary. */
+enum { Q2A_DT_F32 = 0, Q2A_DT_F16 = 1, Q2A_DT_BF16 = 2 };
+typedef struct {
+    void * base;      /* device; 16-byte aligned */
+    int64_t ld;       /* elements between rows, >= d_out, ld * element size a multiple of 16 */
+    int64_t n_rows;   /* rows the destination holds (<= INT32_MAX) */
+    int32_t dtype;    /* Q2A_DT_* */
+    int32_t reserved; /* 0 */
+} q2a_feat_dst;
+/* q2a_projector_apply with that epilogue (same operand conversion, workspace and one-stream rule): packed row m of
+ * x_dev goes to destination row row_map_dev[m] (device int32 [rows]; NULL: row m, rows <= n_rows required), element
+ * (r, n) at base + (r * ld + n) * element size. A row with r < 0 or r >= n_rows is not stored — whatever the map holds,
+ * nothing outside [0, n_rows) x [0, d_out) is written; columns d_out .. ld-1 of a row are never written. Q2A_ERR_ARG
+ * for a NULL or misaligned base, ld < d_out, ld * element size % 16 != 0, an unknown dtype, reserved != 0, n_rows
+ * outside 0 .. INT32_MAX. */
+int q2a_projector_apply_to(q2a_projector * p, const float * x_dev, int64_t rows, const q2a_feat_dst * dst,
+                           const int32_t * row_map_dev, void * stream);
+/* The Q2A_REGIME_* the projector's GEMM takes at `rows` rows on p's device: the launcher's own decision function,
+ * nothing is launched. One answer for q2a_projector_apply and q2a_projector_apply_to. Q2A_ERR_ARG for bad arguments. */
+int q2a_projector_regime(q2a_projector * p, int64_t rows);
+/* q2a_feat_rows: the destination rows of a call (host arithmetic; also exported from libq2a_host.so). Clip c's out_len[c]
+ * rows go to destination rows clip_row[c] .. clip_row[c] + out_len[c] - 1 (the contiguous run of audio tokens the
+ * processor emits per clip); clip_row NULL: packed, clip after clip from row 0. A clip with out_len[c] = 0 is ignored,
+ * whatever its clip_row. Returns N_tot = sum of out_len and fills row_map (may be NULL) for the packed rows 0 .. N_tot-1.
+ * Q2A_ERR_ARG, with nothing written, for a negative out_len or start, a range past n_rows, two non-empty ranges that
+ * overlap, out_len NULL with n_clips > 0, n_clips < 0, n_rows < 0 or N_tot > INT32_MAX. */
+int64_t q2a_feat_rows(const int32_t * out_len, const int32_t * clip_row, int n_clips, int64_t n_rows, int32_t * row_map);
+/* q2a_audio_features_device / _device_mel with dst and clip_row (host [n_clips], or NULL: packed) in place of feat_dev and
+ * rows_cap. p and dst are required. embd_dev (optional) still receives the packed f32 rows, against its own
+ * embd_rows_cap. Every check of the f32 calls, q2a_projector_apply_to's checks of dst and q2a_feat_rows' checks of the
+ * ranges (over the clips that are encoded) are made before anything is launched or written. The device row map is built
+ * inside the call by one small kernel from the call's single metadata upload (clip_row rides in it) and lives in p's
+ * workspace; with clip_row NULL there is no map and no extra launch. Reference activation contract only
+ * (Q2A_ERR_UNSUPPORTED otherwise). The host variants stay f32. */
+int q2a_audio_features_device_to(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                                 const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev, int64_t embd_rows_cap,
+                                 int32_t * out_len, int32_t * status, void * stream);
+int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                     const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                     const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev,
+                                     int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream);
 /* Test hook: the pool kernel of these calls alone, with the engine's final-LayerNorm weights, on caller rows.
  *   x_dev      packed [M_tot][n_audio_state] f32 (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx)
  *   embd_dev   [N_tot][n_audio_state] f32 (q2a_packed_out_rows over key_len), or NULL

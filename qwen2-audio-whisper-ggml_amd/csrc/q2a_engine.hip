@@ -892,14 +892,16 @@ inline hipStream_t call_stream(const void * stream) { return (hipStream_t) strea
 
 // The per-clip metadata of a call, on the device (e->meta) and pinned on the host (e->meta_host): five rows of the
 // call's B entries, then row_start with B + 1 entries (the packed layout of the variable-length encode) and out_start
-// with B + 1 entries (the packed output layout of the audio-feature calls, which alone upload it). clip_max is
-// written on the device (the mel kernel's running maximum); every other row comes from the host through upload_meta.
-constexpr size_t meta_words(int B) { return (size_t) B * 7 + 2; }
+// with B + 1 entries (the packed output layout of the audio-feature calls, which alone upload it), and behind that
+// (`end`, where the f32 audio-feature calls' copy stops) clip_row with B entries: the first destination row of every
+// clip, uploaded by the q2a_audio_features_device*_to calls alone. clip_max is written on the device (the mel kernel's
+// running maximum); every other row comes from the host through upload_meta.
+constexpr size_t meta_words(int B) { return (size_t) B * 8 + 2; }
 struct meta_rows {
-    int32_t *nsamp, *seek, *clip_ok, *clip_max, *key_len, *row_start, *out_start, *end;
+    int32_t *nsamp, *seek, *clip_ok, *clip_max, *key_len, *row_start, *out_start, *end, *clip_row, *end_to;
     meta_rows(int32_t * p, int B)
         : nsamp(p), seek(p + B), clip_ok(p + 2 * B), clip_max(p + 3 * B), key_len(p + 4 * B), row_start(p + 5 * B),
-          out_start(p + 6 * B + 1), end(p + meta_words(B)) {}
+          out_start(p + 6 * B + 1), end(p + 7 * B + 2), clip_row(end), end_to(p + meta_words(B)) {}
 };
 
 // The one writer of meta_host. It waits until the previous upload has left the pinned buffer (a queued copy may still
@@ -1375,6 +1377,10 @@ struct encode_call {
     float * feat;
     float * embd;               // NULL: not written
     int64_t rows_cap;
+    // the _to form: the features go to dst (f32 / fp16 / bf16 rows of the caller's, feat NULL), clip c's rows from row
+    // clip_row[c] on (host [B]; NULL: packed); rows_cap then bounds embd alone
+    const q2a_feat_dst * dst;
+    const int32_t * clip_row;
     frontend_src src() const { return {pcm, stride, mel, ld}; }
 };
 
@@ -1415,7 +1421,7 @@ int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStr
     rows = block_rows{B, B * e->d.T, e->X, kind == ENC_PLAIN ? nullptr : dev.key_len, nullptr, 0};
     max_frames = 0;
     const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start
-                      : c.features ? &meta_rows::end : &meta_rows::out_start;
+                      : !c.features ? &meta_rows::out_start : (c.dst && c.clip_row) ? &meta_rows::end_to : &meta_rows::end;
     return upload_meta(e, B, &meta_rows::nsamp, last, s, [&](const meta_rows & mh) -> int {
         if (c.mel && c.stride != 0 && c.stride < e->d.M * c.ld) { set_err("clip_stride %lld below n_mels * ld", (long long) c.stride); return Q2A_ERR_ARG; }
         for (int i = 0; i < B; ++i) {
@@ -1437,6 +1443,7 @@ int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStr
             // the clip_max row lies between clip_ok and the key lengths, inside the copy: it is device-written, and
             // run_frontend resets it after this copy on the same stream, to the value uploaded here
             if (kind != ENC_PLAIN) { mh.clip_max[i] = (int32_t) 0x80808080u; mh.key_len[i] = c.kl[i]; }
+            if (c.features && c.dst && c.clip_row) mh.clip_row[i] = c.clip_row[i];
         }
         if (kind != ENC_PACKED) return Q2A_OK;
         rows.X = e->Xp;
@@ -1545,18 +1552,20 @@ struct proj_operand {
     float * dy;
     q2a_half * aext;
     int ld;
+    int32_t * map;   // device row map [rows] of a _to call with clip_row (proj_workspace with_map), else NULL
 };
 // the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0 (q2a_ln_args' modes)
 int proj_mode(const q2a_projector * p) { return p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
 
 // grows the workspace (after everything queued on s: calls on one handle are ordered on one stream) and cuts it up
-int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o) {
+int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o, bool with_map = false) {
     const int K = p->d_in, blk = p->blk;
     const int64_t MP = (rows + 255) / 256 * 256;
     const size_t a_bytes = ((size_t) rows * K * 2 + 255) & ~size_t(255);
     const size_t dy_bytes = blk ? ((size_t) (K / blk) * MP * 4 + 255) & ~size_t(255) : 0;
     const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;   // (Q6_K: written by the quantizer, unread)
-    const size_t need = a_bytes + dy_bytes + ae_bytes;
+    const size_t map_bytes = with_map ? (size_t) MP * 4 : 0;
+    const size_t need = a_bytes + dy_bytes + ae_bytes + map_bytes;
     if (need > p->ws_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (p->ws) (void) hipFree(p->ws);
@@ -1568,6 +1577,7 @@ int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand 
     o.dy = (float *) ((char *) p->ws + a_bytes);
     o.aext = (q2a_half *) ((char *) p->ws + a_bytes + dy_bytes);
     o.ld = (int) MP;
+    o.map = with_map ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes) : nullptr;
     return Q2A_OK;
 }
 
@@ -1600,11 +1610,51 @@ q2a_gemm_args proj_gemm(const q2a_projector * p, int M, const proj_operand & o, 
     return a;
 }
 
+// y = the same GEMM with the row-map epilogue: row m of the operand to row row_map[m] (NULL: m) of dst, in dst's type
+q2a_gemm_args proj_gemm_to(const q2a_projector * p, int M, const proj_operand & o, const q2a_feat_dst & dst, const int32_t * row_map) {
+    q2a_gemm_args a = proj_gemm(p, M, o, nullptr);
+    a.out_rows = dst.base; a.out_ld = dst.ld; a.n_rows = (int) dst.n_rows; a.out_dt = dst.dtype; a.row_map = row_map;
+    return a;
+}
+
+// a feature destination against the projector's d_out (include/q2a_encoder.h, q2a_feat_dst)
+int feat_dst_check(const q2a_projector * p, const q2a_feat_dst * dst) {
+    if (!p || !dst) { set_err("feature destination: it goes with a projector, and both are required"); return Q2A_ERR_ARG; }
+    const int es = dst->dtype == Q2A_DT_F32 ? 4 : (dst->dtype == Q2A_DT_F16 || dst->dtype == Q2A_DT_BF16) ? 2 : 0;
+    if (!es || dst->reserved != 0) { set_err("feature destination: dtype %d, reserved %d", dst->dtype, dst->reserved); return Q2A_ERR_ARG; }
+    if (!dst->base || ((uintptr_t) dst->base & 15)) { set_err("feature destination: base must be 16-byte aligned"); return Q2A_ERR_ARG; }
+    if (dst->ld < p->d_out || (dst->ld * es) % 16 != 0) {
+        set_err("feature destination: ld %lld with d_out %d (ld * %d bytes must be a multiple of 16)", (long long) dst->ld, p->d_out, es);
+        return Q2A_ERR_ARG;
+    }
+    if (dst->n_rows < 0 || dst->n_rows > INT32_MAX) { set_err("feature destination: n_rows %lld", (long long) dst->n_rows); return Q2A_ERR_ARG; }
+    return Q2A_OK;
+}
+
+// map[n] = clip_row[c] + (n - out_start[c]) for the packed output rows n of clip c: the device row map of a _to call,
+// from the rows of the call's one metadata upload
+__global__ void k_feat_row_map(const int32_t * out_start, const int32_t * clip_row, int32_t * map) {
+    const int c = blockIdx.y, n0 = out_start[c], len = out_start[c + 1] - n0;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j < len) map[n0 + j] = clip_row[c] + j;
+}
+hipError_t launch_feat_row_map(const int32_t * out_start, const int32_t * clip_row, int32_t * map, int B, int max_len, hipStream_t s) {
+    if (B <= 0 || max_len <= 0 || !map) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_feat_row_map, dim3((unsigned) ((max_len + 255) / 256), (unsigned) B), dim3(256), 0, s, out_start, clip_row, map);
+    return hipGetLastError();
+}
+
 // the checks of the audio-feature tail, made before anything is launched or written: the outputs, the projector, and the
-// packed rows against rows_cap (the clips the too-short rule skips have none)
+// packed rows against rows_cap (the clips the too-short rule skips have none); for the _to form the destination and
+// q2a_feat_rows' checks of the clips' ranges in it, rows_cap then bounding embd alone
 int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
-    if (!c.feat && !c.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
-    if (c.proj ? !c.feat : c.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
+    if (c.dst) {
+        if (c.feat) { set_err("audio features: feat and dst exclude each other"); return Q2A_ERR_ARG; }
+        if (int rc = feat_dst_check(c.proj, c.dst)) return rc;
+    } else {
+        if (!c.feat && !c.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
+        if (c.proj ? !c.feat : c.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
+    }
     if (c.proj && (c.proj->device != e->device || c.proj->d_in != e->d.D)) {
         set_err("audio features: projector on device %d with d_in %d, engine on device %d with n_audio_state %d", c.proj->device,
                 c.proj->d_in, e->device, e->d.D);
@@ -1613,6 +1663,17 @@ int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
     int64_t n_tot = 0;
     for (int i = 0; i < c.B; ++i) {
         if (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) n_tot += c.kl[i] / 2;
+    }
+    if (c.dst) {
+        std::vector<int32_t> ol(c.B);
+        for (int i = 0; i < c.B; ++i)
+            ol[i] = (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) ? c.kl[i] / 2 : 0;
+        if (q2a_feat_rows(ol.data(), c.clip_row, c.B, c.dst->n_rows, nullptr) < 0) {
+            set_err("audio features: a clip's destination rows start below 0, end past n_rows %lld, or overlap another clip's",
+                    (long long) c.dst->n_rows);
+            return Q2A_ERR_ARG;
+        }
+        if (!c.embd) return Q2A_OK;
     }
     if (n_tot > c.rows_cap) { set_err("audio features: %lld output rows, rows_cap %lld", (long long) n_tot, (long long) c.rows_cap); return Q2A_ERR_ARG; }
     return Q2A_OK;
@@ -1648,7 +1709,7 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
     // the projector's operand buffers, before the first launch (growing them waits for the stream)
     proj_operand po{nullptr, nullptr, nullptr, 0};
-    if (feats && c.proj && rows.N_out > 0 && (rc = proj_workspace(c.proj, rows.N_out, s, po))) return rc;
+    if (feats && c.proj && rows.N_out > 0 && (rc = proj_workspace(c.proj, rows.N_out, s, po, c.dst && c.clip_row))) return rc;
     // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros. The
     // audio-feature tail writes valid rows only: without any, nothing is launched behind the metadata)
     if (feats ? rows.N_out > 0 : kind != ENC_PACKED || rows.M > 0) {
@@ -1666,7 +1727,14 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         q2a_pool_pack_args pa{e->Xp, B, d.D, rows.N_out, lnw, lnb, dev.row_start, dev.out_start, c.embd,
                               c.proj ? proj_mode(c.proj) : -1, po.A, po.dy, po.aext, po.ld};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_pack(pa, s));
-        if (c.proj) LAUNCH(q2a_launch_gemm(proj_gemm(c.proj, rows.N_out, po, c.feat), Q2A_EPI_STORE_F, c.proj->gblk, s));
+        if (c.dst) {
+            // the _to form: the device row map from the uploaded out_start and clip_row (none when packed), then the
+            // same GEMM with the row-map epilogue straight into the caller's rows
+            if (po.map) PLAUNCH(e, s, Q2A_PROF_POOL, launch_feat_row_map(dev.out_start, dev.clip_row, po.map, B, d.TO, s));
+            LAUNCH(q2a_launch_gemm(proj_gemm_to(c.proj, rows.N_out, po, *c.dst, po.map), Q2A_EPI_STORE_ROWS, c.proj->gblk, s));
+        } else if (c.proj) {
+            LAUNCH(q2a_launch_gemm(proj_gemm(c.proj, rows.N_out, po, c.feat), Q2A_EPI_STORE_F, c.proj->gblk, s));
+        }
     } else if (kind == ENC_PACKED) {
         q2a_pool_varlen_args pa{e->Xp, B, d.T, d.D, lnw, lnb, c.out, dev.key_len, dev.row_start};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
@@ -2089,6 +2157,42 @@ int q2a_audio_features_device_mel(q2a_engine * e, q2a_projector * p, const float
     if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     const encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
     return encode(e, ENC_PACKED, features_call(c, p, feat_dev, embd_dev, rows_cap), call_stream(stream));
+}
+
+// the _to form: dst and clip_row in place of feat and rows_cap; the projector and the destination are both required
+// (without dst the call would be the f32 one's "embd alone")
+static int features_to_check(const q2a_projector * p, const q2a_feat_dst * dst) {
+    if (p && dst) return Q2A_OK;
+    set_err("audio features: the _to calls need a projector and a destination");
+    return Q2A_ERR_ARG;
+}
+
+int q2a_audio_features_device_to(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                                 const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev, int64_t embd_rows_cap,
+                                 int32_t * out_len, int32_t * status, void * stream) {
+    std::vector<int32_t> kl;
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    if (int rc = features_to_check(p, dst)) return rc;
+    encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
+    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
+    c.dst = dst; c.clip_row = clip_row;
+    return encode(e, ENC_PACKED, c, call_stream(stream));
+}
+
+int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                     const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                     const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev,
+                                     int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = features_to_check(p, dst)) return rc;
+    encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
+    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
+    c.dst = dst; c.clip_row = clip_row;
+    return encode(e, ENC_PACKED, c, call_stream(stream));
 }
 
 // The host variants, plain: chunks of up to 64 clips, each staged into device buffers of its own, run through the device
@@ -2601,7 +2705,9 @@ q2a_projector * q2a_projector_open(const char * path, int device) {
     };
     if (!wt || !bt || wt->n_dims != 2 || bt->type != Q2A_TYPE_F32 || bt->ne[0] != wt->ne[1]) return fail(Q2A_ERR_FORMAT, "missing or malformed tensors");
     const int K = (int) wt->ne[0], N = (int) wt->ne[1];
-    if (N % 128 != 0 || K % 256 != 0) return fail(Q2A_ERR_UNSUPPORTED, "d_out must be a multiple of 128, d_in of 256");
+    // (F16 weights: whole 64-deep K-steps suffice — an odd count takes the 256x256 tiles without the 8-phase pipeline)
+    if (N % 128 != 0 || K % (wt->type == Q2A_TYPE_F16 ? 64 : 256) != 0)
+        return fail(Q2A_ERR_UNSUPPORTED, "d_out must be a multiple of 128, d_in of 256 (F16 weights: of 64)");
     std::vector<uint8_t> packed;
     uint64_t off[A_COUNT];
     if (q2a_pack_linear(mf->data + wt->offset, wt->type, N, K, packed, off) != Q2A_OK)
@@ -2666,6 +2772,41 @@ int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float 
     }
     LAUNCH(q2a_launch_gemm(proj_gemm(p, M, o, y), Q2A_EPI_STORE_F, p->gblk, s));
     return Q2A_OK;
+}
+
+int q2a_projector_apply_to(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const int32_t * row_map,
+                           void * stream) {
+    if (!p || !x || !dst || rows <= 0 || rows > (1 << 30) / 4) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = feat_dst_check(p, dst)) return rc;
+    if (!row_map && rows > dst->n_rows) { set_err("feature destination: %lld rows into n_rows %lld", (long long) rows, (long long) dst->n_rows); return Q2A_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = call_stream(stream);
+    const int M = (int) rows, K = p->d_in;
+    proj_operand o;
+    if (int rc = proj_workspace(p, rows, s, o)) return rc;
+    if (p->blk == 0) {
+        const int64_t n = (int64_t) M * K;
+        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
+        LAUNCH(hipGetLastError());
+    } else {
+        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
+        LAUNCH(q2a_launch_quant_act(qa, s));
+    }
+    LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, row_map), Q2A_EPI_STORE_ROWS, p->gblk, s));
+    return Q2A_OK;
+}
+
+int q2a_projector_regime(q2a_projector * p, int64_t rows) {
+    if (!p || rows <= 0 || rows > (1 << 30) / 4) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    HIP_TRY(hipSetDevice(p->device));
+    // the plan reads shapes, strides and which scale arrays exist, never memory: the operand pointers need no workspace,
+    // only to be non-NULL like a call's
+    proj_operand o{(q2a_half *) p->wdev, (float *) p->wdev, (q2a_half *) p->wdev, (int) ((rows + 255) / 256 * 256), nullptr};
+    const q2a_gemm_args a = proj_gemm(p, (int) rows, o, nullptr);
+    const int rf = q2a_gemm_plan_for(a, Q2A_EPI_STORE_F, p->gblk).regime;
+    const int rt = q2a_gemm_plan_for(a, Q2A_EPI_STORE_ROWS, p->gblk).regime;
+    if (rf != rt) { set_err("projector regime: the f32 call takes %d, the row-map call %d", rf, rt); return Q2A_ERR_HIP; }
+    return rf;
 }
 
 }  // extern "C"

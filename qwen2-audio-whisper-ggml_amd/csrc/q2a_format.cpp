@@ -162,6 +162,37 @@ extern "C" int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int
     return rows;
 }
 
+// the destination rows of the audio-feature _to calls (include/q2a_encoder.h); here for the same reason
+extern "C" int64_t q2a_feat_rows(const int32_t * out_len, const int32_t * clip_row, int n_clips, int64_t n_rows, int32_t * row_map) {
+    if (n_clips < 0 || (n_clips > 0 && !out_len) || n_rows < 0) return Q2A_ERR_ARG;
+    // (everything checked first: nothing is written on an error)
+    int64_t n_tot = 0;
+    std::vector<std::pair<int64_t, int64_t>> runs;   // non-empty [start, end)
+    for (int c = 0; c < n_clips; ++c) {
+        if (out_len[c] < 0) return Q2A_ERR_ARG;
+        if (out_len[c] == 0) continue;
+        const int64_t start = clip_row ? (int64_t) clip_row[c] : n_tot;
+        if (start < 0 || start + out_len[c] > n_rows || start + out_len[c] > INT32_MAX) return Q2A_ERR_ARG;
+        runs.emplace_back(start, start + out_len[c]);
+        n_tot += out_len[c];
+    }
+    if (n_tot > INT32_MAX) return Q2A_ERR_ARG;
+    if (clip_row) {
+        std::sort(runs.begin(), runs.end());
+        for (size_t i = 1; i < runs.size(); ++i)
+            if (runs[i].first < runs[i - 1].second) return Q2A_ERR_ARG;
+    }
+    if (row_map) {
+        int64_t m = 0;
+        for (int c = 0; c < n_clips; ++c) {
+            const int64_t start = clip_row ? (int64_t) clip_row[c] : m;
+            for (int32_t j = 0; j < out_len[c]; ++j) row_map[m + j] = (int32_t) (start + j);
+            m += out_len[c];
+        }
+    }
+    return n_tot;
+}
+
 static double hz_to_mel_slaney(double f) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
     const double logstep = std::log(6.4) / 27.0;

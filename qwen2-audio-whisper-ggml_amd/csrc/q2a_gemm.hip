@@ -1420,7 +1420,78 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
         b = make_uint4(rb[0], rb[1], rb[2], rb[3]);
     };
     const int pcol = 16 * (q & 1) + 8 * (q >> 1);    // column of this lane's 16-B piece within a 32-column pair
-    if (PIPE == 1 && (EPI == Q2A_EPI_PRE_H || (EPI == Q2A_EPI_QKV && (part < 2 || p.v_rows)))) {
+    if constexpr (EPI == Q2A_EPI_STORE_ROWS) {
+        // fl32(acc + bias) — STORE_F's value with store_bias — as f32, fp16 or bf16 (p.out_dt, wave-uniform: one scalar
+        // branch per tile, so the twelve tile instantiations serve the three types) into destination row
+        // row_map[m] (NULL: m) of out_rows, rows outside [0, n_rows) dropped. Whole 128-B lines per store, as the
+        // branches below: after line_pair a lane stores rows 16i + (l & 7) and 16i + 8 + (l & 7), so those two row
+        // indices are what it reads, once per 16-row block and for all column tiles, before the first value is formed.
+        int drow[MI][2];
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                const int m = rbase + i * 16 + 8 * hf + (l16 & 7);
+                int r = -1;
+                if (m < p.M) r = p.row_map ? p.row_map[m] : m;
+                drow[i][hf] = (r >= 0 && r < p.n_rows) ? r : -1;
+            }
+        // (rounded to f32 before any 16-bit conversion: the 16-bit output is the conversion of the f32 output)
+        auto rval = [&](int i, int j, int r) -> float {
+#pragma clang fp contract(off)
+            float v = acc[i][j][r] + bias4[j][r];
+            asm volatile("" : "+v"(v));
+            return v;
+        };
+        if (p.out_dt == Q2A_DT_F32) {
+            float * dst = (float *) p.out_rows;
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                f4 v[NJ];
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[j][r] = rval(i, j, r);
+#pragma unroll
+                for (int jp = 0; jp < NJ / 2; ++jp) {
+                    uint4 a, b;
+                    line_pair(__builtin_bit_cast(uint4, v[2 * jp]), __builtin_bit_cast(uint4, v[2 * jp + 1]), a, b);
+                    const int col = cbase + 4 * q + 16 * (2 * jp + hi8);
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf)
+                        if (drow[i][hf] >= 0 && Q2A_ST) q2a_st(hf ? b : a, (uint4 *) (dst + (int64_t) drow[i][hf] * p.out_ld + col));
+                }
+            }
+        } else {
+            // 64 columns of 2 bytes = one line per row: pair16 + line_pair, 16 B per lane, 8 rows x 128 B per store
+            q2a_half * dst = (q2a_half *) p.out_rows;
+            auto rows16 = [&](auto bfc) {
+                constexpr bool OBF = decltype(bfc)::value;
+#pragma unroll
+                for (int i = 0; i < MI; ++i) {
+                    uint4 hvj[2];
+#pragma unroll
+                    for (int jp = 0; jp < NJ / 2; ++jp) {
+                        h4v ha, hb;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            ha[r] = to16<OBF>(rval(i, 2 * jp, r));
+                            hb[r] = to16<OBF>(rval(i, 2 * jp + 1, r));
+                        }
+                        hvj[jp] = pair16(ha, hb);
+                    }
+                    uint4 hA, hB;
+                    line_pair(hvj[0], hvj[1], hA, hB);
+                    const int col = cbase + pcol + 32 * hi8;
+#pragma unroll
+                    for (int hf = 0; hf < 2; ++hf)
+                        if (drow[i][hf] >= 0 && Q2A_ST) q2a_st(hf ? hB : hA, (uint4 *) (dst + (int64_t) drow[i][hf] * p.out_ld + col));
+                }
+            };
+            if (p.out_dt == Q2A_DT_BF16) rows16(std::true_type{});
+            else rows16(std::false_type{});
+        }
+    } else if (PIPE == 1 && (EPI == Q2A_EPI_PRE_H || (EPI == Q2A_EPI_QKV && (part < 2 || p.v_rows)))) {
       if constexpr (PIPE == 1 && (EPI == Q2A_EPI_PRE_H || EPI == Q2A_EPI_QKV)) {
         // fp16 outputs of the 8-phase tile (fc1's pre-activation; Q / K hi and lo), staged through LDS so every store
         // instruction writes two WHOLE 512-B output rows: all 8 waves write the tile [256 rows][256 cols] into the idle
@@ -1919,6 +1990,12 @@ q2a_gemm_plan pipe8_plan(const q2a_gemm_args & a, int epi, int blk, int cus) {
 // launch_epi / launch_pipe8 below act on it and q2a_test_gemm_regime reports it. Q2A_REGIME_NONE = no kernel exists.
 q2a_gemm_plan q2a_gemm_plan_of(const q2a_gemm_args & a, int epi, int blk, int cus) {
     const q2a_gemm_plan none{Q2A_REGIME_NONE, 0, 0};
+    if (epi == Q2A_EPI_STORE_ROWS) {
+        // STORE_F's decision for the same arguments (the K order and the accumulators are then STORE_F's), in the weight
+        // modes a projector has; never split, never grouped
+        if (!(blk == 0 || blk == 256 || blk == 32 || blk == Q2A_BLK_Q6K) || a.ksplit > 1 || a.ngroup == 2) return none;
+        epi = Q2A_EPI_STORE_F;
+    }
     const bool big = wide_tiles(a.M, a.N);
     const bool p8 = pipe8_ok(a, blk) && (blk != 256 || a.beta);
     if (epi == Q2A_EPI_GELU_Q8K) {
@@ -2004,7 +2081,7 @@ hipError_t launch_epi(const q2a_gemm_args & a, int blk, hipStream_t s) {
             return small ? launch_cfg<128, 128, 2, 2, EPI, 32>(a, s) : launch_cfg<128, 256, 2, 4, EPI, 32>(a, s);
         }
         if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_PRE_H ||
-                      EPI == Q2A_EPI_STORE_F) {
+                      EPI == Q2A_EPI_STORE_F || EPI == Q2A_EPI_STORE_ROWS) {
             if (blk == Q2A_BLK_Q6K) return launch_cfg<128, 128, 2, 2, EPI, Q2A_BLK_Q6K>(a, s);
         }
         if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_STORE_F) {
@@ -2076,6 +2153,12 @@ hipError_t q2a_launch_gemm(const q2a_gemm_args & a_in, int epi, int blk, hipStre
         case Q2A_EPI_STORE_F: return launch_epi<Q2A_EPI_STORE_F>(a, blk, s);
         case Q2A_EPI_GELU_Q8K: return launch_epi<Q2A_EPI_GELU_Q8K>(a, blk, s);
         case Q2A_EPI_PRE_H: return launch_epi<Q2A_EPI_PRE_H>(a, blk, s);
+        case Q2A_EPI_STORE_ROWS:
+            if (!a.out_rows || ((uintptr_t) a.out_rows & 15) || a.out_ld < a.N || a.n_rows < 0 || !a.bias ||
+                !(a.out_dt == Q2A_DT_F32 || a.out_dt == Q2A_DT_F16 || a.out_dt == Q2A_DT_BF16) ||
+                (a.out_ld * (a.out_dt == Q2A_DT_F32 ? 4 : 2)) % 16 != 0)
+                return hipErrorInvalidValue;
+            return launch_epi<Q2A_EPI_STORE_ROWS>(a, blk, s);
         default: return hipErrorInvalidValue;
     }
 }

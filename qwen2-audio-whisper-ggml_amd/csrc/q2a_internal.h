@@ -34,6 +34,9 @@ enum q2a_epi {
                             // ggml's x >= 10 branch returns the f32 x; here (and in GELU_H + quantizer, and in the
                             // 8-phase GELU_Q8K epilogue) it reaches the quantizer as fp16(x): a stated deviation,
                             // pinned and measured in tests/test_gpu_operands.py
+    Q2A_EPI_STORE_ROWS = 8, // out_rows[row(m)][n] = dt(fl32(acc + bias[n])), row(m) = row_map ? row_map[m] : m, dt f32 /
+                            // fp16 / bf16 (out_dt); rows outside [0, n_rows) are not stored (the projector's feature
+                            // output into the caller's rows; the regimes and the K order are STORE_F's, no split, no group)
 };
 
 // compact GELU table: entries for fp16 bits 0x0000..0x4900 (+0..+10) then 0x8000..0xC900 (-0..-10), padded to
@@ -114,6 +117,13 @@ struct q2a_gemm_args {
     int v_rows;                       // Q2A_EPI_QKV: 1 = V hi / lo row-major [M][D] into vt / vtl (like Q and K; the engine's
                                       //   reference contract), 0 = V^T [clip][head][64][TP] (bf16 contract, ggml backend)
     int m_base;                       // first output row of the launch (tiles cover rows [m_base, M)); set by the launcher
+    // Q2A_EPI_STORE_ROWS alone (no other epilogue reads these): element (row(m), n) at out_rows + (row(m) * out_ld + n) *
+    // element size, row(m) = row_map ? row_map[m] : m; a row outside [0, n_rows) is skipped
+    void * out_rows;                  // 16-byte aligned
+    int64_t out_ld;                   // elements between destination rows, >= N; out_ld * element size % 16 == 0
+    const int32_t * row_map;          // device [M], or NULL: the identity
+    int n_rows;                       // rows the destination holds
+    int out_dt;                       // Q2A_DT_F32 / Q2A_DT_F16 / Q2A_DT_BF16 (include/q2a_encoder.h)
 };
 
 // the launcher's split factor for a small-tile Q2A_EPI_RESID GEMM (0 = none): a function of K only, so every batch

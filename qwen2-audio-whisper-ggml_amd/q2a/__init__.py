@@ -32,6 +32,8 @@ EXPORTS = (
     "whisper_set_mel", "whisper_set_mel_with_state",
     "q2a_packed_out_rows", "q2a_audio_features_device", "q2a_audio_features_device_mel", "q2a_audio_features_host",
     "q2a_audio_features_host_mel", "q2a_test_pool_operand",
+    "q2a_feat_rows", "q2a_projector_apply_to", "q2a_projector_regime", "q2a_audio_features_device_to",
+    "q2a_audio_features_device_mel_to",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -65,6 +67,18 @@ _KINDS = {"plain": ENCODE_PLAIN, "padded": ENCODE_PADDED, "varlen": ENCODE_VARLE
 # activation contracts (include/q2a_encoder.h)
 ACT_REFERENCE = 0
 ACT_BF16 = 1
+
+# element types of a feature destination (include/q2a_encoder.h, q2a_feat_dst)
+DT_F32, DT_F16, DT_BF16 = 0, 1, 2
+
+
+class FeatDst(C.Structure):
+    """q2a_feat_dst: rows of the caller's on the device that the q2a_*_to calls store features into."""
+    _fields_ = [("base", C.c_void_p), ("ld", C.c_int64), ("n_rows", C.c_int64), ("dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+def feat_dst(base_ptr: int, ld: int, n_rows: int, dtype: int) -> FeatDst:
+    return FeatDst(C.c_void_p(base_ptr) if base_ptr else None, ld, n_rows, dtype, 0)
 
 
 _lib = None
@@ -162,6 +176,16 @@ def lib() -> C.CDLL:
             L.q2a_audio_features_host_mel.argtypes = [vp, vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, vp, C.c_int64, i32p,
                                                       i32p]
             L.q2a_test_pool_operand.argtypes = [vp, C.c_int, vp, C.c_int, i32p, vp, vp, vp, vp, C.c_int, vp]
+        if hasattr(L, "q2a_audio_features_device_to"):   # 16-bit / in-place feature output (optional like the hooks above)
+            dstp = C.POINTER(FeatDst)
+            L.q2a_feat_rows.restype = C.c_int64
+            L.q2a_feat_rows.argtypes = [i32p, i32p, C.c_int, C.c_int64, i32p]
+            L.q2a_projector_apply_to.argtypes = [vp, vp, C.c_int64, dstp, vp, vp]
+            L.q2a_projector_regime.argtypes = [vp, C.c_int64]
+            L.q2a_audio_features_device_to.argtypes = [vp, vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, dstp, i32p, vp,
+                                                       C.c_int64, i32p, i32p, vp]
+            L.q2a_audio_features_device_mel_to.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, dstp,
+                                                           i32p, vp, C.c_int64, i32p, i32p, vp]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -436,6 +460,48 @@ class Engine:
                                                    st.ctypes.data_as(i32p), p(stream)))
         return ol, st
 
+    def audio_features_device_to(self, pcm_ptr: int, pcm_stride: int, n_samples, dst: FeatDst, projector, clip_rows=None,
+                                 embd_ptr: int = 0, embd_rows_cap: int = 0, offsets_ms=None, key_len=None,
+                                 stream: int | None = None):
+        """q2a_audio_features_device_to: audio_features_device with the features stored as dst's type into dst's rows,
+        clip c's out_len[c] rows from row clip_rows[c] on (None: packed); embd_ptr [embd_rows_cap][n_audio_state] still
+        receives the packed f32 rows (0: not written). Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        n = len(ns)
+        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        _cr, crp = self._i32(clip_rows, n, "clip_rows")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_audio_features_device_to(self.h, projector.h if projector is not None else None, p(pcm_ptr),
+                                                  C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n,
+                                                  C.byref(dst) if dst is not None else None, crp, p(embd_ptr),
+                                                  C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
+                                                  p(stream)))
+        return ol, st
+
+    def audio_features_device_mel_to(self, mel_ptr: int, clip_stride: int, ld: int, n_len, dst: FeatDst, projector,
+                                     clip_rows=None, embd_ptr: int = 0, embd_rows_cap: int = 0, seek=None, key_len=None,
+                                     stream: int | None = None):
+        """q2a_audio_features_device_mel_to: audio_features_device_mel's inputs, audio_features_device_to's outputs."""
+        i32p = C.POINTER(C.c_int32)
+        nl = np.ascontiguousarray(n_len, dtype=np.int32)
+        n = len(nl)
+        _sk, skp = self._i32(seek, n, "seek")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        _cr, crp = self._i32(clip_rows, n, "clip_rows")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_audio_features_device_mel_to(self.h, projector.h if projector is not None else None, p(mel_ptr),
+                                                      C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp,
+                                                      n, C.byref(dst) if dst is not None else None, crp, p(embd_ptr),
+                                                      C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p),
+                                                      st.ctypes.data_as(i32p), p(stream)))
+        return ol, st
+
     def _features_host(self, fn, ptrs, lens, n, second, key_len, projector, embd, rows_cap, raise_on_error):
         i32p = C.POINTER(C.c_int32)
         _kl, klp = self._i32(key_len, n, "key_len")
@@ -481,13 +547,22 @@ class Engine:
         return self._features_host(lib().q2a_audio_features_host_mel, ptrs, nl, n, skp, key_len, projector, embd, rows_cap,
                                    raise_on_error)
 
-    def audio_features(self, input_features, feature_attention_mask=None, projector=None, return_embd: bool = False):
+    def audio_features(self, input_features, feature_attention_mask=None, projector=None, return_embd: bool = False,
+                       out=None, clip_rows=None):
         """What Qwen2AudioForConditionalGeneration scatters into the text embeddings, from what its processor hands the
         model: input_features [B][n_mels][L] f32 (a torch CUDA tensor: device entry point on torch's current stream, the
         results tensors on that device; or a numpy array: host entry point) and optionally feature_attention_mask [B][L]
         — encode_features' argument handling. Returns (features [N_tot][d_out], out_len [B]): the projector applied to
         the valid rows of embd_enc alone, clip c's out_len[c] rows at the prefix sum of out_len; with return_embd also
-        the packed embd_enc [N_tot][n_audio_state]. projector=None (return_embd required): features is None."""
+        the packed embd_enc [N_tot][n_audio_state]. projector=None (return_embd required): features is None.
+        out: a contiguous CUDA tensor [rows][d_out] or [B][S][d_out] (viewed as rows) of float32, float16 or bfloat16 —
+        inputs_embeds. The features are then written into it (q2a_audio_features_device_mel_to, on torch's current
+        stream), clip c's rows from flat row clip_rows[c] on (audio_token_runs' starts; None: packed from row 0), and
+        out is returned in place of the packed features. input_features must be a CUDA tensor on out's device."""
+        if out is not None:
+            return self._audio_features_into(input_features, feature_attention_mask, projector, return_embd, out, clip_rows)
+        if clip_rows is not None:
+            raise ValueError("audio_features: clip_rows goes with out")
         if projector is None and not return_embd:
             raise ValueError("audio_features: a projector, or return_embd=True")
         shape = tuple(input_features.shape)
@@ -521,6 +596,43 @@ class Engine:
             feat, emb, ol, _ = self.audio_features_host_mel(list(x), projector=projector, key_len=kl, embd=return_embd,
                                                             rows_cap=n_tot)
         return (feat, ol, emb) if return_embd else (feat, ol)
+
+    def _audio_features_into(self, input_features, feature_attention_mask, projector, return_embd, out, clip_rows):
+        import torch
+        if projector is None:
+            raise ValueError("audio_features: out needs a projector")
+        dts = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
+        if not (hasattr(out, "is_cuda") and out.is_cuda and out.is_contiguous() and out.dtype in dts and out.dim() in (2, 3)
+                and out.shape[-1] == projector.d_out):
+            raise ValueError(f"out: a contiguous CUDA tensor [rows][{projector.d_out}] or [B][S][{projector.d_out}] of "
+                             "float32, float16 or bfloat16")
+        x = input_features
+        if not (hasattr(x, "is_cuda") and x.is_cuda and x.dtype == torch.float32 and x.device == out.device):
+            raise ValueError("input_features: a float32 CUDA tensor on out's device")
+        shape = tuple(x.shape)
+        if len(shape) != 3 or shape[1] != self.info.n_mels:
+            raise ValueError(f"input_features must be [B][{self.info.n_mels}][L]")
+        B, _, L = shape
+        if feature_attention_mask is not None:
+            m = feature_attention_mask
+            m = m.detach().cpu().numpy() if hasattr(m, "detach") else np.asarray(m)
+            if m.shape != (B, L):
+                raise ValueError(f"feature_attention_mask must be [{B}][{L}]")
+            kl = features_key_len(m.astype(np.int64).sum(-1))
+        else:
+            kl = np.full(B, mel_valid_lengths(L, 0, self.info.n_audio_ctx)[0], dtype=np.int32)
+        n_tot, _ = packed_out_rows(kl, self.info.n_audio_ctx)
+        n_rows = out.numel() // projector.d_out
+        x = x.contiguous()
+        emb = torch.empty((n_tot, self.info.n_audio_state), dtype=torch.float32, device=x.device) if return_embd else None
+        ol = np.zeros(B, dtype=np.int32)
+        if n_tot:
+            dst = feat_dst(out.data_ptr(), projector.d_out, n_rows, dts[out.dtype])
+            ol, _ = self.audio_features_device_mel_to(x.data_ptr(), self.info.n_mels * L, L, [L] * B, dst, projector,
+                                                      clip_rows=clip_rows, embd_ptr=emb.data_ptr() if emb is not None else 0,
+                                                      embd_rows_cap=n_tot, key_len=kl,
+                                                      stream=torch.cuda.current_stream(x.device).cuda_stream)
+        return (out, ol, emb) if return_embd else (out, ol)
 
     def test_pool_operand(self, mode, x_ptr, n_clips, key_len, embd_ptr=0, codes_ptr=0, dy_ptr=0, aext_ptr=0, ld=0, stream=None):
         """q2a_test_pool_operand: the audio-feature calls' pool kernel alone on packed caller rows x [M_tot][D] ->
@@ -636,6 +748,8 @@ def _host() -> C.CDLL:
         _host_lib.q2a_varlen_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
         _host_lib.q2a_packed_out_rows.restype = C.c_int64
         _host_lib.q2a_packed_out_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        _host_lib.q2a_feat_rows.restype = C.c_int64
+        _host_lib.q2a_feat_rows.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.POINTER(C.c_int32)]
     return _host_lib
 
 
@@ -667,6 +781,47 @@ def packed_out_rows(key_len, n_audio_ctx: int = 1500) -> tuple[int, np.ndarray]:
         err.rc = int(n)
         raise err
     return int(n), os_
+
+
+def feat_rows(out_len, clip_rows, n_rows: int, row_map: np.ndarray | None = None) -> tuple[int, np.ndarray]:
+    """(N_tot, row_map): the destination rows of the audio-feature _to calls (q2a_feat_rows) — packed row m of the call
+    goes to row row_map[m]; clip c's out_len[c] rows are rows clip_rows[c] .. of a destination of n_rows rows
+    (clip_rows None: packed from row 0; a clip with no rows is ignored). Raises Q2AError (rc -4) for a negative start, a
+    range past n_rows or two non-empty ranges that overlap, and then writes nothing into row_map (an int32 array of at
+    least N_tot entries to fill; None: a new one). Host arithmetic through lib/libq2a_host.so: needs no GPU."""
+    ol = np.ascontiguousarray(out_len, dtype=np.int32).reshape(-1)
+    cr = None if clip_rows is None else np.ascontiguousarray(clip_rows, dtype=np.int32).reshape(-1)
+    if cr is not None and len(cr) != len(ol):
+        raise ValueError("clip_rows: one entry per clip")
+    if row_map is None:
+        row_map = np.zeros(int(np.maximum(ol, 0).sum()), dtype=np.int32)
+    elif row_map.dtype != np.int32 or not row_map.flags.c_contiguous or row_map.size < int(np.maximum(ol, 0).sum()):
+        raise ValueError("row_map: a contiguous int32 array of at least sum(out_len) entries")
+    i32p = C.POINTER(C.c_int32)
+    n = _host().q2a_feat_rows(ol.ctypes.data_as(i32p), cr.ctypes.data_as(i32p) if cr is not None else None, len(ol),
+                              C.c_int64(n_rows), row_map.ctypes.data_as(i32p))
+    if n < 0:
+        err = Q2AError(f"q2a error {n}: invalid arguments to q2a_feat_rows")
+        err.rc = int(n)
+        raise err
+    return int(n), row_map
+
+
+def audio_token_runs(input_ids, audio_token_id: int) -> tuple[np.ndarray, np.ndarray]:
+    """(starts, lengths) of every maximal run of audio_token_id in input_ids [B][S] (numpy, host only), in row-major
+    order: starts are flat rows b * S + s of inputs_embeds viewed as [B * S][d], a run never crosses a sequence's end.
+    The starts are the clip_rows of Engine.audio_features(..., out=inputs_embeds) once the lengths have been checked
+    against out_len — the processor emits one run of out_len[c] audio tokens per clip."""
+    ids = np.asarray(input_ids)
+    if ids.ndim != 2:
+        raise ValueError("input_ids must be [B][S]")
+    B, S = ids.shape
+    hit = np.zeros((B, S + 2), dtype=np.int8)
+    hit[:, 1:-1] = ids == audio_token_id
+    d = np.diff(hit, axis=1)          # +1 where a run starts (at s), -1 one past its end
+    b0, s0 = np.nonzero(d == 1)
+    _, s1 = np.nonzero(d == -1)
+    return (b0 * S + s0).astype(np.int64), (s1 - s0).astype(np.int64)
 
 
 def valid_lengths(n_samples: int, offset_ms: int = 0, n_audio_ctx: int = 1500) -> tuple[int, int]:
@@ -780,6 +935,20 @@ class Projector:
     def apply(self, x_ptr: int, rows: int, y_ptr: int, stream=None):
         _check(lib().q2a_projector_apply(self.h, C.c_void_p(x_ptr), rows, C.c_void_p(y_ptr),
                                          C.c_void_p(stream) if stream else None))
+
+    def apply_to(self, x_ptr: int, rows: int, dst: FeatDst, row_map_ptr: int = 0, stream=None):
+        """q2a_projector_apply_to: apply's values as dst's type, packed row m stored at row row_map[m] of dst
+        (row_map_ptr: device int32 [rows]; 0: the identity)."""
+        _check(lib().q2a_projector_apply_to(self.h, C.c_void_p(x_ptr), rows, C.byref(dst) if dst is not None else None,
+                                            C.c_void_p(row_map_ptr) if row_map_ptr else None,
+                                            C.c_void_p(stream) if stream else None))
+
+    def regime(self, rows: int) -> int:
+        """q2a_projector_regime: the REGIME_* the projector's GEMM takes at `rows` rows (nothing is launched)."""
+        r = lib().q2a_projector_regime(self.h, rows)
+        if r < 0:
+            _check(r)
+        return r
 
     def close(self):
         if self.h:
