@@ -483,6 +483,69 @@ int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const fl
                                      const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
                                      const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev,
                                      int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream);
+/* ---- inputs_embeds on the device: the audio rows placed by input_ids, the text rows gathered ----------------------------
+ * The model does inputs_embeds = embed_tokens(input_ids), then masked_scatter(input_ids == audio_token_id, audio_features):
+ * the k-th feature row goes to the k-th audio token, wherever it is. The calls below do that on the device from the
+ * input_ids the pipeline already holds there: one compaction (two small kernels: a count per chunk of 2048 tokens, then
+ * the places; stable, deterministic, no workgroup waits for another) writes the row map of the projector GEMM's row-map
+ * epilogue into p's workspace, and one gather kernel copies the text rows out of the embedding table. No copy of
+ * input_ids to the host, no run-finding, no separate embedding pass; audio tokens need not form one run per clip. */
+typedef struct {
+    const void * input_ids;    /* device [n_tokens], int32 or int64 (aligned to its width); int64 ids are compared on
+                                  all 64 bits */
+    int32_t ids_width;         /* 4 or 8 */
+    int32_t reserved;          /* 0 */
+    int64_t n_tokens;          /* must equal dst->n_rows; 1 .. 2^24 */
+    int64_t audio_token_id;
+    const void * embed_table;  /* device [vocab][table_ld] of dst's dtype, 16-byte aligned, table_ld >= d_out,
+                                  table_ld * element size % 16 == 0; NULL: text rows are left untouched (vocab and
+                                  table_ld are then not read) */
+    int64_t vocab, table_ld;   /* vocab >= 1 */
+    int32_t * report_dev;      /* device int32[4] or NULL: audio tokens found, feature rows of the call,
+                                  text ids outside [0, vocab), flags (bit 0: found != rows, bit 1: bad ids) */
+} q2a_embeds_src;
+/* The row map of these calls, on the host (pure arithmetic; also exported from libq2a_host.so): row_map[k] = the flat
+ * position of the k-th id equal to audio_token_id for k < min(count, map_cap), -1 for count <= k < map_cap. Returns
+ * count, the number found, even where it exceeds map_cap. Q2A_ERR_ARG, with nothing written, for a width other than
+ * 4 / 8, n_tokens outside 0 .. INT32_MAX, a NULL ids_host with n_tokens > 0, map_cap < 0 or row_map NULL with
+ * map_cap > 0. */
+int64_t q2a_audio_token_rows(const void * ids_host, int32_t ids_width, int64_t n_tokens, int64_t audio_token_id,
+                             int32_t * row_map, int64_t map_cap);
+/* q2a_projector_apply_to with the map derived from src (feature row k of x_dev to the k-th audio token's row), and the
+ * gather: for every position t, input_ids[t] == audio_token_id leaves row t to the GEMM; 0 <= id < vocab copies row id
+ * of the table to row t (d_out elements, a byte copy in 16-byte pieces); any other id stores nothing and is counted.
+ * Columns d_out .. ld-1 of a row are never written. When the audio tokens found differ from `rows`, the first
+ * min(found, rows) pairs are placed, further feature rows are dropped (map entry -1), further audio positions keep what
+ * they held, and the report says so (HF raises there). Every check — q2a_projector_apply_to's, and of src: non-NULL,
+ * input_ids non-NULL and aligned, ids_width, reserved, n_tokens in range and equal to dst->n_rows, and with a table its
+ * alignment, table_ld and vocab — is made before anything is launched or written (Q2A_ERR_ARG). The compaction and the
+ * gather run on the call's stream in front of the GEMM; the map, the chunk counts (and the report words when
+ * report_dev is NULL) live in p's workspace. */
+int q2a_projector_apply_ids(q2a_projector * p, const float * x_dev, int64_t rows, const q2a_feat_dst * dst,
+                            const q2a_embeds_src * src, void * stream);
+/* q2a_audio_features_device_to / _device_mel_to with src in place of clip_row: a finished inputs_embeds in one call. The
+ * _to calls' own checks (no clip ranges: the map comes from input_ids) and q2a_projector_apply_ids' checks of src are
+ * made before anything is launched or written. The GEMM is the _to call's with that map: same operand, M, N, K, hence
+ * the same tile regime and the same bits as q2a_audio_features_device_mel_to given row_map = the audio positions. With no
+ * valid audio row at all (N_tot = 0) no encoder kernel runs, but the gather does and the report is written
+ * ({found, 0, bad ids, flags}). The three small launches are booked under the engine's pool profile class. */
+int q2a_inputs_embeds_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                             const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                             const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev, int64_t embd_rows_cap,
+                             int32_t * out_len, int32_t * status, void * stream);
+int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                 const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
+                                 int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream);
+/* Test hooks. q2a_test_audio_token_rows: the compaction exactly as these calls launch it (map and chunk counts in p's
+ * workspace, sized for n_feat rows, 0 <= n_feat <= 2^28), then the n_feat map words copied to row_map_out_dev (device
+ * int32 [n_feat]; nothing behind them is written); report_dev (device int32[4], required) receives
+ * {found, n_feat, 0, found != n_feat}. q2a_test_embed_gather: the gather alone into dst (d_out columns; src's and dst's
+ * checks as above, a table and report_dev required); the report is {0, 0, bad ids, bad ids ? 2 : 0}. */
+int q2a_test_audio_token_rows(q2a_projector * p, const void * ids_dev, int32_t ids_width, int64_t n_tokens,
+                              int64_t audio_token_id, int64_t n_feat, int32_t * row_map_out_dev, int32_t * report_dev,
+                              void * stream);
+int q2a_test_embed_gather(const q2a_embeds_src * src, const q2a_feat_dst * dst, int32_t d_out, void * stream);
 /* Test hook: the pool kernel of these calls alone, with the engine's final-LayerNorm weights, on caller rows.
  *   x_dev      packed [M_tot][n_audio_state] f32 (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx)
  *   embd_dev   [N_tot][n_audio_state] f32 (q2a_packed_out_rows over key_len), or NULL

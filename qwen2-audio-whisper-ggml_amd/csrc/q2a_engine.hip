@@ -877,6 +877,7 @@ struct q2a_projector {
     uint64_t off[A_COUNT] = {};
     float * bias = nullptr;
     void * ws = nullptr;            // A operand [rows][d_in] fp16 | dy [d_in/blk][MP] | aext [d_in/256][MP][16]
+                                    // | row map [MP] | chunk counts, 4 report words (calls with input_ids)
     size_t ws_bytes = 0;
     const uint16_t * gelu = nullptr;   // the GEMM's table argument (unused by STORE_F, kept valid)
 };
@@ -1381,6 +1382,9 @@ struct encode_call {
     // clip_row[c] on (host [B]; NULL: packed); rows_cap then bounds embd alone
     const q2a_feat_dst * dst;
     const int32_t * clip_row;
+    // the inputs_embeds form (with dst, clip_row NULL): the row map comes from ids->input_ids on the device, and the
+    // text rows are gathered from ids->embed_table
+    const q2a_embeds_src * ids;
     frontend_src src() const { return {pcm, stride, mel, ld}; }
 };
 
@@ -1553,19 +1557,25 @@ struct proj_operand {
     q2a_half * aext;
     int ld;
     int32_t * map;   // device row map [rows] of a _to call with clip_row (proj_workspace with_map), else NULL
+    // a call with input_ids (proj_workspace ids_tokens > 0; it has the map too): the compaction's count per chunk, and
+    // four report words for a caller that passes no report_dev
+    int32_t * chunk_count;
+    int32_t * report;
 };
 // the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0 (q2a_ln_args' modes)
 int proj_mode(const q2a_projector * p) { return p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
 
 // grows the workspace (after everything queued on s: calls on one handle are ordered on one stream) and cuts it up
-int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o, bool with_map = false) {
+int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o, bool with_map = false, int64_t ids_tokens = 0) {
+    with_map = with_map || ids_tokens > 0;
     const int K = p->d_in, blk = p->blk;
     const int64_t MP = (rows + 255) / 256 * 256;
     const size_t a_bytes = ((size_t) rows * K * 2 + 255) & ~size_t(255);
     const size_t dy_bytes = blk ? ((size_t) (K / blk) * MP * 4 + 255) & ~size_t(255) : 0;
     const size_t ae_bytes = blk == 256 ? (size_t) (K / 256 + 1) * MP * 32 : 0;   // (Q6_K: written by the quantizer, unread)
     const size_t map_bytes = with_map ? (size_t) MP * 4 : 0;
-    const size_t need = a_bytes + dy_bytes + ae_bytes + map_bytes;
+    const size_t cc_bytes = ids_tokens > 0 ? (((size_t) (ids_tokens + Q2A_IDS_CHUNK - 1) / Q2A_IDS_CHUNK * 4 + 255) & ~size_t(255)) : 0;
+    const size_t need = a_bytes + dy_bytes + ae_bytes + map_bytes + cc_bytes + (ids_tokens > 0 ? 256 : 0);
     if (need > p->ws_bytes) {
         HIP_TRY(hipStreamSynchronize(s));
         if (p->ws) (void) hipFree(p->ws);
@@ -1578,6 +1588,8 @@ int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand 
     o.aext = (q2a_half *) ((char *) p->ws + a_bytes + dy_bytes);
     o.ld = (int) MP;
     o.map = with_map ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes) : nullptr;
+    o.chunk_count = ids_tokens > 0 ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes + map_bytes) : nullptr;
+    o.report = ids_tokens > 0 ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes + map_bytes + cc_bytes) : nullptr;
     return Q2A_OK;
 }
 
@@ -1618,17 +1630,63 @@ q2a_gemm_args proj_gemm_to(const q2a_projector * p, int M, const proj_operand & 
 }
 
 // a feature destination against the projector's d_out (include/q2a_encoder.h, q2a_feat_dst)
-int feat_dst_check(const q2a_projector * p, const q2a_feat_dst * dst) {
-    if (!p || !dst) { set_err("feature destination: it goes with a projector, and both are required"); return Q2A_ERR_ARG; }
+int feat_dst_check_cols(int d_out, const q2a_feat_dst * dst) {
     const int es = dst->dtype == Q2A_DT_F32 ? 4 : (dst->dtype == Q2A_DT_F16 || dst->dtype == Q2A_DT_BF16) ? 2 : 0;
     if (!es || dst->reserved != 0) { set_err("feature destination: dtype %d, reserved %d", dst->dtype, dst->reserved); return Q2A_ERR_ARG; }
     if (!dst->base || ((uintptr_t) dst->base & 15)) { set_err("feature destination: base must be 16-byte aligned"); return Q2A_ERR_ARG; }
-    if (dst->ld < p->d_out || (dst->ld * es) % 16 != 0) {
-        set_err("feature destination: ld %lld with d_out %d (ld * %d bytes must be a multiple of 16)", (long long) dst->ld, p->d_out, es);
+    if (dst->ld < d_out || (dst->ld * es) % 16 != 0) {
+        set_err("feature destination: ld %lld with d_out %d (ld * %d bytes must be a multiple of 16)", (long long) dst->ld, d_out, es);
         return Q2A_ERR_ARG;
     }
     if (dst->n_rows < 0 || dst->n_rows > INT32_MAX) { set_err("feature destination: n_rows %lld", (long long) dst->n_rows); return Q2A_ERR_ARG; }
     return Q2A_OK;
+}
+
+int feat_dst_check(const q2a_projector * p, const q2a_feat_dst * dst) {
+    if (!p || !dst) { set_err("feature destination: it goes with a projector, and both are required"); return Q2A_ERR_ARG; }
+    return feat_dst_check_cols(p->d_out, dst);
+}
+
+// ---- inputs_embeds: the row map from input_ids and the text-row gather (q2a_embeds.hip) ---------------------------
+int dt_size(int dtype) { return dtype == Q2A_DT_F32 ? 4 : 2; }
+
+// a q2a_embeds_src against a checked destination of d_out columns (include/q2a_encoder.h)
+int embeds_src_check(const q2a_embeds_src * src, const q2a_feat_dst & dst, int d_out) {
+    if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
+    if ((src->ids_width != 4 && src->ids_width != 8) || src->reserved != 0) {
+        set_err("inputs_embeds: ids_width %d, reserved %d", src->ids_width, src->reserved);
+        return Q2A_ERR_ARG;
+    }
+    if (!src->input_ids || ((uintptr_t) src->input_ids & (uintptr_t) (src->ids_width - 1))) {
+        set_err("inputs_embeds: input_ids must be non-NULL and aligned to ids_width");
+        return Q2A_ERR_ARG;
+    }
+    if (src->n_tokens < 1 || src->n_tokens > Q2A_IDS_MAX_TOKENS || src->n_tokens != dst.n_rows) {
+        set_err("inputs_embeds: n_tokens %lld (1 .. 2^24) with a destination of %lld rows", (long long) src->n_tokens, (long long) dst.n_rows);
+        return Q2A_ERR_ARG;
+    }
+    if (src->embed_table) {
+        const int es = dt_size(dst.dtype);
+        if (((uintptr_t) src->embed_table & 15) || src->table_ld < d_out || (src->table_ld * es) % 16 != 0 || src->vocab < 1) {
+            set_err("inputs_embeds: embedding table: 16-byte aligned, table_ld %lld >= d_out %d with table_ld * %d bytes a multiple of 16, vocab %lld >= 1",
+                    (long long) src->table_ld, d_out, es, (long long) src->vocab);
+            return Q2A_ERR_ARG;
+        }
+    }
+    return Q2A_OK;
+}
+
+q2a_ids_args ids_args(const void * ids, int width, int64_t n_tokens, int64_t audio_id, int n_feat, const proj_operand & o, int32_t * report) {
+    return {ids, width, n_tokens, audio_id, n_feat, o.chunk_count, o.map, report ? report : o.report};
+}
+
+// the text rows of a checked src into dst (nothing without a table); the report words 2 and 3 must already be written
+hipError_t launch_embeds_gather(const q2a_embeds_src & src, const q2a_feat_dst & dst, int d_out, int32_t * report, hipStream_t s) {
+    if (!src.embed_table) return hipSuccess;
+    const int es = dt_size(dst.dtype);
+    const q2a_embed_gather_args ga{src.input_ids, src.ids_width, src.n_tokens, src.audio_token_id, src.embed_table, src.vocab,
+                                   src.table_ld * es, dst.base, dst.ld * es, (int64_t) d_out * es, report};
+    return q2a_launch_embed_gather(ga, s);
 }
 
 // map[n] = clip_row[c] + (n - out_start[c]) for the packed output rows n of clip c: the device row map of a _to call,
@@ -1651,6 +1709,10 @@ int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
     if (c.dst) {
         if (c.feat) { set_err("audio features: feat and dst exclude each other"); return Q2A_ERR_ARG; }
         if (int rc = feat_dst_check(c.proj, c.dst)) return rc;
+        if (c.ids) {
+            if (c.clip_row) { set_err("audio features: clip_row and input_ids exclude each other"); return Q2A_ERR_ARG; }
+            if (int rc = embeds_src_check(c.ids, *c.dst, c.proj->d_out)) return rc;
+        }
     } else {
         if (!c.feat && !c.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
         if (c.proj ? !c.feat : c.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
@@ -1664,7 +1726,11 @@ int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
     for (int i = 0; i < c.B; ++i) {
         if (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) n_tot += c.kl[i] / 2;
     }
-    if (c.dst) {
+    if (c.dst && c.ids) {
+        // (no clip ranges: the k-th feature row goes where the k-th audio token is, a row without one is dropped)
+        if (n_tot > (1 << 30) / 4) { set_err("audio features: %lld output rows", (long long) n_tot); return Q2A_ERR_ARG; }
+        if (!c.embd) return Q2A_OK;
+    } else if (c.dst) {
         std::vector<int32_t> ol(c.B);
         for (int i = 0; i < c.B; ++i)
             ol[i] = (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) ? c.kl[i] / 2 : 0;
@@ -1709,7 +1775,17 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
     // the projector's operand buffers, before the first launch (growing them waits for the stream)
     proj_operand po{nullptr, nullptr, nullptr, 0};
-    if (feats && c.proj && rows.N_out > 0 && (rc = proj_workspace(c.proj, rows.N_out, s, po, c.dst && c.clip_row))) return rc;
+    const q2a_embeds_src * ids = feats && c.dst ? c.ids : nullptr;
+    if (feats && c.proj && (rows.N_out > 0 || ids) &&
+        (rc = proj_workspace(c.proj, rows.N_out, s, po, c.dst && c.clip_row, ids ? ids->n_tokens : 0))) return rc;
+    if (ids) {
+        // the inputs_embeds form: the row map from input_ids (and the report), then the text rows; they run whether or
+        // not the call has a feature row
+        int32_t * report = ids->report_dev ? ids->report_dev : po.report;
+        PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_audio_token_rows(ids_args(ids->input_ids, ids->ids_width, ids->n_tokens, ids->audio_token_id,
+                                                                          rows.N_out, po, report), s));
+        if (ids->embed_table) PLAUNCH(e, s, Q2A_PROF_POOL, launch_embeds_gather(*ids, *c.dst, c.proj->d_out, report, s));
+    }
     // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros. The
     // audio-feature tail writes valid rows only: without any, nothing is launched behind the metadata)
     if (feats ? rows.N_out > 0 : kind != ENC_PACKED || rows.M > 0) {
@@ -1730,7 +1806,7 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         if (c.dst) {
             // the _to form: the device row map from the uploaded out_start and clip_row (none when packed), then the
             // same GEMM with the row-map epilogue straight into the caller's rows
-            if (po.map) PLAUNCH(e, s, Q2A_PROF_POOL, launch_feat_row_map(dev.out_start, dev.clip_row, po.map, B, d.TO, s));
+            if (po.map && !ids) PLAUNCH(e, s, Q2A_PROF_POOL, launch_feat_row_map(dev.out_start, dev.clip_row, po.map, B, d.TO, s));
             LAUNCH(q2a_launch_gemm(proj_gemm_to(c.proj, rows.N_out, po, *c.dst, po.map), Q2A_EPI_STORE_ROWS, c.proj->gblk, s));
         } else if (c.proj) {
             LAUNCH(q2a_launch_gemm(proj_gemm(c.proj, rows.N_out, po, c.feat), Q2A_EPI_STORE_F, c.proj->gblk, s));
@@ -2192,6 +2268,37 @@ int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const fl
     encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
     c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
     c.dst = dst; c.clip_row = clip_row;
+    return encode(e, ENC_PACKED, c, call_stream(stream));
+}
+
+// the inputs_embeds form: src in place of clip_row
+int q2a_inputs_embeds_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                             const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                             const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev, int64_t embd_rows_cap,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    std::vector<int32_t> kl;
+    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
+    if (int rc = features_to_check(p, dst)) return rc;
+    if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
+    encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
+    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
+    c.dst = dst; c.ids = src;
+    return encode(e, ENC_PACKED, c, call_stream(stream));
+}
+
+int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                 const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
+                                 int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    encode_kind ek;
+    std::vector<int32_t> kl;
+    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
+    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = features_to_check(p, dst)) return rc;
+    if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
+    encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
+    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
+    c.dst = dst; c.ids = src;
     return encode(e, ENC_PACKED, c, call_stream(stream));
 }
 
@@ -2793,6 +2900,59 @@ int q2a_projector_apply_to(q2a_projector * p, const float * x, int64_t rows, con
         LAUNCH(q2a_launch_quant_act(qa, s));
     }
     LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, row_map), Q2A_EPI_STORE_ROWS, p->gblk, s));
+    return Q2A_OK;
+}
+
+int q2a_projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const q2a_embeds_src * src,
+                            void * stream) {
+    if (!p || !x || !dst || rows <= 0 || rows > (1 << 30) / 4) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = feat_dst_check(p, dst)) return rc;
+    if (int rc = embeds_src_check(src, *dst, p->d_out)) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = call_stream(stream);
+    const int M = (int) rows, K = p->d_in;
+    proj_operand o;
+    if (int rc = proj_workspace(p, rows, s, o, true, src->n_tokens)) return rc;
+    int32_t * report = src->report_dev ? src->report_dev : o.report;
+    LAUNCH(q2a_launch_audio_token_rows(ids_args(src->input_ids, src->ids_width, src->n_tokens, src->audio_token_id, M, o, report), s));
+    LAUNCH(launch_embeds_gather(*src, *dst, p->d_out, report, s));
+    if (p->blk == 0) {
+        const int64_t n = (int64_t) M * K;
+        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
+        LAUNCH(hipGetLastError());
+    } else {
+        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
+        LAUNCH(q2a_launch_quant_act(qa, s));
+    }
+    LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, o.map), Q2A_EPI_STORE_ROWS, p->gblk, s));
+    return Q2A_OK;
+}
+
+int q2a_test_audio_token_rows(q2a_projector * p, const void * ids_dev, int32_t ids_width, int64_t n_tokens, int64_t audio_token_id,
+                              int64_t n_feat, int32_t * row_map_out_dev, int32_t * report_dev, void * stream) {
+    if (!p || !ids_dev || (ids_width != 4 && ids_width != 8) || ((uintptr_t) ids_dev & (uintptr_t) (ids_width - 1)) || n_tokens < 1 ||
+        n_tokens > Q2A_IDS_MAX_TOKENS || n_feat < 0 || n_feat > (1 << 30) / 4 || (n_feat > 0 && !row_map_out_dev) || !report_dev) {
+        set_err("invalid arguments");
+        return Q2A_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    hipStream_t s = call_stream(stream);
+    proj_operand o;
+    if (int rc = proj_workspace(p, n_feat, s, o, true, n_tokens)) return rc;
+    LAUNCH(q2a_launch_audio_token_rows(ids_args(ids_dev, ids_width, n_tokens, audio_token_id, (int) n_feat, o, report_dev), s));
+    if (n_feat > 0) HIP_TRY(hipMemcpyAsync(row_map_out_dev, o.map, (size_t) n_feat * 4, hipMemcpyDeviceToDevice, s));
+    return Q2A_OK;
+}
+
+int q2a_test_embed_gather(const q2a_embeds_src * src, const q2a_feat_dst * dst, int32_t d_out, void * stream) {
+    if (!src || !dst || d_out < 1 || !src->embed_table || !src->report_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    const int es0 = dst->dtype == Q2A_DT_F32 ? 4 : 2;
+    if (((int64_t) d_out * es0) % 16 != 0) { set_err("embed gather: d_out %d is no whole number of 16-byte pieces", d_out); return Q2A_ERR_ARG; }
+    if (int rc = feat_dst_check_cols(d_out, dst)) return rc;
+    if (int rc = embeds_src_check(src, *dst, d_out)) return rc;
+    hipStream_t s = call_stream(stream);
+    HIP_TRY(hipMemsetAsync(src->report_dev, 0, 16, s));
+    LAUNCH(launch_embeds_gather(*src, *dst, d_out, src->report_dev, s));
     return Q2A_OK;
 }
 

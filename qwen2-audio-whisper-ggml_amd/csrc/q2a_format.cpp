@@ -193,6 +193,23 @@ extern "C" int64_t q2a_feat_rows(const int32_t * out_len, const int32_t * clip_r
     return n_tot;
 }
 
+// the row map the q2a_inputs_embeds_* calls derive on the device (include/q2a_encoder.h); here for the same reason
+extern "C" int64_t q2a_audio_token_rows(const void * ids_host, int32_t ids_width, int64_t n_tokens, int64_t audio_token_id,
+                                        int32_t * row_map, int64_t map_cap) {
+    if ((ids_width != 4 && ids_width != 8) || n_tokens < 0 || n_tokens > INT32_MAX || (n_tokens > 0 && !ids_host) || map_cap < 0 ||
+        (map_cap > 0 && !row_map))
+        return Q2A_ERR_ARG;
+    int64_t count = 0;
+    for (int64_t t = 0; t < n_tokens; ++t) {
+        const int64_t id = ids_width == 8 ? ((const int64_t *) ids_host)[t] : (int64_t) ((const int32_t *) ids_host)[t];
+        if (id != audio_token_id) continue;
+        if (count < map_cap) row_map[count] = (int32_t) t;
+        ++count;
+    }
+    for (int64_t k = count; k < map_cap; ++k) row_map[k] = -1;
+    return count;
+}
+
 static double hz_to_mel_slaney(double f) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
     const double logstep = std::log(6.4) / 27.0;

@@ -326,3 +326,38 @@ struct q2a_pool_pack_args {
     int dy_ld;
 };
 hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s);
+
+// ---- inputs_embeds on the device (q2a_embeds.hip; include/q2a_encoder.h, q2a_embeds_src) --------------------------------
+constexpr int Q2A_IDS_CHUNK = 2048;                 // tokens per workgroup of the compaction: a power of two <= 4096
+constexpr int64_t Q2A_IDS_MAX_TOKENS = 1 << 24;
+// Stable compaction of the positions of audio_id in ids [n_tokens] (device, int32 or int64 by width, compared on all
+// their bits): row_map[k] = flat position of the k-th one for k < min(count, n_feat), -1 for count <= k < n_feat, nothing
+// at or behind n_feat; report[0..3] = {count, n_feat, 0, count != n_feat}. Two launches (a count per chunk, then the
+// places); chunk_count: device scratch of ceil(n_tokens / Q2A_IDS_CHUNK) words.
+struct q2a_ids_args {
+    const void * ids;
+    int width;                   // 4 or 8
+    int64_t n_tokens;            // 1 .. Q2A_IDS_MAX_TOKENS
+    int64_t audio_id;
+    int n_feat;                  // >= 0
+    int32_t * chunk_count;
+    int32_t * row_map;           // device [n_feat] (may be NULL when n_feat == 0)
+    int32_t * report;            // device int32[4]
+};
+hipError_t q2a_launch_audio_token_rows(const q2a_ids_args & a, hipStream_t s);
+// Text-row gather: for every token t with ids[t] != audio_id, row ids[t] of the table is copied (row_bytes bytes, in
+// 16-byte pieces) to row t of out; an id outside [0, vocab) stores nothing, adds 1 to report[2] and sets bit 1 of
+// report[3] (both must hold defined values: the compaction writes them first). Bytes row_bytes .. out_ld_bytes-1 of a
+// destination row are never written.
+struct q2a_embed_gather_args {
+    const void * ids;
+    int width;
+    int64_t n_tokens;
+    int64_t audio_id;
+    const void * table;          // 16-byte aligned
+    int64_t vocab, table_ld_bytes;
+    void * out;                  // 16-byte aligned
+    int64_t out_ld_bytes, row_bytes;   // multiples of 16
+    int32_t * report;
+};
+hipError_t q2a_launch_embed_gather(const q2a_embed_gather_args & a, hipStream_t s);

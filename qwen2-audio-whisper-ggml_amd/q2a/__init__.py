@@ -34,6 +34,8 @@ EXPORTS = (
     "q2a_audio_features_host_mel", "q2a_test_pool_operand",
     "q2a_feat_rows", "q2a_projector_apply_to", "q2a_projector_regime", "q2a_audio_features_device_to",
     "q2a_audio_features_device_mel_to",
+    "q2a_audio_token_rows", "q2a_projector_apply_ids", "q2a_inputs_embeds_device", "q2a_inputs_embeds_device_mel",
+    "q2a_test_audio_token_rows", "q2a_test_embed_gather",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -79,6 +81,19 @@ class FeatDst(C.Structure):
 
 def feat_dst(base_ptr: int, ld: int, n_rows: int, dtype: int) -> FeatDst:
     return FeatDst(C.c_void_p(base_ptr) if base_ptr else None, ld, n_rows, dtype, 0)
+
+
+class EmbedsSrc(C.Structure):
+    """q2a_embeds_src: input_ids on the device, the audio token id, and the embedding table the text rows come from."""
+    _fields_ = [("input_ids", C.c_void_p), ("ids_width", C.c_int32), ("reserved", C.c_int32), ("n_tokens", C.c_int64),
+                ("audio_token_id", C.c_int64), ("embed_table", C.c_void_p), ("vocab", C.c_int64), ("table_ld", C.c_int64),
+                ("report_dev", C.c_void_p)]
+
+
+def embeds_src(ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int, table_ptr: int = 0, vocab: int = 0,
+               table_ld: int = 0, report_ptr: int = 0) -> EmbedsSrc:
+    p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+    return EmbedsSrc(p(ids_ptr), ids_width, 0, n_tokens, audio_token_id, p(table_ptr), vocab, table_ld, p(report_ptr))
 
 
 _lib = None
@@ -186,6 +201,17 @@ def lib() -> C.CDLL:
                                                        C.c_int64, i32p, i32p, vp]
             L.q2a_audio_features_device_mel_to.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, dstp,
                                                            i32p, vp, C.c_int64, i32p, i32p, vp]
+        if hasattr(L, "q2a_inputs_embeds_device"):   # inputs_embeds from input_ids on the device
+            dstp, srcp = C.POINTER(FeatDst), C.POINTER(EmbedsSrc)
+            L.q2a_audio_token_rows.restype = C.c_int64
+            L.q2a_audio_token_rows.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int64]
+            L.q2a_projector_apply_ids.argtypes = [vp, vp, C.c_int64, dstp, srcp, vp]
+            L.q2a_inputs_embeds_device.argtypes = [vp, vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, dstp, srcp, vp, C.c_int64,
+                                                   i32p, i32p, vp]
+            L.q2a_inputs_embeds_device_mel.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, dstp, srcp,
+                                                       vp, C.c_int64, i32p, i32p, vp]
+            L.q2a_test_audio_token_rows.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp]
+            L.q2a_test_embed_gather.argtypes = [srcp, dstp, C.c_int32, vp]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -502,6 +528,46 @@ class Engine:
                                                       st.ctypes.data_as(i32p), p(stream)))
         return ol, st
 
+    def inputs_embeds_device(self, pcm_ptr: int, pcm_stride: int, n_samples, dst: FeatDst, src: EmbedsSrc, projector,
+                             embd_ptr: int = 0, embd_rows_cap: int = 0, offsets_ms=None, key_len=None,
+                             stream: int | None = None):
+        """q2a_inputs_embeds_device: audio_features_device_to with the rows placed by src's input_ids (the k-th feature
+        row at the k-th audio token) and the text rows gathered from src's embedding table. Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
+        n = len(ns)
+        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_inputs_embeds_device(self.h, projector.h if projector is not None else None, p(pcm_ptr),
+                                              C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n,
+                                              C.byref(dst) if dst is not None else None,
+                                              C.byref(src) if src is not None else None, p(embd_ptr), C.c_int64(embd_rows_cap),
+                                              ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p), p(stream)))
+        return ol, st
+
+    def inputs_embeds_device_mel(self, mel_ptr: int, clip_stride: int, ld: int, n_len, dst: FeatDst, src: EmbedsSrc, projector,
+                                 embd_ptr: int = 0, embd_rows_cap: int = 0, seek=None, key_len=None,
+                                 stream: int | None = None):
+        """q2a_inputs_embeds_device_mel: audio_features_device_mel's inputs, inputs_embeds_device's outputs."""
+        i32p = C.POINTER(C.c_int32)
+        nl = np.ascontiguousarray(n_len, dtype=np.int32)
+        n = len(nl)
+        _sk, skp = self._i32(seek, n, "seek")
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_inputs_embeds_device_mel(self.h, projector.h if projector is not None else None, p(mel_ptr),
+                                                  C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp, n,
+                                                  C.byref(dst) if dst is not None else None,
+                                                  C.byref(src) if src is not None else None, p(embd_ptr),
+                                                  C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
+                                                  p(stream)))
+        return ol, st
+
     def _features_host(self, fn, ptrs, lens, n, second, key_len, projector, embd, rows_cap, raise_on_error):
         i32p = C.POINTER(C.c_int32)
         _kl, klp = self._i32(key_len, n, "key_len")
@@ -634,6 +700,76 @@ class Engine:
                                                       stream=torch.cuda.current_stream(x.device).cuda_stream)
         return (out, ol, emb) if return_embd else (out, ol)
 
+    def inputs_embeds(self, input_features, feature_attention_mask, input_ids, audio_token_id: int, projector,
+                      embed_tokens=None, out=None, check: bool = True):
+        """The language model's inputs_embeds in one call (q2a_inputs_embeds_device_mel, on torch's current stream):
+        embed_tokens[input_ids] with the k-th audio feature row stored at the k-th position whose id is audio_token_id —
+        Qwen2AudioForConditionalGeneration's embedding pass, cast and masked_scatter, without a host copy of input_ids.
+        input_features [B][n_mels][L] f32 (CUDA) and feature_attention_mask [B][L] (or None) as for audio_features — the
+        key lengths are host arithmetic, so a mask that lives on the device is copied back; pass it as a host tensor;
+        input_ids: a contiguous CUDA int32 or int64 tensor [B][S] or [n]; embed_tokens: the embedding weight [vocab][d_out]
+        of out's dtype on that device (rows may be strided), or None: text rows keep what out holds; out: a contiguous
+        CUDA tensor input_ids.shape + (d_out,) of float32 / float16 / bfloat16 (None: allocated, embed_tokens' dtype, or
+        float32 zeros without a table). Returns (inputs_embeds, out_len [B], report): report is a CUDA int32[4] tensor —
+        audio tokens found, feature rows, text ids outside [0, vocab), flags (bit 0: found != rows, bit 1: bad ids). With
+        check=True the four words are read (one synchronising copy) and a mismatch or a bad id raises ValueError;
+        check=False reads nothing on the host."""
+        import torch
+        if projector is None:
+            raise ValueError("inputs_embeds: a projector is required")
+        ids = input_ids
+        if not (hasattr(ids, "is_cuda") and ids.is_cuda and ids.dtype in (torch.int32, torch.int64) and ids.dim() in (1, 2)
+                and ids.is_contiguous() and ids.numel() >= 1):
+            raise ValueError("input_ids: a contiguous CUDA int32 or int64 tensor [B][S] or [n]")
+        n_tok = ids.numel()
+        if n_tok > 1 << 24:
+            raise ValueError("input_ids: at most 2^24 tokens")
+        d_out = projector.d_out
+        dts = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
+        tab = embed_tokens
+        if tab is not None and not (hasattr(tab, "is_cuda") and tab.is_cuda and tab.device == ids.device and tab.dim() == 2
+                                    and tab.shape[1] == d_out and tab.dtype in dts and tab.stride(1) == 1 and tab.shape[0] >= 1
+                                    and tab.stride(0) >= d_out):
+            raise ValueError(f"embed_tokens: a CUDA tensor [vocab][{d_out}] of float32, float16 or bfloat16 on input_ids' device")
+        if out is None:
+            shape = tuple(ids.shape) + (d_out,)
+            out = (torch.empty(shape, dtype=tab.dtype, device=ids.device) if tab is not None
+                   else torch.zeros(shape, dtype=torch.float32, device=ids.device))
+        elif not (hasattr(out, "is_cuda") and out.is_cuda and out.device == ids.device and out.is_contiguous() and out.dtype in dts
+                  and tuple(out.shape) == tuple(ids.shape) + (d_out,)):
+            raise ValueError(f"out: a contiguous CUDA tensor input_ids.shape + ({d_out},) of float32, float16 or bfloat16")
+        if tab is not None and tab.dtype != out.dtype:
+            raise ValueError("embed_tokens: out's dtype")
+        x = input_features
+        if not (hasattr(x, "is_cuda") and x.is_cuda and x.dtype == torch.float32 and x.device == out.device):
+            raise ValueError("input_features: a float32 CUDA tensor on input_ids' device")
+        shape = tuple(x.shape)
+        if len(shape) != 3 or shape[1] != self.info.n_mels:
+            raise ValueError(f"input_features must be [B][{self.info.n_mels}][L]")
+        B, _, L = shape
+        if feature_attention_mask is not None:
+            m = feature_attention_mask
+            m = m.detach().cpu().numpy() if hasattr(m, "detach") else np.asarray(m)
+            if m.shape != (B, L):
+                raise ValueError(f"feature_attention_mask must be [{B}][{L}]")
+            kl = features_key_len(m.astype(np.int64).sum(-1))
+        else:
+            kl = np.full(B, mel_valid_lengths(L, 0, self.info.n_audio_ctx)[0], dtype=np.int32)
+        x = x.contiguous()
+        report = torch.empty(4, dtype=torch.int32, device=ids.device)
+        dst = feat_dst(out.data_ptr(), d_out, n_tok, dts[out.dtype])
+        src = embeds_src(ids.data_ptr(), ids.element_size(), n_tok, int(audio_token_id),
+                         tab.data_ptr() if tab is not None else 0, tab.shape[0] if tab is not None else 0,
+                         tab.stride(0) if tab is not None else 0, report.data_ptr())
+        ol, _ = self.inputs_embeds_device_mel(x.data_ptr(), self.info.n_mels * L, L, [L] * B, dst, src, projector, key_len=kl,
+                                              stream=torch.cuda.current_stream(x.device).cuda_stream)
+        if check:
+            found, rows, bad, flags = (int(v) for v in report.cpu())
+            if flags:
+                raise ValueError(f"inputs_embeds: {found} audio tokens in input_ids for {rows} audio feature rows, "
+                                 f"{bad} text ids outside the embedding table")
+        return out, ol, report
+
     def test_pool_operand(self, mode, x_ptr, n_clips, key_len, embd_ptr=0, codes_ptr=0, dy_ptr=0, aext_ptr=0, ld=0, stream=None):
         """q2a_test_pool_operand: the audio-feature calls' pool kernel alone on packed caller rows x [M_tot][D] ->
         embd [N_tot][D] f32 and / or the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0) in test_operand's layouts."""
@@ -750,6 +886,8 @@ def _host() -> C.CDLL:
         _host_lib.q2a_packed_out_rows.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32)]
         _host_lib.q2a_feat_rows.restype = C.c_int64
         _host_lib.q2a_feat_rows.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.POINTER(C.c_int32)]
+        _host_lib.q2a_audio_token_rows.restype = C.c_int64
+        _host_lib.q2a_audio_token_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64]
     return _host_lib
 
 
@@ -805,6 +943,40 @@ def feat_rows(out_len, clip_rows, n_rows: int, row_map: np.ndarray | None = None
         err.rc = int(n)
         raise err
     return int(n), row_map
+
+
+def audio_token_rows(input_ids, audio_token_id: int, map_cap: int | None = None) -> tuple[int, np.ndarray]:
+    """(count, row_map): the row map the inputs_embeds calls derive on the device (q2a_audio_token_rows) — row_map[k] is
+    the flat position of the k-th entry of input_ids (numpy int32 or int64, any shape, row-major) equal to
+    audio_token_id, -1 for count <= k < map_cap (None: map_cap = count). count is the number found, also where it
+    exceeds map_cap. Host arithmetic through lib/libq2a_host.so: needs no GPU."""
+    ids = np.asarray(input_ids)
+    if ids.dtype not in (np.int32, np.int64):
+        raise ValueError("input_ids: int32 or int64")
+    ids = np.ascontiguousarray(ids).reshape(-1)
+    fn = _host().q2a_audio_token_rows
+    i32p = C.POINTER(C.c_int32)
+    args = (ids.ctypes.data_as(C.c_void_p), ids.itemsize, C.c_int64(ids.size), C.c_int64(int(audio_token_id)))
+    if map_cap is None:
+        map_cap = int(fn(*args, None, C.c_int64(0)))
+    if map_cap < 0:
+        raise ValueError("map_cap must be >= 0")
+    row_map = np.zeros(map_cap, dtype=np.int32)
+    n = fn(*args, row_map.ctypes.data_as(i32p) if map_cap else None, C.c_int64(map_cap))
+    if n < 0:
+        err = Q2AError(f"q2a error {n}: invalid arguments to q2a_audio_token_rows")
+        err.rc = int(n)
+        raise err
+    return int(n), row_map
+
+
+def test_embed_gather(src: EmbedsSrc, dst: FeatDst, d_out: int, stream=None):
+    """q2a_test_embed_gather: the text-row gather of the inputs_embeds calls alone."""
+    _check(lib().q2a_test_embed_gather(C.byref(src) if src is not None else None, C.byref(dst) if dst is not None else None,
+                                       d_out, C.c_void_p(stream) if stream else None))
+
+
+test_embed_gather.__test__ = False   # (a library hook, not a test)
 
 
 def audio_token_runs(input_ids, audio_token_id: int) -> tuple[np.ndarray, np.ndarray]:
@@ -942,6 +1114,21 @@ class Projector:
         _check(lib().q2a_projector_apply_to(self.h, C.c_void_p(x_ptr), rows, C.byref(dst) if dst is not None else None,
                                             C.c_void_p(row_map_ptr) if row_map_ptr else None,
                                             C.c_void_p(stream) if stream else None))
+
+    def apply_ids(self, x_ptr: int, rows: int, dst: FeatDst, src: EmbedsSrc, stream=None):
+        """q2a_projector_apply_ids: apply_to with the row map derived on the device from src's input_ids (feature row k
+        at the k-th audio token), and the text rows gathered from src's embedding table."""
+        _check(lib().q2a_projector_apply_ids(self.h, C.c_void_p(x_ptr), rows, C.byref(dst) if dst is not None else None,
+                                             C.byref(src) if src is not None else None,
+                                             C.c_void_p(stream) if stream else None))
+
+    def test_audio_token_rows(self, ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int, n_feat: int,
+                              row_map_ptr: int, report_ptr: int, stream=None):
+        """q2a_test_audio_token_rows: the compaction of the inputs_embeds calls alone — the n_feat map words to
+        row_map_ptr (device int32 [n_feat]), {found, n_feat, 0, found != n_feat} to report_ptr (device int32[4])."""
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(lib().q2a_test_audio_token_rows(self.h, p(ids_ptr), ids_width, C.c_int64(n_tokens), C.c_int64(audio_token_id),
+                                               C.c_int64(n_feat), p(row_map_ptr), p(report_ptr), p(stream)))
 
     def regime(self, rows: int) -> int:
         """q2a_projector_regime: the REGIME_* the projector's GEMM takes at `rows` rows (nothing is launched)."""
