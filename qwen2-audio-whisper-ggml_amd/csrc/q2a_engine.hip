@@ -6,589 +6,28 @@
 // run time: the model is packed once into a device blob and every intermediate lives in a workspace reserved
 // for the batch size, so a batch is ~11 launches per layer on one stream (capturable into a hipGraph).
 #include "q2a_encoder.h"
-#include "q2a_format.h"
-#include "q2a_internal.h"
+#include "q2a_blob.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cerrno>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
-#include <thread>
-#include <vector>
+
+using namespace q2a_blob;
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-void set_err(const char * fmt, ...) {
+void q2a_blob::set_err(const char * fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof(buf), fmt, ap);
     va_end(ap);
     g_err = buf;
-}
-
-#define HIP_TRY(x)                                                                        \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess) {                                                           \
-            set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return Q2A_ERR_HIP;                                                           \
-        }                                                                                 \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// packed device blob: 16 KiB self-describing header + 256-B aligned sections
-// ------------------------------------------------------------------------------------------------
-constexpr uint32_t BLOB_MAGIC = 0x42413251u;   // "Q2AB"
-// version 3: the Q4_K gamma array holds -(dmin/dx) (stored negated); a version-2 blob (positive gamma) is refused
-constexpr uint32_t BLOB_VERSION = 5;   // 4: conv1 taps against the three-part mel operand; 5: compact transport form
-constexpr int MAX_LAYERS = 64;
-constexpr size_t HEADER_BYTES = 32768;
-
-enum { G_CONV1_W, G_CONV1_B, G_CONV2_W, G_CONV2_B, G_PE, G_LNP_W, G_LNP_B, G_FILT, G_TAB, G_GELU, G_GELU_C, G_COUNT };
-// per-matrix arrays: W (fp16 [N][K]); block-major DX, DMIN, BETA = DX_{b-1}/DX_b, GAMMA = DMIN_b/DX_b (f32 [nblk][N]),
-// WEXT (fp16 [nblk][N][16]). Q6_K: W = q - 32, DX = d [K/256][N], and in the WEXT slot its sub-block scales
-// SC (f32 [K/16][N], sub-block-major: one K-step's four rows of a tile are contiguous runs)
-enum { A_W, A_DX, A_DMIN, A_WEXT, A_BETA, A_GAMMA, A_COUNT };
-constexpr int A_SC = A_WEXT;
-enum { L_BQKV, L_BO, L_B1, L_B2, L_LN1W, L_LN1B, L_LN2W, L_LN2B, L_MAT0, L_COUNT = L_MAT0 + 4 * A_COUNT };
-
-struct blob_header {
-    uint32_t magic, version;
-    q2a_hparams hp;
-    int32_t wtype, blk, n_bins, act;   // act: Q2A_ACT_REFERENCE (0) or Q2A_ACT_BF16 (1)
-    int32_t compact;                   // 1: the transport form (compact_of below); 0: the device layout
-    uint64_t total;                    // bytes of the device layout (goff / loff address it)
-    uint64_t goff[G_COUNT];
-    uint64_t loff[MAX_LAYERS][L_COUNT];
-};
-static_assert(sizeof(blob_header) <= HEADER_BYTES, "header too large");
-
-struct dims {
-    int T, D, H, L, M, F, TM, TO;
-};
-dims dims_of(const q2a_hparams & hp) {
-    dims d;
-    d.T = hp.n_audio_ctx; d.D = hp.n_audio_state; d.H = hp.n_audio_head; d.L = hp.n_audio_layer; d.M = hp.n_mels;
-    d.F = 4 * d.D; d.TM = 2 * d.T; d.TO = d.T / 2;
-    return d;
-}
-void mat_dims(const dims & d, int which, int & N, int & K) {
-    switch (which) {
-        case 0: N = 3 * d.D; K = d.D; break;
-        case 1: N = d.D; K = d.D; break;
-        case 2: N = d.F; K = d.D; break;
-        default: N = d.D; K = d.F; break;
-    }
-}
-// the activation block of a weight type (its vec_dot_type's: Q8_K for the k-quants, Q8_0 for Q8_0 / Q4_0), 0 = fp16
-int blk_of(int wtype) {
-    return (wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K || wtype == Q2A_TYPE_Q6_K) ? 256
-           : (wtype == Q2A_TYPE_Q8_0 || wtype == Q2A_TYPE_Q4_0) ? 32 : 0;
-}
-// the GEMM's block mode: the activation block, but for Q6_K (per-16 integer scales inside the 256-block)
-int gblk_of(int wtype) { return wtype == Q2A_TYPE_Q6_K ? Q2A_BLK_Q6K : blk_of(wtype); }
-// Q4_K's device layout (sc*q weights, min operand, block-ratio arrays): Q4_K and Q5_K
-bool kq_minmax(int wtype) { return wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K; }
-
-bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act) {
-    memset(&h, 0, sizeof(h));
-    // bf16-activation mode: every linear weight dequantized to bf16 [N][K] (no block scales, no splits)
-    h.magic = BLOB_MAGIC; h.version = BLOB_VERSION; h.hp = hp; h.wtype = wtype; h.blk = act ? 0 : blk_of(wtype); h.n_bins = 201;
-    h.act = act;
-    const dims d = dims_of(hp);
-    if (d.L > MAX_LAYERS) return false;
-    // all-F32 files: every fp16 operand is a [hi | .. ] split (SPLIT = 3 parts of K for the linears, conv1 taps of
-    // 3 mel parts, conv2 taps of 2 parts), see expand_rows / pack
-    const bool f32 = wtype == Q2A_TYPE_F32;
-    const uint64_t kx = f32 && !act ? 3 : 1;
-    uint64_t off = HEADER_BYTES;
-    auto take = [&](uint64_t bytes) { const uint64_t o = off; off += (bytes + 255) & ~uint64_t(255); return o; };
-    h.goff[G_CONV1_W] = take((uint64_t) d.D * 3 * 3 * d.M * 2);
-    h.goff[G_CONV1_B] = take((uint64_t) d.D * 4);
-    h.goff[G_CONV2_W] = take((uint64_t) d.D * 3 * (f32 ? 2 : 1) * d.D * 2);
-    h.goff[G_CONV2_B] = take((uint64_t) d.D * 4);
-    h.goff[G_PE] = take((uint64_t) d.T * d.D * 4);
-    h.goff[G_LNP_W] = take((uint64_t) d.D * 4);
-    h.goff[G_LNP_B] = take((uint64_t) d.D * 4);
-    h.goff[G_FILT] = take((uint64_t) d.M * 201 * 4);
-    h.goff[G_TAB] = take(1200 * 4);
-    h.goff[G_GELU] = take(65536 * 2);
-    h.goff[G_GELU_C] = take(Q2A_GELU_C_BYTES);
-    for (int l = 0; l < d.L; ++l) {
-        uint64_t * lo = h.loff[l];
-        lo[L_BQKV] = take((uint64_t) 3 * d.D * 4);
-        lo[L_BO] = take((uint64_t) d.D * 4);
-        lo[L_B1] = take((uint64_t) d.F * 4);
-        lo[L_B2] = take((uint64_t) d.D * 4);
-        lo[L_LN1W] = take((uint64_t) d.D * 4);
-        lo[L_LN1B] = take((uint64_t) d.D * 4);
-        lo[L_LN2W] = take((uint64_t) d.D * 4);
-        lo[L_LN2B] = take((uint64_t) d.D * 4);
-        for (int w = 0; w < 4; ++w) {
-            int N, K;
-            mat_dims(d, w, N, K);
-            uint64_t * a = lo + L_MAT0 + w * A_COUNT;
-            a[A_W] = take((uint64_t) N * K * 2 * kx);
-            if (h.blk) a[A_DX] = take((uint64_t) N * (K / h.blk) * 4);
-            if (h.blk && kq_minmax(wtype)) {
-                a[A_DMIN] = take((uint64_t) N * (K / 256) * 4);
-                a[A_WEXT] = take((uint64_t) N * (K / 256) * 16 * 2);
-                a[A_BETA] = take((uint64_t) N * (K / 256) * 4);
-                a[A_GAMMA] = take((uint64_t) N * (K / 256) * 4);
-            } else if (h.blk && wtype == Q2A_TYPE_Q6_K) {
-                a[A_SC] = take((uint64_t) N * (K / 16) * 4);
-            }
-        }
-    }
-    h.total = off;
-    return true;
-}
-
-// The compact TRANSPORT form of a blob (what rank 0 broadcasts): the header (compact = 1, goff / loff
-// still describing the device layout), the small sections verbatim as two kinds of runs — the global one
-// [HEADER_BYTES, loff[0][L_BQKV]) and, per layer, the biases + LayerNorm run [loff[l][L_BQKV], loff[l][L_MAT0]) — then
-// every linear weight as the model file's own ggml rows (QKV: the q | k | v rows), e.g. raw block_q4_K at 144 B per
-// 256 weights instead of the 2-byte sc*q expansion plus its block-scale arrays. expand_blob rebuilds the device
-// layout from it on the GPU, byte for byte what pack() writes on the host.
-struct compact_layout {
-    uint64_t g_off, g_len;
-    uint64_t l_off[MAX_LAYERS], l_len[MAX_LAYERS];
-    uint64_t raw_off[MAX_LAYERS][4], raw_len[MAX_LAYERS][4];
-    uint64_t total;
-};
-compact_layout compact_of(const blob_header & h) {
-    compact_layout c;
-    memset(&c, 0, sizeof(c));
-    const dims d = dims_of(h.hp);
-    uint64_t off = HEADER_BYTES;
-    auto take = [&](uint64_t bytes) { const uint64_t o = off; off += (bytes + 255) & ~uint64_t(255); return o; };
-    c.g_len = h.loff[0][L_BQKV] - HEADER_BYTES;
-    c.g_off = take(c.g_len);
-    for (int l = 0; l < d.L; ++l) {
-        c.l_len[l] = h.loff[l][L_MAT0 + A_W] - h.loff[l][L_BQKV];
-        c.l_off[l] = take(c.l_len[l]);
-    }
-    for (int l = 0; l < d.L; ++l)
-        for (int w = 0; w < 4; ++w) {
-            int N, K;
-            mat_dims(d, w, N, K);
-            c.raw_len[l][w] = (uint64_t) N * q2a_row_size(h.wtype, K);
-            c.raw_off[l][w] = take(c.raw_len[l][w]);
-        }
-    c.total = off;
-    return c;
-}
-
-// A header that arrives from outside the packer (a device blob, an RCCL-broadcast buffer, a caller's host copy) is
-// checked before anything is derived from it: compact_of and expand_blob index fixed [MAX_LAYERS] arrays by its layer
-// count and address device memory by its offsets. Magic, version, the shape rules pack() enforces, and every offset
-// equal to what plan() lays out for those hparams. nullptr = valid, else the reason.
-const char * header_problem(const blob_header & h) {
-    if (h.magic != BLOB_MAGIC || h.version != BLOB_VERSION) return "not a q2a weight blob";
-    const dims d = dims_of(h.hp);
-    if (d.L <= 0 || d.L > MAX_LAYERS) return "not a q2a weight blob (layer count out of range)";
-    if (d.D <= 0 || d.D % 128 || d.D != d.H * 64 || d.T <= 0 || d.T % 2 || d.M <= 0 || d.M % 4 || d.T > (1 << 20) ||
-        d.M > 4096)
-        return "not a q2a weight blob (unsupported shapes)";
-    if ((h.compact != 0 && h.compact != 1) || (h.act != Q2A_ACT_REFERENCE && h.act != Q2A_ACT_BF16) ||
-        q2a_row_size(h.wtype, d.D) == 0 || (blk_of(h.wtype) == 256 && d.D % 256))
-        return "not a q2a weight blob (bad type fields)";
-    blob_header p;
-    if (!plan(p, h.hp, h.wtype, h.act)) return "not a q2a weight blob (layout)";
-    if (p.total != h.total || p.blk != h.blk || p.n_bins != h.n_bins || memcmp(p.goff, h.goff, sizeof(p.goff)) ||
-        memcmp(p.loff, h.loff, sizeof(p.loff[0]) * d.L))
-        return "not a q2a weight blob (inconsistent layout)";
-    return nullptr;
-}
-
-inline void scale_min_k4(int j, const uint8_t * q, uint8_t * dd, uint8_t * mm) {   // ggml-quants.c:1898
-    if (j < 4) { *dd = q[j] & 63; *mm = q[j + 4] & 63; }
-    else {
-        *dd = (uint8_t) ((q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4));
-        *mm = (uint8_t) ((q[j + 4] >> 4) | ((q[j - 0] >> 6) << 4));
-    }
-}
-
-// the 5-bit code of weight l of sub-block j (ggml-quants.c:2782-2783: nibble j & 1 of qs[32 (j / 2) + l], bit j of qh[l])
-inline int q5k_code(const q2a_block_q5_K * x, int j, int l) {
-    const uint8_t q = x->qs[32 * (j / 2) + l];
-    return ((j & 1) ? (q >> 4) : (q & 0xF)) + (((x->qh[l] >> j) & 1) << 4);
-}
-// the 6-bit code (0..63) of weight k of a block (ggml-quants.c:2988-2998: per 128 weights, four runs of 32 over two
-// 32-byte rows of nibbles and one of 2-bit pairs)
-inline int q6k_code(const q2a_block_q6_K * x, int k) {
-    const int h = k / 128, r = (k % 128) / 32, l = k % 32;
-    const uint8_t n = x->ql[64 * h + 32 * (r & 1) + l];
-    return ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
-}
-
-// Expand rows [r0, r1) of a ggml weight matrix into the blob arrays (rows offset by dst_row0).
-// F16: copied. Q4_K: W' = sc_j * q (exact small integers), DX = d, DMIN = dmin, WEXT = (64 m_j, m_j). Q5_K: the same
-// with its 5-bit codes (sc_j * q <= 1953, still an exact fp16 integer). Q6_K: W' = q - 32, DX = d, SC = sc_j.
-// Q8_0: W' = q, DX = d. Q4_0: W' = q - 8, DX = d.
-// one ggml row -> f32 values, as ggml's dequantize_row_* computes them (ggml-quants.c: q8_0 :1734, q4_0 :1694,
-// q4_K :2555-2577 with d1 = d*sc, m1 = dmin*m, y = d1*q - m1)
-void dequant_row(const uint8_t * row, int wtype, int K, float * y) {
-    if (wtype == Q2A_TYPE_F32) { memcpy(y, row, (size_t) K * 4); return; }
-    if (wtype == Q2A_TYPE_F16) { for (int k = 0; k < K; ++k) y[k] = q2a_fp16_to_fp32(((const uint16_t *) row)[k]); return; }
-    if (wtype == Q2A_TYPE_Q8_0) {
-        for (int b = 0; b < K / 32; ++b) {
-            const q2a_block_q8_0 * x = (const q2a_block_q8_0 *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int l = 0; l < 32; ++l) y[b * 32 + l] = x->qs[l] * d;
-        }
-    } else if (wtype == Q2A_TYPE_Q4_0) {
-        for (int b = 0; b < K / 32; ++b) {
-            const q2a_block_q4_0 * x = (const q2a_block_q4_0 *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int l = 0; l < 16; ++l) {
-                y[b * 32 + l] = ((x->qs[l] & 0xF) - 8) * d;
-                y[b * 32 + 16 + l] = ((x->qs[l] >> 4) - 8) * d;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q4_K) {
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q4_K * x = (const q2a_block_q4_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
-            for (int j = 0; j < 8; ++j) {
-                uint8_t sc, m;
-                scale_min_k4(j, x->scales, &sc, &m);
-                const float d1 = d * sc, m1 = dmin * m;
-                const uint8_t * q = x->qs + 32 * (j / 2);
-                for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * ((j & 1) ? (q[l] >> 4) : (q[l] & 0xF)) - m1;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q5_K) {   // dequantize_row_q5_K, ggml-quants.c:2763-2788
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q5_K * x = (const q2a_block_q5_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
-            for (int j = 0; j < 8; ++j) {
-                uint8_t sc, m;
-                scale_min_k4(j, x->scales, &sc, &m);
-                const float d1 = d * sc, m1 = dmin * m;
-                for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * q5k_code(x, j, l) - m1;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q6_K) {   // dequantize_row_q6_K, ggml-quants.c:2977-3006: (d * sc) * q
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int k = 0; k < 256; ++k) y[b * 256 + k] = d * x->scales[k / 16] * (int8_t) (q6k_code(x, k) - 32);
-        }
-    }
-}
-
-uint16_t f32_to_bf16(float f) {   // round to nearest even (finite inputs)
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (uint16_t) ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1, uint8_t * blob, const uint64_t * a, int dst_row0,
-                 int act = 0) {
-    uint16_t * W = (uint16_t *) (blob + a[A_W]);
-    const size_t rs = q2a_row_size(wtype, K);
-    std::vector<float> tmp(act ? K : 0);
-    for (int r = r0; r < r1; ++r) {
-        const uint8_t * row = src + (size_t) r * rs;
-        const int n = dst_row0 + r;
-        uint16_t * wr = W + (size_t) n * K;
-        if (act) {   // bf16-activation mode: dequantized weight, RNE to bf16
-            dequant_row(row, wtype, K, tmp.data());
-            for (int k = 0; k < K; ++k) wr[k] = f32_to_bf16(tmp[k]);
-        } else if (wtype == Q2A_TYPE_F16) {
-            memcpy(wr, row, (size_t) K * 2);
-        } else if (wtype == Q2A_TYPE_F32) {
-            // [Wh | Wh | Wl] against activations [Ah | Al | Ah]: Ah.Wh + Al.Wh + Ah.Wl, F32-class products
-            const float * x = (const float *) row;
-            uint16_t * w3 = W + (size_t) n * 3 * K;
-            for (int k = 0; k < K; ++k) {
-                const uint16_t hi = q2a_fp32_to_fp16(x[k]);
-                w3[k] = hi;
-                w3[K + k] = hi;
-                w3[2 * K + k] = q2a_fp32_to_fp16(x[k] - q2a_fp16_to_fp32(hi));
-            }
-        } else if (wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K) {
-            // block-major scale arrays: [nb][Ntot] / [nb][Ntot][16] so a tile's block scales are contiguous
-            // (block_q5_K begins like block_q4_K: d, dmin, scales[12]; only the codes are read by type)
-            const bool q5 = wtype == Q2A_TYPE_Q5_K;
-            const int nb = K / 256;
-            float * dx = (float *) (blob + a[A_DX]);
-            float * dm = (float *) (blob + a[A_DMIN]);
-            float * be = (float *) (blob + a[A_BETA]);
-            float * ga = (float *) (blob + a[A_GAMMA]);
-            uint16_t * we = (uint16_t *) (blob + a[A_WEXT]);
-            float dprev = 1.0f;
-            for (int b = 0; b < nb; ++b) {
-                const q2a_block_q5_K * x5 = (const q2a_block_q5_K *) row + b;
-                const q2a_block_q4_K * x = q5 ? (const q2a_block_q4_K *) x5 : (const q2a_block_q4_K *) row + b;
-                // d = 0: the block's d*sc*q terms vanish; store dx = 1 with zero weights instead (same products,
-                // and the block-ratio rescaling of the 8-phase kernel never divides by zero)
-                const float d = q2a_fp16_to_fp32(x->d);
-                const float deff = d != 0.0f ? d : 1.0f;
-                dx[(size_t) b * Ntot + n] = deff;
-                dm[(size_t) b * Ntot + n] = q2a_fp16_to_fp32(x->dmin);
-                be[(size_t) b * Ntot + n] = dprev / deff;
-                ga[(size_t) b * Ntot + n] = -(q2a_fp16_to_fp32(x->dmin) / deff);   // negated: the kernels' fma addend
-                dprev = deff;
-                for (int j = 0; j < 8; ++j) {
-                    uint8_t sc, m;
-                    scale_min_k4(j, x->scales, &sc, &m);
-                    we[((size_t) b * Ntot + n) * 16 + 2 * j + 0] = q2a_fp32_to_fp16(64.0f * m);
-                    we[((size_t) b * Ntot + n) * 16 + 2 * j + 1] = q2a_fp32_to_fp16((float) m);
-                    const uint8_t * q = x->qs + 32 * (j / 2);
-                    for (int l = 0; l < 32; ++l) {
-                        const int v = q5 ? q5k_code(x5, j, l) : (j & 1) ? (q[l] >> 4) : (q[l] & 0xF);
-                        wr[b * 256 + 32 * j + l] = q2a_fp32_to_fp16(d != 0.0f ? (float) (sc * v) : 0.0f);
-                    }
-                }
-            }
-        } else if (wtype == Q2A_TYPE_Q6_K) {
-            // (a block the quantizer zeroed, d = 0 with every byte 0, needs no special case: nothing divides by d)
-            const int nb = K / 256;
-            float * dx = (float *) (blob + a[A_DX]);
-            float * sc = (float *) (blob + a[A_SC]);
-            for (int b = 0; b < nb; ++b) {
-                const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
-                dx[(size_t) b * Ntot + n] = q2a_fp16_to_fp32(x->d);
-                for (int j = 0; j < 16; ++j) sc[(size_t) (b * 16 + j) * Ntot + n] = (float) x->scales[j];
-                for (int k = 0; k < 256; ++k) wr[b * 256 + k] = q2a_fp32_to_fp16((float) (q6k_code(x, k) - 32));
-            }
-        } else if (wtype == Q2A_TYPE_Q8_0) {
-            const int nb = K / 32;
-            float * dx = (float *) (blob + a[A_DX]);
-            for (int b = 0; b < nb; ++b) {
-                const q2a_block_q8_0 * x = (const q2a_block_q8_0 *) row + b;
-                dx[(size_t) b * Ntot + n] = q2a_fp16_to_fp32(x->d);
-                for (int l = 0; l < 32; ++l) wr[b * 32 + l] = q2a_fp32_to_fp16((float) x->qs[l]);
-            }
-        } else if (wtype == Q2A_TYPE_Q4_0) {
-            const int nb = K / 32;
-            float * dx = (float *) (blob + a[A_DX]);
-            for (int b = 0; b < nb; ++b) {
-                const q2a_block_q4_0 * x = (const q2a_block_q4_0 *) row + b;
-                dx[(size_t) b * Ntot + n] = q2a_fp16_to_fp32(x->d);
-                for (int l = 0; l < 16; ++l) {
-                    wr[b * 32 + l] = q2a_fp32_to_fp16((float) ((x->qs[l] & 0xF) - 8));
-                    wr[b * 32 + 16 + l] = q2a_fp32_to_fp16((float) ((x->qs[l] >> 4) - 8));
-                }
-            }
-        }
-    }
-}
-
-int pack(const char * path, std::vector<uint8_t> & out, int act = 0, bool compact = false) {
-    char err[256];
-    q2a_model_file * mf = q2a_model_file_read(path, err, sizeof(err));
-    if (!mf) { set_err("%s", err); return errno == ENOENT ? Q2A_ERR_IO : Q2A_ERR_FORMAT; }
-    struct guard { q2a_model_file * m; ~guard() { q2a_model_file_free(m); } } gd{mf};
-    const q2a_hparams & hp = mf->hp;
-    const int wtype = mf->wtype;
-    const dims d = dims_of(hp);
-    if (d.D % 128 || d.D != d.H * 64 || d.T % 2 || d.M % 4 || (blk_of(wtype) == 256 && d.D % 256)) {
-        set_err("unsupported shapes: D=%d H=%d T=%d M=%d", d.D, d.H, d.T, d.M);
-        return Q2A_ERR_UNSUPPORTED;
-    }
-    if (mf->n_mel_filt != d.M || mf->n_fft_filt != 201) { set_err("bad mel filter shape"); return Q2A_ERR_FORMAT; }
-    blob_header h;
-    if (!plan(h, hp, wtype, act)) { set_err("too many layers"); return Q2A_ERR_UNSUPPORTED; }
-    // the compact transport form is written directly (its size, not the device layout's: 0.38 vs 1.40 GB for Q4_K)
-    compact_layout c;
-    if (compact) { h.compact = 1; c = compact_of(h); }
-    out.assign(compact ? c.total : h.total, 0);
-    uint8_t * blob = out.data();
-    memcpy(blob, &h, sizeof(h));
-    // a small section's device-layout offset -> its bytes in `out` (the compact form keeps the global run and each
-    // layer's bias / LayerNorm run verbatim, packed one after the other)
-    auto at = [&](uint64_t off) -> uint8_t * {
-        if (!compact) return blob + off;
-        if (off < h.loff[0][L_BQKV]) return blob + c.g_off + (off - HEADER_BYTES);
-        int l = d.L - 1;
-        while (l > 0 && off < h.loff[l][L_BQKV]) --l;
-        return blob + c.l_off[l] + (off - h.loff[l][L_BQKV]);
-    };
-
-    auto T = [&](const std::string & name, int type, std::initializer_list<int64_t> ne) -> const uint8_t * {
-        const q2a_tensor_desc * t = q2a_model_file_find(mf, name.c_str());
-        if (!t) { set_err("tensor '%s' missing from model file", name.c_str()); return nullptr; }
-        if (type >= 0 && t->type != type) { set_err("tensor '%s' has type %d, expected %d", name.c_str(), t->type, type); return nullptr; }
-        int i = 0;
-        for (int64_t v : ne) {
-            if (t->ne[i] != v) { set_err("tensor '%s' has wrong shape", name.c_str()); return nullptr; }
-            ++i;
-        }
-        return mf->data + t->offset;
-    };
-    auto cpy = [&](uint64_t off, const uint8_t * src, size_t n) { memcpy(at(off), src, n); };
-
-    // conv kernels are F16 in every file but the all-F32 one (vtype, qwen2-whisper.cpp:1542-1543)
-    const bool f32 = wtype == Q2A_TYPE_F32;
-    const int ctype = f32 ? Q2A_TYPE_F32 : Q2A_TYPE_F16;
-    const uint8_t * c1 = T("conv1.weight", ctype, {3, d.M, d.D});
-    const uint8_t * c1b = T("conv1.bias", Q2A_TYPE_F32, {1, d.D});
-    const uint8_t * c2 = T("conv2.weight", ctype, {3, d.D, d.D});
-    const uint8_t * c2b = T("conv2.bias", Q2A_TYPE_F32, {1, d.D});
-    const uint8_t * pe = T("embed_positions.weight", Q2A_TYPE_F32, {d.D, d.T});
-    const uint8_t * lnw = T("layer_norm.weight", Q2A_TYPE_F32, {d.D});
-    const uint8_t * lnb = T("layer_norm.bias", Q2A_TYPE_F32, {d.D});
-    if (!c1 || !c1b || !c2 || !c2b || !pe || !lnw || !lnb) return Q2A_ERR_FORMAT;
-    {
-        // hi / lo fp16 halves of a conv kernel element (F16 kernels: the value itself, lo = 0)
-        auto hl = [&](const uint8_t * src, size_t i, uint16_t & hi, uint16_t & lo) {
-            if (!f32) { hi = ((const uint16_t *) src)[i]; lo = 0; return; }
-            const float x = ((const float *) src)[i];
-            hi = q2a_fp32_to_fp16(x);
-            lo = q2a_fp32_to_fp16(x - q2a_fp16_to_fp32(hi));
-        };
-        // conv1: [oc][ic][k] -> k-major taps against the mel operand rows: F16 [w | w | w] x [mel_h | mel_m | mel_l]
-        // (exact); F32 [wh | wh | wl] x [mel_h | mel_l | mel_h]
-        const int P1 = 3;
-        uint16_t * w = (uint16_t *) at(h.goff[G_CONV1_W]);
-        for (int oc = 0; oc < d.D; ++oc)
-            for (int ic = 0; ic < d.M; ++ic)
-                for (int k = 0; k < 3; ++k) {
-                    uint16_t hi, lo;
-                    hl(c1, ((size_t) oc * d.M + ic) * 3 + k, hi, lo);
-                    uint16_t * t = w + (size_t) oc * 3 * P1 * d.M + (size_t) k * P1 * d.M + ic;
-                    t[0] = hi;
-                    t[d.M] = hi;
-                    t[2 * d.M] = f32 ? lo : hi;
-                }
-        // conv2: k-major taps over three consecutive conv1 output rows: F16 [w]; F32 [wh | wl] x rows [y | y]
-        const int P2 = f32 ? 2 : 1;
-        uint16_t * w2 = (uint16_t *) at(h.goff[G_CONV2_W]);
-        for (int oc = 0; oc < d.D; ++oc)
-            for (int ic = 0; ic < d.D; ++ic)
-                for (int k = 0; k < 3; ++k) {
-                    uint16_t hi, lo;
-                    hl(c2, ((size_t) oc * d.D + ic) * 3 + k, hi, lo);
-                    uint16_t * t = w2 + (size_t) oc * 3 * P2 * d.D + (size_t) k * P2 * d.D + ic;
-                    t[0] = hi;
-                    if (f32) t[d.D] = lo;
-                }
-    }
-    cpy(h.goff[G_CONV1_B], c1b, (size_t) d.D * 4);
-    cpy(h.goff[G_CONV2_B], c2b, (size_t) d.D * 4);
-    cpy(h.goff[G_PE], pe, (size_t) d.T * d.D * 4);
-    cpy(h.goff[G_LNP_W], lnw, (size_t) d.D * 4);
-    cpy(h.goff[G_LNP_B], lnb, (size_t) d.D * 4);
-    cpy(h.goff[G_FILT], (const uint8_t *) mf->filters, (size_t) d.M * 201 * 4);
-    q2a_make_mel_tables((float *) at(h.goff[G_TAB]));
-    q2a_make_gelu_table((uint16_t *) at(h.goff[G_GELU]));
-    {   // compact |x| <= 10 image of the table for the LDS-resident epilogue lookups: [+0 .. +10] | [-0 .. -10]
-        const uint16_t * t = (const uint16_t *) at(h.goff[G_GELU]);
-        uint16_t * cg = (uint16_t *) at(h.goff[G_GELU_C]);
-        memset(cg, 0, Q2A_GELU_C_BYTES);
-        for (int i = 0; i < Q2A_GELU_C_HALF; ++i) { cg[i] = t[i]; cg[Q2A_GELU_C_HALF + i] = t[0x8000 + i]; }
-    }
-
-    struct job { const uint8_t * src; int K, Ntot, r0, r1; const uint64_t * a; int dst0; };
-    std::vector<job> jobs;
-    for (int l = 0; l < d.L; ++l) {
-        const std::string p = "layers." + std::to_string(l) + ".";
-        const uint64_t * lo = h.loff[l];
-        const uint8_t * wq = T(p + "self_attn.q_proj.weight", wtype, {d.D, d.D});
-        const uint8_t * bq = T(p + "self_attn.q_proj.bias", Q2A_TYPE_F32, {d.D});
-        const uint8_t * wk = T(p + "self_attn.k_proj.weight", wtype, {d.D, d.D});
-        const uint8_t * wv = T(p + "self_attn.v_proj.weight", wtype, {d.D, d.D});
-        const uint8_t * bv = T(p + "self_attn.v_proj.bias", Q2A_TYPE_F32, {d.D});
-        const uint8_t * wo = T(p + "self_attn.out_proj.weight", wtype, {d.D, d.D});
-        const uint8_t * bo = T(p + "self_attn.out_proj.bias", Q2A_TYPE_F32, {d.D});
-        const uint8_t * l1w = T(p + "self_attn_layer_norm.weight", Q2A_TYPE_F32, {d.D});
-        const uint8_t * l1b = T(p + "self_attn_layer_norm.bias", Q2A_TYPE_F32, {d.D});
-        const uint8_t * w1 = T(p + "fc1.weight", wtype, {d.D, d.F});
-        const uint8_t * b1 = T(p + "fc1.bias", Q2A_TYPE_F32, {d.F});
-        const uint8_t * w2 = T(p + "fc2.weight", wtype, {d.F, d.D});
-        const uint8_t * b2 = T(p + "fc2.bias", Q2A_TYPE_F32, {d.D});
-        const uint8_t * l2w = T(p + "final_layer_norm.weight", Q2A_TYPE_F32, {d.D});
-        const uint8_t * l2b = T(p + "final_layer_norm.bias", Q2A_TYPE_F32, {d.D});
-        if (!wq || !bq || !wk || !wv || !bv || !wo || !bo || !l1w || !l1b || !w1 || !b1 || !w2 || !b2 || !l2w || !l2b)
-            return Q2A_ERR_FORMAT;
-        float * bqkv = (float *) at(lo[L_BQKV]);
-        memcpy(bqkv, bq, (size_t) d.D * 4);                 // q bias; k has no bias (qwen2-whisper.cpp:2037)
-        memcpy(bqkv + 2 * d.D, bv, (size_t) d.D * 4);
-        cpy(lo[L_BO], bo, (size_t) d.D * 4);
-        cpy(lo[L_B1], b1, (size_t) d.F * 4);
-        cpy(lo[L_B2], b2, (size_t) d.D * 4);
-        cpy(lo[L_LN1W], l1w, (size_t) d.D * 4);
-        cpy(lo[L_LN1B], l1b, (size_t) d.D * 4);
-        cpy(lo[L_LN2W], l2w, (size_t) d.D * 4);
-        cpy(lo[L_LN2B], l2b, (size_t) d.D * 4);
-        const uint64_t * a0 = lo + L_MAT0;
-        jobs.push_back({wq, d.D, 3 * d.D, 0, d.D, a0, 0});
-        jobs.push_back({wk, d.D, 3 * d.D, 0, d.D, a0, d.D});
-        jobs.push_back({wv, d.D, 3 * d.D, 0, d.D, a0, 2 * d.D});
-        jobs.push_back({wo, d.D, d.D, 0, d.D, lo + L_MAT0 + A_COUNT, 0});
-        jobs.push_back({w1, d.D, d.F, 0, d.F, lo + L_MAT0 + 2 * A_COUNT, 0});
-        jobs.push_back({w2, d.F, d.D, 0, d.D, lo + L_MAT0 + 3 * A_COUNT, 0});
-    }
-    if (compact) {   // the transport form: small sections written above, linear weights as the file's ggml rows
-        for (int l = 0; l < d.L; ++l)
-            for (int w = 0; w < 4; ++w) {   // jobs[6l..6l+5] = q, k, v, o, fc1, fc2
-                const int j0 = w == 0 ? 0 : w + 2, nj = w == 0 ? 3 : 1;
-                uint64_t o = c.raw_off[l][w];
-                for (int q = 0; q < nj; ++q) {
-                    const job & jb = jobs[6 * l + j0 + q];
-                    const size_t n = (size_t) (jb.r1 - jb.r0) * q2a_row_size(wtype, jb.K);
-                    memcpy(blob + o, jb.src, n);
-                    o += n;
-                }
-            }
-        return Q2A_OK;
-    }
-    const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() {
-            for (const job & j : jobs) {
-                const int n = j.r1 - j.r0;
-                expand_rows(j.src, wtype, j.K, j.Ntot, j.r0 + n * t / nt, j.r0 + n * (t + 1) / nt, blob, j.a, j.dst0, act);
-            }
-        });
-    for (auto & x : th) x.join();
-    return Q2A_OK;
-}
-
-}  // namespace
-
-// One weight matrix on its own (the ggml-backend plugin's MUL_MAT weights): same arrays as a blob matrix,
-// laid out in one allocation whose offsets go to off[A_W..A_GAMMA] (0 = absent).
-uint64_t q2a_pack_layout(int wtype, int N, int K, uint64_t off[6]) {
-    const int blk = blk_of(wtype);
-    if ((wtype != Q2A_TYPE_F16 && !blk) || (blk && K % blk) || N <= 0 || K <= 0) return 0;
-    uint64_t o = 0;
-    auto take = [&](uint64_t bytes) { const uint64_t r = o; o += (bytes + 255) & ~uint64_t(255); return r; };
-    for (int i = 0; i < A_COUNT; ++i) off[i] = 0;
-    off[A_W] = take((uint64_t) N * K * 2);
-    if (blk) off[A_DX] = take((uint64_t) N * (K / blk) * 4);
-    if (kq_minmax(wtype)) {
-        off[A_DMIN] = take((uint64_t) N * (K / 256) * 4);
-        off[A_WEXT] = take((uint64_t) N * (K / 256) * 16 * 2);
-        off[A_BETA] = take((uint64_t) N * (K / 256) * 4);
-        off[A_GAMMA] = take((uint64_t) N * (K / 256) * 4);
-    } else if (wtype == Q2A_TYPE_Q6_K) {
-        off[A_SC] = take((uint64_t) N * (K / 16) * 4);
-    }
-    return o;
-}
-
-int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6]) {
-    const uint64_t o = q2a_pack_layout(wtype, N, K, off);
-    if (!o) return Q2A_ERR_UNSUPPORTED;
-    out.assign(o, 0);
-    const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() { expand_rows(raw, wtype, K, N, (int) ((int64_t) N * t / nt), (int) ((int64_t) N * (t + 1) / nt), out.data(), off, 0); });
-    for (auto & x : th) x.join();
-    return Q2A_OK;
 }
 
 namespace {
@@ -625,162 +64,6 @@ __global__ void k_split3(const float * x, q2a_half * y, int K, int64_t n) {
     o[0] = h;
     o[K] = (_Float16) (v - (float) h);
     o[2 * K] = h;
-}
-
-// ---- compact blob -> device layout (expand_rows on the GPU: every value bit-identical to the host pack) ----
-__device__ __forceinline__ float h2f(uint16_t u) { return (float) __builtin_bit_cast(_Float16, u); }
-__device__ __forceinline__ uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16) f); }   // RNE
-__device__ __forceinline__ uint16_t f2bf(float f) {   // RNE on the bits, as f32_to_bf16 (finite inputs)
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    return (uint16_t) ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ void scale_min_k4_d(int j, const uint8_t * q, int & dd, int & mm) {   // ggml-quants.c:1898
-    if (j < 4) { dd = q[j] & 63; mm = q[j + 4] & 63; }
-    else { dd = (q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4); mm = (q[j + 4] >> 4) | ((q[j - 0] >> 6) << 4); }
-}
-__device__ __forceinline__ int q5k_code_d(const q2a_block_q5_K * x, int j, int l) {   // as q5k_code
-    const int q = x->qs[32 * (j / 2) + l];
-    return ((j & 1) ? (q >> 4) : (q & 0xF)) + (((x->qh[l] >> j) & 1) << 4);
-}
-__device__ __forceinline__ int q6k_code_d(const q2a_block_q6_K * x, int k) {   // as q6k_code
-    const int h = k / 128, r = (k % 128) / 32, l = k % 32;
-    const int n = x->ql[64 * h + 32 * (r & 1) + l];
-    return ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
-}
-
-struct expand_args {
-    const uint8_t * raw;    // ggml rows [nrows][row_size]
-    uint8_t * blob;         // device layout
-    uint64_t a[A_COUNT];    // the matrix's array offsets in the device layout
-    int wtype, act, K, Ntot, kx;
-};
-
-// one workgroup = 256 consecutive weights of one row (blockIdx.x = row, blockIdx.y = 256-chunk of K); the float
-// operations are expand_rows' / dequant_row's, uncontracted, so every byte equals the host pack
-__global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
-#pragma clang fp contract(off)
-    const int n = blockIdx.x, t = threadIdx.x, k = blockIdx.y * 256 + t;
-    const size_t rs = p.wtype == Q2A_TYPE_Q4_K ? (size_t) p.K / 256 * 144 : p.wtype == Q2A_TYPE_Q5_K ? (size_t) p.K / 256 * 176
-                    : p.wtype == Q2A_TYPE_Q6_K ? (size_t) p.K / 256 * 210 : p.wtype == Q2A_TYPE_Q8_0 ? (size_t) p.K / 32 * 34
-                    : p.wtype == Q2A_TYPE_Q4_0 ? (size_t) p.K / 32 * 18 : p.wtype == Q2A_TYPE_F16 ? (size_t) p.K * 2 : (size_t) p.K * 4;
-    const uint8_t * row = p.raw + (size_t) n * rs;
-    uint16_t * W = (uint16_t *) (p.blob + p.a[A_W]);
-    if (k >= p.K) return;
-    float val = 0.0f;   // dequantized value (bf16 mode)
-    if (p.wtype == Q2A_TYPE_Q4_K || p.wtype == Q2A_TYPE_Q5_K) {
-        const bool q5 = p.wtype == Q2A_TYPE_Q5_K;   // (block_q5_K begins like block_q4_K: d, dmin, scales[12])
-        const int b = k / 256, j = (k % 256) / 32, l = k % 32;
-        const q2a_block_q5_K * x5 = (const q2a_block_q5_K *) row + b;
-        const q2a_block_q4_K * x = q5 ? (const q2a_block_q4_K *) x5 : (const q2a_block_q4_K *) row + b;
-        int sc, m;
-        scale_min_k4_d(j, x->scales, sc, m);
-        const int v = q5 ? q5k_code_d(x5, j, l) : (j & 1) ? (x->qs[32 * (j / 2) + l] >> 4) : (x->qs[32 * (j / 2) + l] & 0xF);
-        const float d = h2f(x->d), dmin = h2f(x->dmin);
-        if (p.act) {
-            const float d1 = d * (float) sc, m1 = dmin * (float) m;
-            val = d1 * (float) v - m1;
-        } else {
-            W[(size_t) n * p.K + k] = d != 0.0f ? f2h((float) (sc * v)) : (uint16_t) 0;
-            const size_t bi = (size_t) b * p.Ntot + n;
-            const float deff = d != 0.0f ? d : 1.0f;
-            if (t == 0) {
-                float dprev = 1.0f;
-                if (b > 0) {
-                    const float dp = q5 ? h2f((x5 - 1)->d) : h2f((x - 1)->d);
-                    dprev = dp != 0.0f ? dp : 1.0f;
-                }
-                ((float *) (p.blob + p.a[A_DX]))[bi] = deff;
-                ((float *) (p.blob + p.a[A_DMIN]))[bi] = dmin;
-                ((float *) (p.blob + p.a[A_BETA]))[bi] = dprev / deff;
-                ((float *) (p.blob + p.a[A_GAMMA]))[bi] = -(dmin / deff);
-            }
-            if (t < 16) {
-                int sj, mj;
-                scale_min_k4_d(t / 2, x->scales, sj, mj);
-                ((uint16_t *) (p.blob + p.a[A_WEXT]))[bi * 16 + t] = f2h((t & 1) ? (float) mj : 64.0f * (float) mj);
-            }
-            return;
-        }
-    } else if (p.wtype == Q2A_TYPE_Q6_K) {
-        const int b = k / 256, kk = k % 256;
-        const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
-        const int q = q6k_code_d(x, kk) - 32;
-        const float d = h2f(x->d);
-        if (p.act) val = d * (float) x->scales[kk / 16] * (float) q;
-        else {
-            W[(size_t) n * p.K + k] = f2h((float) q);
-            if (t == 0) ((float *) (p.blob + p.a[A_DX]))[(size_t) b * p.Ntot + n] = d;
-            if (t < 16) ((float *) (p.blob + p.a[A_SC]))[(size_t) (b * 16 + t) * p.Ntot + n] = (float) x->scales[t];
-            return;
-        }
-    } else if (p.wtype == Q2A_TYPE_Q8_0) {
-        const q2a_block_q8_0 * x = (const q2a_block_q8_0 *) row + k / 32;
-        const float d = h2f(x->d);
-        if (p.act) val = x->qs[k % 32] * d;
-        else {
-            W[(size_t) n * p.K + k] = f2h((float) x->qs[k % 32]);
-            if (k % 32 == 0) ((float *) (p.blob + p.a[A_DX]))[(size_t) (k / 32) * p.Ntot + n] = d;
-            return;
-        }
-    } else if (p.wtype == Q2A_TYPE_Q4_0) {
-        const q2a_block_q4_0 * x = (const q2a_block_q4_0 *) row + k / 32;
-        const int l = k % 32, q = (l < 16 ? (x->qs[l] & 0xF) : (x->qs[l - 16] >> 4)) - 8;
-        const float d = h2f(x->d);
-        if (p.act) val = q * d;
-        else {
-            W[(size_t) n * p.K + k] = f2h((float) q);
-            if (l == 0) ((float *) (p.blob + p.a[A_DX]))[(size_t) (k / 32) * p.Ntot + n] = d;
-            return;
-        }
-    } else if (p.wtype == Q2A_TYPE_F16) {
-        const uint16_t u = ((const uint16_t *) row)[k];
-        if (p.act) val = h2f(u);
-        else { W[(size_t) n * p.K + k] = u; return; }
-    } else {   // F32
-        const float x = ((const float *) row)[k];
-        if (p.act) val = x;
-        else {   // [Wh | Wh | Wl]
-            uint16_t * w3 = W + (size_t) n * 3 * p.K;
-            const uint16_t hi = f2h(x);
-            w3[k] = hi;
-            w3[p.K + k] = hi;
-            w3[2 * p.K + k] = f2h(x - h2f(hi));
-            return;
-        }
-    }
-    W[(size_t) n * p.K + k] = f2bf(val);
-}
-
-// device layout of `h` (compact = 1) from the compact blob `cb` (both on the current device); `out` holds h.total bytes
-int expand_blob(const uint8_t * cb, const blob_header & h, uint8_t * out, hipStream_t s) {
-    const compact_layout c = compact_of(h);
-    const dims d = dims_of(h.hp);
-    std::vector<uint8_t> head(HEADER_BYTES, 0);
-    // on every return (errors included) the stream drains before `head`, which an async copy may still read, is freed
-    struct drain { hipStream_t s; ~drain() { (void) hipStreamSynchronize(s); } } dr{s};
-    blob_header hx = h;
-    hx.compact = 0;
-    memcpy(head.data(), &hx, sizeof(hx));
-    HIP_TRY(hipMemsetAsync(out, 0, h.total, s));
-    HIP_TRY(hipMemcpyAsync(out, head.data(), HEADER_BYTES, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(out + HEADER_BYTES, cb + c.g_off, c.g_len, hipMemcpyDeviceToDevice, s));
-    const int kx = h.wtype == Q2A_TYPE_F32 && !h.act ? 3 : 1;
-    for (int l = 0; l < d.L; ++l) {
-        HIP_TRY(hipMemcpyAsync(out + h.loff[l][L_BQKV], cb + c.l_off[l], c.l_len[l], hipMemcpyDeviceToDevice, s));
-        for (int w = 0; w < 4; ++w) {
-            int N, K;
-            mat_dims(d, w, N, K);
-            expand_args a;
-            a.raw = cb + c.raw_off[l][w];
-            a.blob = out;
-            for (int i = 0; i < A_COUNT; ++i) a.a[i] = h.loff[l][L_MAT0 + w * A_COUNT + i];
-            a.wtype = h.wtype; a.act = h.act; a.K = K; a.Ntot = N; a.kx = kx;
-            hipLaunchKernelGGL(k_expand_rows, dim3((unsigned) N, (unsigned) ((K + 255) / 256)), dim3(256), 0, s, a);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(s));   // (the header's host staging must outlive its copy)
-    return Q2A_OK;
 }
 
 hipError_t launch_split3(const float * x, q2a_half * y, int K, int64_t n, hipStream_t s) {
@@ -1296,27 +579,84 @@ q2a_mel_args mel_args(const q2a_engine * e, const float * pcm, int64_t stride, c
     return ma;
 }
 
-// what the front end reads: PCM (pcm [B][stride], the mel kernels), or with `mel` set caller-owned log-mel (clip c:
-// [n_mels][ld] at mel + c * stride, the ingest kernel). The per-clip lengths and seeks are in the call's device rows.
-struct frontend_src {
-    const float * pcm;
-    int64_t stride;             // 0: every clip reads the same PCM / the same mel
-    const float * mel;
-    int64_t ld;
+// The clips of a call: B clips in device memory, clip c at data + c * stride (stride 0: every clip reads the same
+// array), and host arrays of B entries. PCM (pcm_input): len[c] samples, encoded from offs[c] ms (offs NULL: offset_ms
+// for every clip). Log-mel (mel_input): the caller's normalised mel [n_mels][ld] with len[c] frames, encoded from frame
+// seek[c] (NULL: 0). A host entry point describes its clips the same way with data NULL (host_clips).
+struct clip_input {
+    bool mel;
+    int B;
+    const float * data;
+    int64_t stride;
+    const int32_t * len;
+    const int32_t * offs;       // PCM
+    int offset_ms;
+    int64_t ld;                 // log-mel
+    const int32_t * seek;
 };
+clip_input pcm_input(const float * pcm, int64_t stride, const int32_t * n_samples, int B, const int32_t * offs, int offset_ms = 0) {
+    clip_input in{};
+    in.B = B; in.data = pcm; in.stride = stride; in.len = n_samples; in.offs = offs; in.offset_ms = offset_ms;
+    return in;
+}
+clip_input mel_input(const float * mel, int64_t clip_stride, int64_t ld, const int32_t * n_len, const int32_t * seek, int B) {
+    clip_input in{};
+    in.mel = true; in.B = B; in.data = mel; in.stride = clip_stride; in.len = n_len; in.ld = ld; in.seek = seek;
+    return in;
+}
+
+// Where a call's result goes, exactly one of: the windows out [B][TO][D] (window_sink); the valid output rows of all
+// clips packed (q2a_packed_out_rows) as f32 into embd [rows_cap][D] and / or, through the projector, into feat
+// [rows_cap][d_out] (packed_sink); the features as dst's type into dst's rows, clip c's from row clip_row[c] on (host
+// [B]; NULL: packed), embd [rows_cap][D] still the packed f32 rows (rows_sink); or into dst's rows where ids->input_ids
+// holds the audio token, the text rows gathered from ids->embed_table (ids_sink). All but the first are the
+// audio-feature tail of a variable-length encode.
+struct out_sink {
+    enum { WINDOWS, PACKED, ROWS, IDS } kind;
+    float * out;
+    float * feat;
+    float * embd;               // NULL: not written
+    int64_t rows_cap;
+    const q2a_feat_dst * dst;
+    const int32_t * clip_row;
+    const q2a_embeds_src * ids;
+    bool features() const { return kind != WINDOWS; }
+    bool to_dst() const { return kind == ROWS || kind == IDS; }
+};
+out_sink window_sink(float * out) {
+    out_sink k{};
+    k.kind = out_sink::WINDOWS; k.out = out;
+    return k;
+}
+out_sink packed_sink(float * feat, float * embd, int64_t rows_cap) {
+    out_sink k{};
+    k.kind = out_sink::PACKED; k.feat = feat; k.embd = embd; k.rows_cap = rows_cap;
+    return k;
+}
+out_sink rows_sink(const q2a_feat_dst * dst, const int32_t * clip_row, float * embd, int64_t rows_cap) {
+    out_sink k{};
+    k.kind = out_sink::ROWS; k.dst = dst; k.clip_row = clip_row; k.embd = embd; k.rows_cap = rows_cap;
+    return k;
+}
+out_sink ids_sink(const q2a_feat_dst * dst, const q2a_embeds_src * ids, float * embd, int64_t rows_cap) {
+    out_sink k{};
+    k.kind = out_sink::IDS; k.dst = dst; k.ids = ids; k.embd = embd; k.rows_cap = rows_cap;
+    return k;
+}
 
 // mel + conv frontend: PCM or log-mel -> X [B*T][D] (conv graph qwen2-whisper.cpp:1892-1952 + pe add :2005); the same
-// conv launches after either mel producer
-int run_frontend(q2a_engine * e, const frontend_src & src, int B, int max_frames, hipStream_t s) {
+// conv launches after either mel producer. The per-clip lengths and seeks are in the call's device rows.
+int run_frontend(q2a_engine * e, const clip_input & in, int max_frames, hipStream_t s) {
     const dims & d = e->d;
+    const int B = in.B;
     const meta_rows dev(e->meta, B);
-    if (src.mel) {
-        const q2a_mel_ingest_args ia{src.mel, src.stride, src.ld, dev.nsamp, dev.seek, B, d.M, d.TM, e->xc1, e->f32 ? 1 : 0};
+    if (in.mel) {
+        const q2a_mel_ingest_args ia{in.data, in.stride, in.ld, dev.nsamp, dev.seek, B, d.M, d.TM, e->xc1, e->f32 ? 1 : 0};
         PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel_ingest(ia, s));
     } else {
         LAUNCH(hipMemsetAsync(dev.clip_max, 0x80, (size_t) B * 4, s));
         if (int rc = ensure_frange(e, s)) return rc;
-        const q2a_mel_args ma = mel_args(e, src.pcm, src.stride, dev, B, max_frames);
+        const q2a_mel_args ma = mel_args(e, in.data, in.stride, dev, B, max_frames);
         PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_mel(ma, s));
     }
     const int P1 = 3, P2 = e->f32 ? 2 : 1;   // operand parts per mel row / per conv1 output row
@@ -1354,44 +694,28 @@ int run_frontend(q2a_engine * e, const frontend_src & src, int B, int max_frames
 // the attention, the blocks on all B*T rows) and the variable-length ones (the blocks on the packed valid rows)
 enum encode_kind { ENC_PLAIN, ENC_PADDED, ENC_PACKED };
 
-// the arguments of one encode: B clips in device memory, host arrays of B entries. The input is PCM, or with `mel`
-// set (q2a_encode_device_mel) log-mel: pcm is then NULL, stride the clip stride of mel, n_samples the clips' n_len and
-// seek their first window frames (NULL: 0); offset_ms and offs are not read
-struct encode_call {
-    const float * pcm;
-    int64_t stride;             // 0: every clip reads the same PCM
-    const int32_t * n_samples;
-    int B;
-    int offset_ms;
-    const int32_t * offs;       // per-clip offsets, NULL = offset_ms for every clip
-    const int32_t * kl;         // key lengths, checked by padded_key_lens (ENC_PADDED, ENC_PACKED)
-    float * out;                // device [B][TO][D]
-    int32_t * out_len;          // NULL, or the clips' valid output rows (ENC_PADDED, ENC_PACKED)
-    int32_t * status;           // NULL, or Q2A_CLIP_* per clip
-    const float * mel;          // device, clip c: [n_mels][ld] at mel + c * stride
-    int64_t ld;
-    const int32_t * seek;
-    // the audio-feature tail (ENC_PACKED with `features`; `out` is then not read): the valid output rows of all clips
-    // packed (q2a_packed_out_rows) into embd [rows_cap][D] and / or, through proj, into feat [rows_cap][d_out]
-    bool features;
-    q2a_projector * proj;       // NULL: no projection (feat NULL)
-    float * feat;
-    float * embd;               // NULL: not written
-    int64_t rows_cap;
-    // the _to form: the features go to dst (f32 / fp16 / bf16 rows of the caller's, feat NULL), clip c's rows from row
-    // clip_row[c] on (host [B]; NULL: packed); rows_cap then bounds embd alone
-    const q2a_feat_dst * dst;
-    const int32_t * clip_row;
-    // the inputs_embeds form (with dst, clip_row NULL): the row map comes from ids->input_ids on the device, and the
-    // text rows are gathered from ids->embed_table
-    const q2a_embeds_src * ids;
-    frontend_src src() const { return {pcm, stride, mel, ld}; }
-};
-
 // whisper_encoder_output_with_state's too-short rule (:2356-2365) for a clip of n samples encoded from frame seek
 bool clip_has_window(const q2a_engine * e, int n, int seek) {
     const int n_len_org = 1 + (n + 200 - 400) / 160;   // mel.n_len_org (:2613), C truncation
     return n > 200 && (e->force_encode || !(n_len_org < seek + 100));
+}
+
+// What a call derives from each clip, in one host pass that checks nothing (the range checks are prepare_meta's): the
+// frame its window starts at, and whether it is encoded (PCM: the too-short rule; log-mel: always). features_check,
+// prepare_meta and the out_len of encode() all read these.
+struct clip_facts {
+    std::vector<int32_t> seek;
+    std::vector<uint8_t> ok;
+};
+clip_facts resolve_clips(const q2a_engine * e, const clip_input & in) {
+    clip_facts f;
+    f.seek.resize(in.B);
+    f.ok.resize(in.B);
+    for (int i = 0; i < in.B; ++i) {
+        f.seek[i] = in.mel ? (in.seek ? in.seek[i] : 0) : (in.offs ? in.offs[i] : in.offset_ms) / 10;
+        f.ok[i] = in.mel || clip_has_window(e, in.len[i], f.seek[i]);
+    }
+    return f;
 }
 
 // the packed layout of a call (host): q2a_varlen_rows over the clips' key lengths, with no rows for a clip whose
@@ -1418,42 +742,40 @@ int packed_layout_of(const q2a_engine * e, const int32_t * key_len, const int32_
 // copy with what the kind adds: 3 B words (plain), 5 B with the key lengths (padded), 6 B + 1 with their packed layout
 // (packed), 7 B + 2 with the packed output layout behind it (the audio-feature tail). `rows` receives what the blocks
 // of the call run on.
-int prepare_meta(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s, int & max_frames, block_rows & rows) {
-    const int B = c.B;
-    const int64_t max_valid = c.stride > 0 ? c.stride : -1;   // stride 0: shared PCM
+int prepare_meta(q2a_engine * e, encode_kind kind, const clip_input & in, const clip_facts & f, const int32_t * kl, const out_sink & sink,
+                 int32_t * status, hipStream_t s, int & max_frames, block_rows & rows) {
+    const int B = in.B;
     const meta_rows dev(e->meta, B);
     rows = block_rows{B, B * e->d.T, e->X, kind == ENC_PLAIN ? nullptr : dev.key_len, nullptr, 0};
     max_frames = 0;
     const auto last = kind == ENC_PLAIN ? &meta_rows::clip_max : kind == ENC_PADDED ? &meta_rows::row_start
-                      : !c.features ? &meta_rows::out_start : (c.dst && c.clip_row) ? &meta_rows::end_to : &meta_rows::end;
+                      : !sink.features() ? &meta_rows::out_start : sink.clip_row ? &meta_rows::end_to : &meta_rows::end;
     return upload_meta(e, B, &meta_rows::nsamp, last, s, [&](const meta_rows & mh) -> int {
-        if (c.mel && c.stride != 0 && c.stride < e->d.M * c.ld) { set_err("clip_stride %lld below n_mels * ld", (long long) c.stride); return Q2A_ERR_ARG; }
+        if (in.mel && in.stride != 0 && in.stride < e->d.M * in.ld) { set_err("clip_stride %lld below n_mels * ld", (long long) in.stride); return Q2A_ERR_ARG; }
         for (int i = 0; i < B; ++i) {
-            const int seek = c.mel ? (c.seek ? c.seek[i] : 0) : (c.offs ? c.offs[i] : c.offset_ms) / 10;
-            if (seek < 0) { set_err("clip %d: negative offset", i); return Q2A_ERR_ARG; }
-            const int n = c.n_samples[i];
-            bool ok = true;
-            if (c.mel) {   // log-mel input: n is n_len (into the nsamp row); no 1 s rule at this level, every clip is encoded
-                if (n < 1 || n > c.ld) { set_err("clip %d: n_len %d outside 1..ld", i, n); return Q2A_ERR_ARG; }
-            } else {
-                if (n < 0 || (max_valid >= 0 && n > max_valid)) { set_err("clip %d: bad n_samples %d", i, n); return Q2A_ERR_ARG; }
-                ok = clip_has_window(e, n, seek);
+            if (f.seek[i] < 0) { set_err("clip %d: negative offset", i); return Q2A_ERR_ARG; }
+            const int n = in.len[i];
+            // (log-mel: n is n_len, into the nsamp row. PCM: at most the stride, unless the clips share one array)
+            if (in.mel ? n < 1 || n > in.ld : n < 0 || (in.stride > 0 && n > in.stride)) {
+                if (in.mel) set_err("clip %d: n_len %d outside 1..ld", i, n); else set_err("clip %d: bad n_samples %d", i, n);
+                return Q2A_ERR_ARG;
             }
+            const bool ok = f.ok[i];
             mh.nsamp[i] = ok ? n : 0;
-            mh.seek[i] = seek;
+            mh.seek[i] = f.seek[i];
             mh.clip_ok[i] = ok ? 1 : 0;
-            if (c.status) c.status[i] = ok ? Q2A_CLIP_ENCODED : Q2A_CLIP_SKIPPED;
+            if (status) status[i] = ok ? Q2A_CLIP_ENCODED : Q2A_CLIP_SKIPPED;
             max_frames = std::max(max_frames, (int) (((int64_t) mh.nsamp[i] + 480000) / 160));
             // the clip_max row lies between clip_ok and the key lengths, inside the copy: it is device-written, and
             // run_frontend resets it after this copy on the same stream, to the value uploaded here
-            if (kind != ENC_PLAIN) { mh.clip_max[i] = (int32_t) 0x80808080u; mh.key_len[i] = c.kl[i]; }
-            if (c.features && c.dst && c.clip_row) mh.clip_row[i] = c.clip_row[i];
+            if (kind != ENC_PLAIN) { mh.clip_max[i] = (int32_t) 0x80808080u; mh.key_len[i] = kl[i]; }
+            if (sink.clip_row) mh.clip_row[i] = sink.clip_row[i];
         }
         if (kind != ENC_PACKED) return Q2A_OK;
         rows.X = e->Xp;
         rows.row_start = dev.row_start;
         // a clip that is not encoded has no rows
-        return packed_layout_of(e, mh.key_len, mh.clip_ok, mh.row_start, rows, c.features ? mh.out_start : nullptr);
+        return packed_layout_of(e, mh.key_len, mh.clip_ok, mh.row_start, rows, sink.features() ? mh.out_start : nullptr);
     });
 }
 
@@ -1492,16 +814,17 @@ hipError_t launch_zero_tail_rows(float * out, const int32_t * key_len, const int
     return hipGetLastError();
 }
 
-// the per-clip key lengths of a padded encode: the caller's (checked), or q2a_valid_lengths' enc_len
-int padded_key_lens(q2a_engine * e, const int32_t * n_samples, const int32_t * offs, const int32_t * key_len, int B,
-                    std::vector<int32_t> & kl) {
-    kl.resize(B);
-    for (int c = 0; c < B; ++c) {
+// the per-clip key lengths of a padded or variable-length encode: the caller's (checked), or the enc_len of
+// q2a_valid_lengths (PCM) / q2a_mel_valid_lengths (log-mel)
+int key_lens(const q2a_engine * e, const clip_input & in, const int32_t * key_len, std::vector<int32_t> & kl) {
+    kl.resize(in.B);
+    for (int c = 0; c < in.B; ++c) {
         if (key_len) {
             kl[c] = key_len[c];
             if (kl[c] < 1 || kl[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, kl[c], e->d.T); return Q2A_ERR_ARG; }
-        } else if (q2a_valid_lengths(n_samples[c], offs ? offs[c] : 0, e->d.T, &kl[c], nullptr) != Q2A_OK) {
-            set_err("clip %d: bad n_samples %d or offset", c, n_samples[c]);
+        } else if ((in.mel ? q2a_mel_valid_lengths(in.len[c], in.seek ? in.seek[c] : 0, e->d.T, &kl[c], nullptr)
+                           : q2a_valid_lengths(in.len[c], in.offs ? in.offs[c] : in.offset_ms, e->d.T, &kl[c], nullptr)) != Q2A_OK) {
+            set_err(in.mel ? "clip %d: bad n_len %d or seek" : "clip %d: bad n_samples %d or offset", c, in.len[c]);
             return Q2A_ERR_ARG;
         }
     }
@@ -1705,43 +1028,37 @@ hipError_t launch_feat_row_map(const int32_t * out_start, const int32_t * clip_r
 // the checks of the audio-feature tail, made before anything is launched or written: the outputs, the projector, and the
 // packed rows against rows_cap (the clips the too-short rule skips have none); for the _to form the destination and
 // q2a_feat_rows' checks of the clips' ranges in it, rows_cap then bounding embd alone
-int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
-    if (c.dst) {
-        if (c.feat) { set_err("audio features: feat and dst exclude each other"); return Q2A_ERR_ARG; }
-        if (int rc = feat_dst_check(c.proj, c.dst)) return rc;
-        if (c.ids) {
-            if (c.clip_row) { set_err("audio features: clip_row and input_ids exclude each other"); return Q2A_ERR_ARG; }
-            if (int rc = embeds_src_check(c.ids, *c.dst, c.proj->d_out)) return rc;
-        }
+int features_check(const q2a_engine * e, const clip_facts & f, const int32_t * kl, const out_sink & k, const q2a_projector * proj) {
+    if (k.to_dst()) {
+        if (int rc = feat_dst_check(proj, k.dst)) return rc;
+        if (k.kind == out_sink::IDS)
+            if (int rc = embeds_src_check(k.ids, *k.dst, proj->d_out)) return rc;
     } else {
-        if (!c.feat && !c.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
-        if (c.proj ? !c.feat : c.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
+        if (!k.feat && !k.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
+        if (proj ? !k.feat : k.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
     }
-    if (c.proj && (c.proj->device != e->device || c.proj->d_in != e->d.D)) {
-        set_err("audio features: projector on device %d with d_in %d, engine on device %d with n_audio_state %d", c.proj->device,
-                c.proj->d_in, e->device, e->d.D);
+    if (proj && (proj->device != e->device || proj->d_in != e->d.D)) {
+        set_err("audio features: projector on device %d with d_in %d, engine on device %d with n_audio_state %d", proj->device,
+                proj->d_in, e->device, e->d.D);
         return Q2A_ERR_ARG;
     }
+    const int B = (int) f.ok.size();
+    std::vector<int32_t> ol(B);
     int64_t n_tot = 0;
-    for (int i = 0; i < c.B; ++i) {
-        if (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) n_tot += c.kl[i] / 2;
+    for (int i = 0; i < B; ++i) {
+        ol[i] = f.ok[i] ? kl[i] / 2 : 0;
+        n_tot += ol[i];
     }
-    if (c.dst && c.ids) {
+    if (k.kind == out_sink::IDS) {
         // (no clip ranges: the k-th feature row goes where the k-th audio token is, a row without one is dropped)
         if (n_tot > (1 << 30) / 4) { set_err("audio features: %lld output rows", (long long) n_tot); return Q2A_ERR_ARG; }
-        if (!c.embd) return Q2A_OK;
-    } else if (c.dst) {
-        std::vector<int32_t> ol(c.B);
-        for (int i = 0; i < c.B; ++i)
-            ol[i] = (mel || clip_has_window(e, c.n_samples[i], (c.offs ? c.offs[i] : c.offset_ms) / 10)) ? c.kl[i] / 2 : 0;
-        if (q2a_feat_rows(ol.data(), c.clip_row, c.B, c.dst->n_rows, nullptr) < 0) {
-            set_err("audio features: a clip's destination rows start below 0, end past n_rows %lld, or overlap another clip's",
-                    (long long) c.dst->n_rows);
-            return Q2A_ERR_ARG;
-        }
-        if (!c.embd) return Q2A_OK;
+    } else if (k.kind == out_sink::ROWS && q2a_feat_rows(ol.data(), k.clip_row, B, k.dst->n_rows, nullptr) < 0) {
+        set_err("audio features: a clip's destination rows start below 0, end past n_rows %lld, or overlap another clip's",
+                (long long) k.dst->n_rows);
+        return Q2A_ERR_ARG;
     }
-    if (n_tot > c.rows_cap) { set_err("audio features: %lld output rows, rows_cap %lld", (long long) n_tot, (long long) c.rows_cap); return Q2A_ERR_ARG; }
+    if (k.to_dst() && !k.embd) return Q2A_OK;   // (rows_cap bounds embd alone)
+    if (n_tot > k.rows_cap) { set_err("audio features: %lld output rows, rows_cap %lld", (long long) n_tot, (long long) k.rows_cap); return Q2A_ERR_ARG; }
     return Q2A_OK;
 }
 
@@ -1752,44 +1069,48 @@ int features_check(const q2a_engine * e, const encode_call & c, bool mel) {
 // attention's 16-query block) are gathered into one [M_tot][D] stream, the blocks run on those M_tot rows, and the pool
 // reads them back into out, zeros past each clip's valid length. Row for row the padded encode's operations: the same
 // bytes.
-// ENC_PACKED with c.features (q2a_audio_features_*): the same up to and including the blocks; then the pool kernel
-// writes the valid output rows alone, packed (q2a_packed_out_rows), as f32 and / or as the projector GEMM's A operand,
-// and that GEMM writes the features. c.out is not read.
-int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t s) {
+// ENC_PACKED with a feature sink (q2a_audio_features_*, q2a_inputs_embeds_*): the same up to and including the blocks;
+// then the pool kernel writes the valid output rows alone, packed (q2a_packed_out_rows), as f32 and / or as the
+// projector GEMM's A operand, and that GEMM writes the features.
+// kl: the checked key lengths (ENC_PADDED, ENC_PACKED). out_len: NULL, or the clips' valid output rows (the same
+// kinds). status: NULL, or Q2A_CLIP_* per clip.
+int encode(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_t * kl, const out_sink & sink, q2a_projector * proj,
+           int32_t * out_len, int32_t * status, hipStream_t s) {
     const dims & d = e->d;
-    const int B = c.B;
-    const bool feats = kind == ENC_PACKED && c.features;
-    if (B <= 0 || !(c.pcm || c.mel) || !c.n_samples || !(c.out || feats) || (kind != ENC_PLAIN && !c.kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (c.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
+    const int B = in.B;
+    const bool feats = sink.features();
+    if (B <= 0 || !in.data || !in.len || (feats ? kind != ENC_PACKED : !sink.out) || (kind != ENC_PLAIN && !kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (in.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
     int rc = lens_supported(e, kind);
     if (rc) return rc;
-    if (feats && (rc = features_check(e, c, c.mel != nullptr))) return rc;
+    const clip_facts facts = resolve_clips(e, in);
+    if (feats && (rc = features_check(e, facts, kl, sink, proj))) return rc;
     HIP_TRY(hipSetDevice(e->device));
     if ((rc = reserve(e, B))) return rc;
     if (kind == ENC_PACKED && (rc = ensure_packed(e))) return rc;
     int max_frames = 0;
     block_rows rows;
-    if ((rc = prepare_meta(e, kind, c, s, max_frames, rows))) return rc;
-    const meta_rows dev(e->meta, B), host(e->meta_host, B);
-    if (kind != ENC_PLAIN && c.out_len)
-        for (int i = 0; i < B; ++i) c.out_len[i] = host.clip_ok[i] ? c.kl[i] / 2 : 0;
+    if ((rc = prepare_meta(e, kind, in, facts, kl, sink, status, s, max_frames, rows))) return rc;
+    const meta_rows dev(e->meta, B);
+    if (kind != ENC_PLAIN && out_len)
+        for (int i = 0; i < B; ++i) out_len[i] = facts.ok[i] ? kl[i] / 2 : 0;
     // the projector's operand buffers, before the first launch (growing them waits for the stream)
     proj_operand po{nullptr, nullptr, nullptr, 0};
-    const q2a_embeds_src * ids = feats && c.dst ? c.ids : nullptr;
-    if (feats && c.proj && (rows.N_out > 0 || ids) &&
-        (rc = proj_workspace(c.proj, rows.N_out, s, po, c.dst && c.clip_row, ids ? ids->n_tokens : 0))) return rc;
+    const q2a_embeds_src * ids = sink.ids;
+    if (feats && proj && (rows.N_out > 0 || ids) &&
+        (rc = proj_workspace(proj, rows.N_out, s, po, sink.clip_row != nullptr, ids ? ids->n_tokens : 0))) return rc;
     if (ids) {
         // the inputs_embeds form: the row map from input_ids (and the report), then the text rows; they run whether or
         // not the call has a feature row
         int32_t * report = ids->report_dev ? ids->report_dev : po.report;
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_audio_token_rows(ids_args(ids->input_ids, ids->ids_width, ids->n_tokens, ids->audio_token_id,
                                                                           rows.N_out, po, report), s));
-        if (ids->embed_table) PLAUNCH(e, s, Q2A_PROF_POOL, launch_embeds_gather(*ids, *c.dst, c.proj->d_out, report, s));
+        if (ids->embed_table) PLAUNCH(e, s, Q2A_PROF_POOL, launch_embeds_gather(*ids, *sink.dst, proj->d_out, report, s));
     }
     // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros. The
     // audio-feature tail writes valid rows only: without any, nothing is launched behind the metadata)
     if (feats ? rows.N_out > 0 : kind != ENC_PACKED || rows.M > 0) {
-        if ((rc = run_frontend(e, c.src(), B, max_frames, s))) return rc;
+        if ((rc = run_frontend(e, in, max_frames, s))) return rc;
         if (kind == ENC_PACKED)
             PLAUNCH(e, s, Q2A_PROF_POOL, launch_gather_rows(e->X, e->Xp, dev.row_start, B, d.T, d.D, rows.r_max, s));
         for (int l = 0; l < d.L; ++l)
@@ -1800,24 +1121,24 @@ int encode(q2a_engine * e, encode_kind kind, const encode_call & c, hipStream_t 
         // the valid rows alone, packed: f32 into embd and / or the projector GEMM's A operand straight from the pool
         // kernel's registers, then that GEMM with its bias epilogue into feat
         if (rows.N_out == 0) return Q2A_OK;
-        q2a_pool_pack_args pa{e->Xp, B, d.D, rows.N_out, lnw, lnb, dev.row_start, dev.out_start, c.embd,
-                              c.proj ? proj_mode(c.proj) : -1, po.A, po.dy, po.aext, po.ld};
+        q2a_pool_pack_args pa{e->Xp, B, d.D, rows.N_out, lnw, lnb, dev.row_start, dev.out_start, sink.embd,
+                              proj ? proj_mode(proj) : -1, po.A, po.dy, po.aext, po.ld};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_pack(pa, s));
-        if (c.dst) {
+        if (sink.to_dst()) {
             // the _to form: the device row map from the uploaded out_start and clip_row (none when packed), then the
             // same GEMM with the row-map epilogue straight into the caller's rows
             if (po.map && !ids) PLAUNCH(e, s, Q2A_PROF_POOL, launch_feat_row_map(dev.out_start, dev.clip_row, po.map, B, d.TO, s));
-            LAUNCH(q2a_launch_gemm(proj_gemm_to(c.proj, rows.N_out, po, *c.dst, po.map), Q2A_EPI_STORE_ROWS, c.proj->gblk, s));
-        } else if (c.proj) {
-            LAUNCH(q2a_launch_gemm(proj_gemm(c.proj, rows.N_out, po, c.feat), Q2A_EPI_STORE_F, c.proj->gblk, s));
+            LAUNCH(q2a_launch_gemm(proj_gemm_to(proj, rows.N_out, po, *sink.dst, po.map), Q2A_EPI_STORE_ROWS, proj->gblk, s));
+        } else if (proj) {
+            LAUNCH(q2a_launch_gemm(proj_gemm(proj, rows.N_out, po, sink.feat), Q2A_EPI_STORE_F, proj->gblk, s));
         }
     } else if (kind == ENC_PACKED) {
-        q2a_pool_varlen_args pa{e->Xp, B, d.T, d.D, lnw, lnb, c.out, dev.key_len, dev.row_start};
+        q2a_pool_varlen_args pa{e->Xp, B, d.T, d.D, lnw, lnb, sink.out, dev.key_len, dev.row_start};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln_varlen(pa, s));
     } else {
-        q2a_pool_args pa{e->X, B, d.T, d.D, lnw, lnb, c.out, dev.clip_ok};
+        q2a_pool_args pa{e->X, B, d.T, d.D, lnw, lnb, sink.out, dev.clip_ok};
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_pool_ln(pa, s));
-        if (kind == ENC_PADDED) PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(c.out, dev.key_len, dev.clip_ok, B, d.TO, d.D, s));
+        if (kind == ENC_PADDED) PLAUNCH(e, s, Q2A_PROF_POOL, launch_zero_tail_rows(sink.out, dev.key_len, dev.clip_ok, B, d.TO, d.D, s));
     }
     return Q2A_OK;
 }
@@ -1986,38 +1307,155 @@ int q2a_reserve(q2a_engine * e, int max_clips, int64_t max_samples) {
     return reserve(e, max_clips);
 }
 
+// the prologue of every encode and feature entry point: arguments, activation contract, and for the key-length kinds
+// the key lengths into kl (the caller's, checked, or the input's own valid lengths)
+static int call_prologue(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_t * key_len, std::vector<int32_t> & kl) {
+    if (!e || !in.len || in.B <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = lens_supported(e, kind)) return rc;
+    return kind == ENC_PLAIN ? Q2A_OK : key_lens(e, in, key_len, kl);
+}
+
+// the `kind` argument of the log-mel entry points (Q2A_ENCODE_*) as the engine's; false: there is no such kind
+static bool kind_of(int kind, encode_kind & ek) {
+    ek = kind == Q2A_ENCODE_PLAIN ? ENC_PLAIN : kind == Q2A_ENCODE_PADDED ? ENC_PADDED : ENC_PACKED;
+    if (kind >= Q2A_ENCODE_PLAIN && kind <= Q2A_ENCODE_VARLEN) return true;
+    set_err("invalid arguments");
+    return false;
+}
+
+// Every device entry point: the prologue, what the sink requires, then the encode on the caller's stream
+static int encode_device(q2a_engine * e, encode_kind kind, q2a_projector * p, const clip_input & in, const int32_t * key_len,
+                         const out_sink & sink, int32_t * out_len, int32_t * status, void * stream) {
+    std::vector<int32_t> kl;
+    if (int rc = call_prologue(e, kind, in, key_len, kl)) return rc;
+    if (!in.data) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    // (without dst a _to call would be the f32 one's "embd alone")
+    if (sink.to_dst() && !(p && sink.dst)) { set_err("audio features: the _to calls need a projector and a destination"); return Q2A_ERR_ARG; }
+    if (sink.kind == out_sink::IDS && !sink.ids) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
+    return encode(e, kind, in, kind == ENC_PLAIN ? nullptr : kl.data(), sink, p, out_len, status, call_stream(stream));
+}
+
 int q2a_encode_device(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                       int n_clips, int offset_ms, float * out_dev, int32_t * status, void * stream) {
-    if (!e) return Q2A_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    return encode(e, ENC_PLAIN, {pcm_dev, pcm_stride, n_samples, n_clips, offset_ms, nullptr, nullptr, out_dev, nullptr, status},
-                  call_stream(stream));
+    return encode_device(e, ENC_PLAIN, nullptr, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, nullptr, offset_ms), nullptr,
+                         window_sink(out_dev), nullptr, status, stream);
 }
 
 int q2a_encode_device_ex(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                          const int32_t * offsets_ms, int n_clips, float * out_dev, int32_t * status, void * stream) {
-    if (!e || !offsets_ms) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    HIP_TRY(hipSetDevice(e->device));
-    return encode(e, ENC_PLAIN, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, nullptr, out_dev, nullptr, status},
-                  call_stream(stream));
+    if (!offsets_ms) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    return encode_device(e, ENC_PLAIN, nullptr, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), nullptr,
+                         window_sink(out_dev), nullptr, status, stream);
 }
 
-int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, int n_clips, int offset_ms,
-                    float * out_host, int32_t * status) {
-    return q2a_encode_host_ex(e, pcm, n_samples, nullptr, n_clips, offset_ms, out_host, status);
+int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PADDED, nullptr, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         window_sink(out_dev), out_len, status, stream);
 }
 
-// q2a_encode_host_ex (ENC_PLAIN), q2a_encode_host_padded and q2a_encode_host_varlen (each chunk of clips packed on its
-// own), the latter two with kl (host [n_clips] key lengths, already checked): every clip's output is then copied back
-// (rows past its valid length, and a skipped clip's rows, are zeros).
-// q2a_encode_host_mel: `mel` set (clip c: [n_mels][n_len[c]] host floats; pcm, n_samples and the offsets are then not
-// read). Only the window columns seek .. min(seek + 2 n_ctx, n_len) - 1 of each row are staged, as clip c of a device
-// array [chunk][n_mels][2 n_ctx] that the encode reads from frame 0.
-struct host_mel {
-    const float * const * mel;
-    const int32_t * n_len;
-    const int32_t * seek;       // NULL: 0
+int q2a_encode_device_varlen(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
+                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PACKED, nullptr, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         window_sink(out_dev), out_len, status, stream);
+}
+
+int q2a_encode_device_mel(q2a_engine * e, int kind, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                          const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                          float * out_dev, int32_t * out_len, int32_t * status, void * stream) {
+    encode_kind ek;
+    if (!kind_of(kind, ek)) return Q2A_ERR_ARG;
+    return encode_device(e, ek, nullptr, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len, window_sink(out_dev),
+                         out_len, status, stream);
+}
+
+// ---- audio features: the variable-length encode with its valid output rows packed and projected; the _to form with
+// dst and clip_row in place of feat, the inputs_embeds form with src in place of clip_row ---------------------------
+int q2a_audio_features_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                              const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                              float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                              void * stream) {
+    return encode_device(e, ENC_PACKED, p, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         packed_sink(feat_dev, embd_dev, rows_cap), out_len, status, stream);
+}
+
+int q2a_audio_features_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                  float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
+                                  void * stream) {
+    return encode_device(e, ENC_PACKED, p, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len,
+                         packed_sink(feat_dev, embd_dev, rows_cap), out_len, status, stream);
+}
+
+int q2a_audio_features_device_to(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                                 const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev, int64_t embd_rows_cap,
+                                 int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PACKED, p, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         rows_sink(dst, clip_row, embd_dev, embd_rows_cap), out_len, status, stream);
+}
+
+int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                     const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                     const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev,
+                                     int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PACKED, p, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len,
+                         rows_sink(dst, clip_row, embd_dev, embd_rows_cap), out_len, status, stream);
+}
+
+int q2a_inputs_embeds_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                             const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                             const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev, int64_t embd_rows_cap,
+                             int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PACKED, p, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         ids_sink(dst, src, embd_dev, embd_rows_cap), out_len, status, stream);
+}
+
+int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                 const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                 const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
+                                 int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    return encode_device(e, ENC_PACKED, p, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len,
+                         ids_sink(dst, src, embd_dev, embd_rows_cap), out_len, status, stream);
+}
+
+// ---- the host entry points -------------------------------------------------------------------------------------
+// Their clips: `in` describes them as for a device call (data NULL), ptr[c] is clip c's PCM, or its log-mel
+// [n_mels][len[c]] host floats
+namespace {
+struct host_clips {
+    clip_input in;
+    const float * const * ptr;
 };
+// the staged log-mel windows of a chunk as its encode sees them (stage_chunk)
+struct chunk_windows {
+    std::vector<int32_t> len, seek;
+};
+}
+
+// checked before any copy (a negative count would be a huge memcpy); a bad clip fails every clip of the call
+static int host_clips_check(const host_clips & h, int32_t * status) {
+    const clip_input & in = h.in;
+    for (int c = 0; c < in.B; ++c) {
+        const int n = in.len[c], sk = in.mel && in.seek ? in.seek[c] : 0;
+        if (in.mel ? n >= 1 && h.ptr[c] && sk >= 0 : n >= 0 && (n == 0 || h.ptr[c])) continue;
+        set_err("clip %d: bad %s (%d, seek %d, %p)", c, in.mel ? "mel" : "samples", n, sk, (const void *) h.ptr[c]);
+        if (status) for (int k = 0; k < in.B; ++k) status[k] = Q2A_CLIP_FAILED;
+        return Q2A_ERR_ARG;
+    }
+    return Q2A_OK;
+}
+
+// floats per staged clip of the chunk [c0, c0 + n): the longest PCM clip (whole 64s), or one log-mel window
+static int64_t stage_stride(const q2a_engine * e, const host_clips & h, int c0, int n) {
+    if (h.in.mel) return (int64_t) e->d.M * e->d.TM;
+    int64_t maxn = 1;
+    for (int c = 0; c < n; ++c) maxn = std::max<int64_t>(maxn, h.in.len[c0 + c]);
+    return (maxn + 63) & ~int64_t(63);
+}
+
 // one clip's window columns of every mel row -> dst [M][TM], and the window as the encode then sees it: win_len frames
 // read from frame win_seek (preset by the caller to 1 and 0)
 static void stage_mel_window(float * dst, const float * mel, int64_t n_len, int64_t seek, int M, int TM, int32_t & win_len,
@@ -2027,20 +1465,36 @@ static void stage_mel_window(float * dst, const float * mel, int64_t n_len, int6
     if (w > 0) win_len = w; else win_seek = 1;
     for (int j = 0; j < M && w > 0; ++j) memcpy(dst + (int64_t) j * TM, mel + j * n_len + seek, (size_t) w * 4);
 }
-static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * const * pcm, const int32_t * n_samples,
-                            const int32_t * offsets_ms, int n_clips, int offset_ms, float * out_host, int32_t * status,
-                            const int32_t * kl, int32_t * out_len, const host_mel * hm = nullptr) {
-    if (!e || !(hm ? hm->mel && hm->n_len : pcm && n_samples) || !out_host || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    for (int c = 0; c < n_clips; ++c) {   // (checked before any copy: a negative count would be a huge memcpy)
-        const bool bad = hm ? hm->n_len[c] < 1 || !hm->mel[c] || (hm->seek && hm->seek[c] < 0)
-                            : n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c]);
-        if (bad) {
-            if (hm) set_err("clip %d: bad mel (n_len %d, seek %d, %p)", c, hm->n_len[c], hm->seek ? hm->seek[c] : 0, (const void *) hm->mel[c]);
-            else set_err("clip %d: bad samples (%d, %p)", c, n_samples[c], (const void *) pcm[c]);
-            if (status) for (int k = 0; k < n_clips; ++k) status[k] = Q2A_CLIP_FAILED;
-            return Q2A_ERR_ARG;
-        }
+
+// The chunk [c0, c0 + n) staged into dst [n][maxn] (host), and the input its encode takes once dst has been copied to
+// d_in. PCM: the clips' samples. Log-mel: only the window columns seek .. min(seek + 2 n_ctx, n_len) - 1 of each row, as
+// clip c of an array [n][n_mels][2 n_ctx] that the encode reads from frame 0; `win` holds those windows' lengths and
+// seeks for as long as the input is used.
+static clip_input stage_chunk(const q2a_engine * e, const host_clips & h, int c0, int n, int64_t maxn, float * dst, const float * d_in,
+                              chunk_windows & win) {
+    const clip_input & in = h.in;
+    if (!in.mel) {
+        for (int c = 0; c < n; ++c)
+            if (in.len[c0 + c] > 0) memcpy(dst + c * maxn, h.ptr[c0 + c], (size_t) in.len[c0 + c] * 4);
+        return pcm_input(d_in, maxn, in.len + c0, n, in.offs ? in.offs + c0 : nullptr, in.offset_ms);
     }
+    win.len.assign(n, 1);
+    win.seek.assign(n, 0);
+    for (int c = 0; c < n; ++c)
+        stage_mel_window(dst + c * maxn, h.ptr[c0 + c], in.len[c0 + c], in.seek ? in.seek[c0 + c] : 0, e->d.M, e->d.TM, win.len[c], win.seek[c]);
+    return mel_input(d_in, maxn, e->d.TM, win.len.data(), win.seek.data(), n);
+}
+
+// q2a_encode_host* of any kind (ENC_PACKED: each chunk of clips packed on its own). For the key-length kinds every
+// clip's output is copied back (rows past its valid length, and a skipped clip's rows, are zeros).
+static int encode_host(q2a_engine * e, encode_kind kind, const host_clips & h, const int32_t * key_len, float * out_host,
+                       int32_t * out_len, int32_t * status) {
+    std::vector<int32_t> klv;
+    if (int rc = call_prologue(e, kind, h.in, key_len, klv)) return rc;
+    const int32_t * kl = kind == ENC_PLAIN ? nullptr : klv.data();
+    const int n_clips = h.in.B;
+    if (!h.ptr || !out_host) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = host_clips_check(h, status)) return rc;
     HIP_TRY(hipSetDevice(e->device));
     // Chunks of clips through two staging sets: chunk k's host->pinned copy and H2D (copy stream) run while chunk k-1
     // encodes (compute stream), and chunk k-1's D2H + pinned->host copy while chunk k encodes. One chunk below 32
@@ -2049,12 +1503,8 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
     // Outputs of skipped clips (< 1 s after the offset) are never copied back: the caller's contents stay untouched.
     const int nchunk = n_clips < 32 ? 1 : std::max(2, (n_clips + 63) / 64);
     const int C = (n_clips + nchunk - 1) / nchunk;
-    int64_t maxn = 1;
-    for (int c = 0; !hm && c < n_clips; ++c) maxn = std::max<int64_t>(maxn, n_samples[c]);
-    maxn = (maxn + 63) & ~int64_t(63);
-    const int M = e->d.M, TM = e->d.TM;
-    if (hm) maxn = (int64_t) M * TM;   // one staged window per clip
-    std::vector<int32_t> win_len, win_seek;   // the staged windows of a chunk as the encode sees them
+    const int64_t maxn = stage_stride(e, h, 0, n_clips);
+    chunk_windows win;
     if (int rc = ensure_host_bufs(e, C, maxn)) return rc;
     const size_t per_out = (size_t) e->d.TO * e->d.D;
     // st: what encode reported per clip; pub: what the caller gets — a clip's status is published only once its
@@ -2079,13 +1529,7 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
         q2a_engine::host_buf & b = e->hb[k & 1];
         // staging set k&1 was last used by chunk k-2: its H2D must have left pin_in, its D2H must have left d_out
         if (hipEventSynchronize(b.h2d) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        for (int c = 0; !hm && c < n; ++c) {
-            memcpy(b.pin_in + c * maxn, pcm[c0 + c], (size_t) n_samples[c0 + c] * 4);
-        }
-        if (hm) { win_len.assign(n, 1); win_seek.assign(n, 0); }
-        for (int c = 0; hm && c < n; ++c)
-            stage_mel_window(b.pin_in + c * maxn, hm->mel[c0 + c], hm->n_len[c0 + c], hm->seek ? hm->seek[c0 + c] : 0, M, TM,
-                             win_len[c], win_seek[c]);
+        const clip_input in = stage_chunk(e, h, c0, n, maxn, b.pin_in, b.d_in, win);
         if (hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||   // chunk k-2's encode no longer reads d_in
             hipMemcpyAsync(b.d_in, b.pin_in, (size_t) n * maxn * 4, hipMemcpyHostToDevice, cs) != hipSuccess ||
             hipEventRecord(b.h2d, cs) != hipSuccess ||
@@ -2094,12 +1538,7 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
             rc = Q2A_ERR_HIP;
             break;
         }
-        if (hm)
-            rc = encode(e, kind, {nullptr, maxn, win_len.data(), n, 0, nullptr, kl ? kl + c0 : nullptr, b.d_out,
-                                  out_len ? out_len + c0 : nullptr, st.data() + c0, b.d_in, TM, win_seek.data()}, s);
-        else
-            rc = encode(e, kind, {b.d_in, maxn, n_samples + c0, n, offset_ms, offsets_ms ? offsets_ms + c0 : nullptr,
-                                  kl ? kl + c0 : nullptr, b.d_out, out_len ? out_len + c0 : nullptr, st.data() + c0}, s);
+        rc = encode(e, kind, in, kl ? kl + c0 : nullptr, window_sink(b.d_out), nullptr, out_len ? out_len + c0 : nullptr, st.data() + c0, s);
         if (rc) break;
         if (hipEventRecord(b.comp, s) != hipSuccess || hipStreamWaitEvent(cs, b.comp, 0) != hipSuccess ||
             hipMemcpyAsync(b.pin_out, b.d_out, (size_t) n * per_out * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
@@ -2118,214 +1557,51 @@ static int encode_host_impl(q2a_engine * e, encode_kind kind, const float * cons
     return rc;
 }
 
+int q2a_encode_host(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, int n_clips, int offset_ms,
+                    float * out_host, int32_t * status) {
+    return q2a_encode_host_ex(e, pcm, n_samples, nullptr, n_clips, offset_ms, out_host, status);
+}
+
 int q2a_encode_host_ex(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                        int n_clips, int offset_ms, float * out_host, int32_t * status) {
-    return encode_host_impl(e, ENC_PLAIN, pcm, n_samples, offsets_ms, n_clips, offset_ms, out_host, status, nullptr, nullptr);
-}
-
-// the prologue of the padded and variable-length entry points: arguments, activation contract, the key lengths into kl
-static int lens_prologue(q2a_engine * e, encode_kind kind, const int32_t * n_samples, const int32_t * offsets_ms,
-                         const int32_t * key_len, int n_clips, std::vector<int32_t> & kl) {
-    if (!e || !n_samples || n_clips <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (int rc = lens_supported(e, kind)) return rc;
-    return padded_key_lens(e, n_samples, offsets_ms, key_len, n_clips, kl);
-}
-
-int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
-                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
-                             int32_t * out_len, int32_t * status, void * stream) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PADDED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode(e, ENC_PADDED, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), out_dev, out_len, status},
-                  call_stream(stream));
+    return encode_host(e, ENC_PLAIN, {pcm_input(nullptr, 0, n_samples, n_clips, offsets_ms, offset_ms), pcm}, nullptr, out_host, nullptr, status);
 }
 
 int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                            const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PADDED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode_host_impl(e, ENC_PADDED, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
-}
-
-int q2a_encode_device_varlen(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
-                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
-                             int32_t * out_len, int32_t * status, void * stream) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode(e, ENC_PACKED, {pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), out_dev, out_len, status},
-                  call_stream(stream));
+    return encode_host(e, ENC_PADDED, {pcm_input(nullptr, 0, n_samples, n_clips, offsets_ms), pcm}, key_len, out_host, out_len, status);
 }
 
 int q2a_encode_host_varlen(q2a_engine * e, const float * const * pcm, const int32_t * n_samples, const int32_t * offsets_ms,
                            const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    return encode_host_impl(e, ENC_PACKED, pcm, n_samples, offsets_ms, n_clips, 0, out_host, status, kl.data(), out_len);
-}
-
-// the prologue of the log-mel entry points: the kind, the activation contract, and for the key-length kinds the key
-// lengths into kl (the caller's, checked, or q2a_mel_valid_lengths' enc_len)
-static int mel_prologue(q2a_engine * e, int kind, const int32_t * n_len, const int32_t * seek, const int32_t * key_len,
-                        int n_clips, encode_kind & ek, std::vector<int32_t> & kl) {
-    if (!e || !n_len || n_clips <= 0 || kind < Q2A_ENCODE_PLAIN || kind > Q2A_ENCODE_VARLEN) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    ek = kind == Q2A_ENCODE_PLAIN ? ENC_PLAIN : kind == Q2A_ENCODE_PADDED ? ENC_PADDED : ENC_PACKED;
-    if (int rc = lens_supported(e, ek)) return rc;
-    if (ek == ENC_PLAIN) return Q2A_OK;
-    kl.resize(n_clips);
-    for (int c = 0; c < n_clips; ++c) {
-        if (key_len) {
-            kl[c] = key_len[c];
-            if (kl[c] < 1 || kl[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, kl[c], e->d.T); return Q2A_ERR_ARG; }
-        } else if (q2a_mel_valid_lengths(n_len[c], seek ? seek[c] : 0, e->d.T, &kl[c], nullptr) != Q2A_OK) {
-            set_err("clip %d: bad n_len %d or seek", c, n_len[c]);
-            return Q2A_ERR_ARG;
-        }
-    }
-    return Q2A_OK;
-}
-
-int q2a_encode_device_mel(q2a_engine * e, int kind, const float * mel_dev, int64_t clip_stride, int64_t ld,
-                          const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
-                          float * out_dev, int32_t * out_len, int32_t * status, void * stream) {
-    encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, kind, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    return encode(e, ek, {nullptr, clip_stride, n_len, n_clips, 0, nullptr, ek == ENC_PLAIN ? nullptr : kl.data(), out_dev,
-                          out_len, status, mel_dev, ld, seek}, call_stream(stream));
+    return encode_host(e, ENC_PACKED, {pcm_input(nullptr, 0, n_samples, n_clips, offsets_ms), pcm}, key_len, out_host, out_len, status);
 }
 
 int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, const int32_t * n_len, const int32_t * seek,
                         const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status) {
     encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, kind, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    const host_mel hm{mel, n_len, seek};
-    return encode_host_impl(e, ek, nullptr, nullptr, nullptr, n_clips, 0, out_host, status, ek == ENC_PLAIN ? nullptr : kl.data(),
-                            out_len, &hm);
+    if (!kind_of(kind, ek)) return Q2A_ERR_ARG;
+    return encode_host(e, ek, {mel_input(nullptr, 0, 0, n_len, seek, n_clips), mel}, key_len, out_host, out_len, status);
 }
 
-// ---- audio features: the variable-length encode with its valid output rows packed and projected -------------------
-static encode_call features_call(encode_call c, q2a_projector * p, float * feat, float * embd, int64_t rows_cap) {
-    c.out = nullptr;
-    c.features = true;
-    c.proj = p; c.feat = feat; c.embd = embd; c.rows_cap = rows_cap;
-    return c;
-}
-
-int q2a_audio_features_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
-                              const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
-                              float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
-                              void * stream) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    const encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
-    return encode(e, ENC_PACKED, features_call(c, p, feat_dev, embd_dev, rows_cap), call_stream(stream));
-}
-
-int q2a_audio_features_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
-                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
-                                  float * feat_dev, float * embd_dev, int64_t rows_cap, int32_t * out_len, int32_t * status,
-                                  void * stream) {
-    encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    const encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
-    return encode(e, ENC_PACKED, features_call(c, p, feat_dev, embd_dev, rows_cap), call_stream(stream));
-}
-
-// the _to form: dst and clip_row in place of feat and rows_cap; the projector and the destination are both required
-// (without dst the call would be the f32 one's "embd alone")
-static int features_to_check(const q2a_projector * p, const q2a_feat_dst * dst) {
-    if (p && dst) return Q2A_OK;
-    set_err("audio features: the _to calls need a projector and a destination");
-    return Q2A_ERR_ARG;
-}
-
-int q2a_audio_features_device_to(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
-                                 const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
-                                 const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev, int64_t embd_rows_cap,
-                                 int32_t * out_len, int32_t * status, void * stream) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    if (int rc = features_to_check(p, dst)) return rc;
-    encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
-    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
-    c.dst = dst; c.clip_row = clip_row;
-    return encode(e, ENC_PACKED, c, call_stream(stream));
-}
-
-int q2a_audio_features_device_mel_to(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
-                                     const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
-                                     const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev,
-                                     int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
-    encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (int rc = features_to_check(p, dst)) return rc;
-    encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
-    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
-    c.dst = dst; c.clip_row = clip_row;
-    return encode(e, ENC_PACKED, c, call_stream(stream));
-}
-
-// the inputs_embeds form: src in place of clip_row
-int q2a_inputs_embeds_device(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
-                             const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
-                             const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev, int64_t embd_rows_cap,
-                             int32_t * out_len, int32_t * status, void * stream) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    if (int rc = features_to_check(p, dst)) return rc;
-    if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
-    encode_call c{pcm_dev, pcm_stride, n_samples, n_clips, 0, offsets_ms, kl.data(), nullptr, out_len, status};
-    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
-    c.dst = dst; c.ids = src;
-    return encode(e, ENC_PACKED, c, call_stream(stream));
-}
-
-int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
-                                 const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
-                                 const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
-                                 int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
-    encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    if (!mel_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (int rc = features_to_check(p, dst)) return rc;
-    if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
-    encode_call c{nullptr, clip_stride, n_len, n_clips, 0, nullptr, kl.data(), nullptr, out_len, status, mel_dev, ld, seek};
-    c = features_call(c, p, nullptr, embd_dev, embd_rows_cap);
-    c.dst = dst; c.ids = src;
-    return encode(e, ENC_PACKED, c, call_stream(stream));
-}
-
-// The host variants, plain: chunks of up to 64 clips, each staged into device buffers of its own, run through the device
-// path on the engine's stream and waited for; a chunk's rows follow the previous chunk's in the caller's arrays. kl: the
-// checked key lengths. A clip's status is published once its chunk's rows reached the caller (Q2A_CLIP_FAILED before).
-static int features_host_impl(q2a_engine * e, q2a_projector * p, const float * const * pcm, const int32_t * n_samples,
-                              const int32_t * offsets_ms, const host_mel * hm, const int32_t * kl, int n_clips, float * feat,
-                              float * embd, int64_t rows_cap, int32_t * out_len, int32_t * status) {
-    auto fail_all = [&](int rc) {
-        if (status) for (int k = 0; k < n_clips; ++k) status[k] = Q2A_CLIP_FAILED;
-        return rc;
-    };
-    for (int c = 0; c < n_clips; ++c) {   // (checked before any copy: a negative count would be a huge memcpy)
-        const bool bad = hm ? hm->n_len[c] < 1 || !hm->mel[c] || (hm->seek && hm->seek[c] < 0)
-                            : n_samples[c] < 0 || (n_samples[c] > 0 && !pcm[c]);
-        if (bad) { set_err("clip %d: bad input", c); return fail_all(Q2A_ERR_ARG); }
-    }
-    const int32_t * lens = hm ? hm->n_len : n_samples;
-    encode_call all{};   // the whole batch against rows_cap, before anything is written
-    all.n_samples = lens; all.B = n_clips; all.offs = offsets_ms; all.kl = kl;
-    all = features_call(all, p, feat, embd, rows_cap);
-    if (int rc = features_check(e, all, hm != nullptr)) return rc;
+// The audio features of host clips: chunks of up to 64 clips, each staged into device buffers of its own, run through
+// the device path on the engine's stream and waited for; a chunk's rows follow the previous chunk's in the caller's
+// arrays. A clip's status is published once its chunk's rows reached the caller (Q2A_CLIP_FAILED before).
+static int features_host(q2a_engine * e, q2a_projector * p, const host_clips & h, const int32_t * key_len, float * feat, float * embd,
+                         int64_t rows_cap, int32_t * out_len, int32_t * status) {
+    std::vector<int32_t> klv;
+    if (int rc = call_prologue(e, ENC_PACKED, h.in, key_len, klv)) return rc;
+    const int32_t * kl = klv.data();
+    const int n_clips = h.in.B;
+    if (!h.ptr) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = host_clips_check(h, status)) return rc;
+    // the whole batch against rows_cap, before anything is written
+    if (int rc = features_check(e, resolve_clips(e, h.in), kl, packed_sink(feat, embd, rows_cap), p)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    const int M = e->d.M, TM = e->d.TM, D = e->d.D, d_out = p ? p->d_out : 0;
+    const int D = e->d.D, d_out = p ? p->d_out : 0;
     const int C = std::min(n_clips, 64);
-    std::vector<int32_t> st(n_clips, Q2A_CLIP_FAILED), ol(n_clips, 0), win_len, win_seek;
+    std::vector<int32_t> st(n_clips, Q2A_CLIP_FAILED), ol(n_clips, 0);
+    chunk_windows win;
     std::vector<float> stage;
     float * d_in = nullptr, * d_feat = nullptr, * d_embd = nullptr;
     auto release = [&]() {
@@ -2336,19 +1612,10 @@ static int features_host_impl(q2a_engine * e, q2a_projector * p, const float * c
     int rc = Q2A_OK;
     for (int c0 = 0; c0 < n_clips && rc == Q2A_OK; c0 += C) {
         const int n = std::min(C, n_clips - c0);
-        int64_t maxn = 64, cap = 1;
-        for (int c = 0; c < n; ++c) {
-            if (!hm) maxn = std::max<int64_t>(maxn, (n_samples[c0 + c] + 63) & ~63);
-            cap += kl[c0 + c] / 2;
-        }
-        if (hm) maxn = (int64_t) M * TM;   // one staged window per clip
+        const int64_t maxn = stage_stride(e, h, c0, n);
+        int64_t cap = 1;
+        for (int c = 0; c < n; ++c) cap += kl[c0 + c] / 2;
         stage.assign((size_t) n * maxn, 0.f);
-        if (hm) { win_len.assign(n, 1); win_seek.assign(n, 0); }
-        for (int c = 0; c < n; ++c) {
-            if (hm) stage_mel_window(stage.data() + c * maxn, hm->mel[c0 + c], hm->n_len[c0 + c], hm->seek ? hm->seek[c0 + c] : 0, M, TM,
-                                     win_len[c], win_seek[c]);
-            else if (n_samples[c0 + c] > 0) memcpy(stage.data() + c * maxn, pcm[c0 + c], (size_t) n_samples[c0 + c] * 4);
-        }
         if (hipMalloc((void **) &d_in, stage.size() * 4) != hipSuccess || (p && hipMalloc((void **) &d_feat, (size_t) cap * d_out * 4) != hipSuccess) ||
             (embd && hipMalloc((void **) &d_embd, (size_t) cap * D * 4) != hipSuccess)) {
             (void) hipGetLastError();
@@ -2356,12 +1623,9 @@ static int features_host_impl(q2a_engine * e, q2a_projector * p, const float * c
             rc = Q2A_ERR_OOM;
             break;
         }
+        const clip_input in = stage_chunk(e, h, c0, n, maxn, stage.data(), d_in, win);
         if (hipMemcpyAsync(d_in, stage.data(), stage.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess) { rc = Q2A_ERR_HIP; break; }
-        encode_call c = hm ? encode_call{nullptr, maxn, win_len.data(), n, 0, nullptr, kl + c0, nullptr, ol.data() + c0, st.data() + c0,
-                                         d_in, TM, win_seek.data()}
-                           : encode_call{d_in, maxn, n_samples + c0, n, 0, offsets_ms ? offsets_ms + c0 : nullptr, kl + c0, nullptr,
-                                         ol.data() + c0, st.data() + c0};
-        if ((rc = encode(e, ENC_PACKED, features_call(c, p, d_feat, d_embd, cap), s))) break;
+        if ((rc = encode(e, ENC_PACKED, in, kl + c0, packed_sink(d_feat, d_embd, cap), p, ol.data() + c0, st.data() + c0, s))) break;
         int64_t rows = 0;
         for (int c = 0; c < n; ++c) rows += ol[c0 + c];
         if ((p && rows && hipMemcpyAsync(feat + row0 * d_out, d_feat, (size_t) rows * d_out * 4, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -2392,21 +1656,13 @@ static int features_host_impl(q2a_engine * e, q2a_projector * p, const float * c
 int q2a_audio_features_host(q2a_engine * e, q2a_projector * p, const float * const * pcm, const int32_t * n_samples,
                             const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
                             int64_t rows_cap, int32_t * out_len, int32_t * status) {
-    std::vector<int32_t> kl;
-    if (int rc = lens_prologue(e, ENC_PACKED, n_samples, offsets_ms, key_len, n_clips, kl)) return rc;
-    if (!pcm) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    return features_host_impl(e, p, pcm, n_samples, offsets_ms, nullptr, kl.data(), n_clips, feat_host, embd_host, rows_cap, out_len, status);
+    return features_host(e, p, {pcm_input(nullptr, 0, n_samples, n_clips, offsets_ms), pcm}, key_len, feat_host, embd_host, rows_cap, out_len, status);
 }
 
 int q2a_audio_features_host_mel(q2a_engine * e, q2a_projector * p, const float * const * mel, const int32_t * n_len,
                                 const int32_t * seek, const int32_t * key_len, int n_clips, float * feat_host, float * embd_host,
                                 int64_t rows_cap, int32_t * out_len, int32_t * status) {
-    encode_kind ek;
-    std::vector<int32_t> kl;
-    if (int rc = mel_prologue(e, Q2A_ENCODE_VARLEN, n_len, seek, key_len, n_clips, ek, kl)) return rc;
-    if (!mel) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    const host_mel hm{mel, n_len, seek};
-    return features_host_impl(e, p, nullptr, nullptr, nullptr, &hm, kl.data(), n_clips, feat_host, embd_host, rows_cap, out_len, status);
+    return features_host(e, p, {mel_input(nullptr, 0, 0, n_len, seek, n_clips), mel}, key_len, feat_host, embd_host, rows_cap, out_len, status);
 }
 
 int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel_out, int64_t mel_cap, int * n_len_out) {
@@ -2643,35 +1899,31 @@ int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void 
     return rc;
 }
 
-// the front end of the clips `c` describes (plain metadata, no status) -> x_dev [B*T][D]
-static int test_frontend(q2a_engine * e, const encode_call & c, float * x_dev, void * stream) {
-    if (!e || !(c.pcm || c.mel) || !c.n_samples || !x_dev || c.B <= 0) return Q2A_ERR_ARG;
+// the front end of the clips `in` (plain metadata, no status) -> x_dev [B*T][D]
+static int test_frontend(q2a_engine * e, const clip_input & in, float * x_dev, void * stream) {
+    if (!e || !in.data || !in.len || !x_dev || in.B <= 0) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
-    int rc = reserve(e, c.B);
+    int rc = reserve(e, in.B);
     if (rc) return rc;
     int max_frames = 0;
     block_rows rows;
-    rc = prepare_meta(e, ENC_PLAIN, c, s, max_frames, rows);
+    rc = prepare_meta(e, ENC_PLAIN, in, resolve_clips(e, in), nullptr, window_sink(x_dev), nullptr, s, max_frames, rows);
     if (rc) return rc;
-    rc = run_frontend(e, c.src(), c.B, max_frames, s);
+    rc = run_frontend(e, in, max_frames, s);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x_dev, e->X, (size_t) c.B * e->d.T * e->d.D * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(x_dev, e->X, (size_t) in.B * e->d.T * e->d.D * 4, hipMemcpyDeviceToDevice, s));
     return Q2A_OK;
 }
 
 int q2a_test_frontend(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples, int n_clips,
                       float * x_dev, void * stream) {
-    encode_call c{};   // no offsets
-    c.pcm = pcm_dev; c.stride = pcm_stride; c.n_samples = n_samples; c.B = n_clips;
-    return test_frontend(e, c, x_dev, stream);
+    return test_frontend(e, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, nullptr), x_dev, stream);   // no offsets
 }
 
 int q2a_test_frontend_mel(q2a_engine * e, const float * mel_dev, int64_t clip_stride, int64_t ld, const int32_t * n_len,
                           const int32_t * seek, int n_clips, float * x_dev, void * stream) {
-    encode_call c{};
-    c.stride = clip_stride; c.n_samples = n_len; c.B = n_clips; c.mel = mel_dev; c.ld = ld; c.seek = seek;
-    return test_frontend(e, c, x_dev, stream);
+    return test_frontend(e, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), x_dev, stream);
 }
 
 int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * out_dev, void * stream) {

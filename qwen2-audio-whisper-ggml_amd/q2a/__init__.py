@@ -449,42 +449,40 @@ class Engine:
         return out, ol
 
     # ---- audio features (q2a_audio_features_*): the valid output rows of all clips packed, through the projector
+    def _features_device(self, fn, projector, data_ptr, strides, lens, second, what, key_len, sink, stream):
+        """One device feature call: fn(engine, projector, data, *strides, lens, second, key_len, n, *sink, out_len,
+        status, stream). second: offsets_ms or seek (named by `what`); a 0 pointer goes as NULL. Returns (out_len, status)."""
+        i32p = C.POINTER(C.c_int32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        n = len(lens)
+        _sd, sdp = self._i32(second, n, what)
+        _kl, klp = self._i32(key_len, n, "key_len")
+        st = np.full(n, -1, dtype=np.int32)
+        ol = np.zeros(n, dtype=np.int32)
+        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
+        _check(fn(self.h, projector.h if projector is not None else None, p(data_ptr), *[C.c_int64(v) for v in strides],
+                  lens.ctypes.data_as(i32p), sdp, klp, n, *[p(a) if isinstance(a, int) else a for a in sink],
+                  ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p), p(stream)))
+        return ol, st
+
+    @staticmethod
+    def _ref(struct):
+        return C.byref(struct) if struct is not None else None
+
     def audio_features_device(self, pcm_ptr: int, pcm_stride: int, n_samples, feat_ptr: int, embd_ptr: int, rows_cap: int,
                               projector=None, offsets_ms=None, key_len=None, stream: int | None = None):
         """q2a_audio_features_device: encode_device_varlen's inputs; feat_ptr [rows_cap][d_out] (0 without a projector)
         and embd_ptr [rows_cap][n_audio_state] (0: not written) receive clip c's out_len[c] rows at the prefix sum of
         out_len (packed_out_rows). Returns (out_len, status)."""
-        i32p = C.POINTER(C.c_int32)
-        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
-        n = len(ns)
-        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_audio_features_device(self.h, projector.h if projector is not None else None, p(pcm_ptr),
-                                               C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n, p(feat_ptr),
-                                               p(embd_ptr), C.c_int64(rows_cap), ol.ctypes.data_as(i32p),
-                                               st.ctypes.data_as(i32p), p(stream)))
-        return ol, st
+        return self._features_device(lib().q2a_audio_features_device, projector, pcm_ptr, (pcm_stride,), n_samples, offsets_ms,
+                                     "offsets_ms", key_len, (feat_ptr, embd_ptr, C.c_int64(rows_cap)), stream)
 
     def audio_features_device_mel(self, mel_ptr: int, clip_stride: int, ld: int, n_len, feat_ptr: int, embd_ptr: int,
                                   rows_cap: int, projector=None, seek=None, key_len=None, stream: int | None = None):
         """q2a_audio_features_device_mel: encode_device_mel's inputs (kind ENCODE_VARLEN), audio_features_device's
         outputs. Returns (out_len, status)."""
-        i32p = C.POINTER(C.c_int32)
-        nl = np.ascontiguousarray(n_len, dtype=np.int32)
-        n = len(nl)
-        _sk, skp = self._i32(seek, n, "seek")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_audio_features_device_mel(self.h, projector.h if projector is not None else None, p(mel_ptr),
-                                                   C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp, n,
-                                                   p(feat_ptr), p(embd_ptr), C.c_int64(rows_cap), ol.ctypes.data_as(i32p),
-                                                   st.ctypes.data_as(i32p), p(stream)))
-        return ol, st
+        return self._features_device(lib().q2a_audio_features_device_mel, projector, mel_ptr, (clip_stride, ld), n_len, seek,
+                                     "seek", key_len, (feat_ptr, embd_ptr, C.c_int64(rows_cap)), stream)
 
     def audio_features_device_to(self, pcm_ptr: int, pcm_stride: int, n_samples, dst: FeatDst, projector, clip_rows=None,
                                  embd_ptr: int = 0, embd_rows_cap: int = 0, offsets_ms=None, key_len=None,
@@ -492,81 +490,32 @@ class Engine:
         """q2a_audio_features_device_to: audio_features_device with the features stored as dst's type into dst's rows,
         clip c's out_len[c] rows from row clip_rows[c] on (None: packed); embd_ptr [embd_rows_cap][n_audio_state] still
         receives the packed f32 rows (0: not written). Returns (out_len, status)."""
-        i32p = C.POINTER(C.c_int32)
-        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
-        n = len(ns)
-        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        _cr, crp = self._i32(clip_rows, n, "clip_rows")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_audio_features_device_to(self.h, projector.h if projector is not None else None, p(pcm_ptr),
-                                                  C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n,
-                                                  C.byref(dst) if dst is not None else None, crp, p(embd_ptr),
-                                                  C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
-                                                  p(stream)))
-        return ol, st
+        _cr, crp = self._i32(clip_rows, len(n_samples), "clip_rows")
+        return self._features_device(lib().q2a_audio_features_device_to, projector, pcm_ptr, (pcm_stride,), n_samples, offsets_ms,
+                                     "offsets_ms", key_len, (self._ref(dst), crp, embd_ptr, C.c_int64(embd_rows_cap)), stream)
 
     def audio_features_device_mel_to(self, mel_ptr: int, clip_stride: int, ld: int, n_len, dst: FeatDst, projector,
                                      clip_rows=None, embd_ptr: int = 0, embd_rows_cap: int = 0, seek=None, key_len=None,
                                      stream: int | None = None):
         """q2a_audio_features_device_mel_to: audio_features_device_mel's inputs, audio_features_device_to's outputs."""
-        i32p = C.POINTER(C.c_int32)
-        nl = np.ascontiguousarray(n_len, dtype=np.int32)
-        n = len(nl)
-        _sk, skp = self._i32(seek, n, "seek")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        _cr, crp = self._i32(clip_rows, n, "clip_rows")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_audio_features_device_mel_to(self.h, projector.h if projector is not None else None, p(mel_ptr),
-                                                      C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp,
-                                                      n, C.byref(dst) if dst is not None else None, crp, p(embd_ptr),
-                                                      C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p),
-                                                      st.ctypes.data_as(i32p), p(stream)))
-        return ol, st
+        _cr, crp = self._i32(clip_rows, len(n_len), "clip_rows")
+        return self._features_device(lib().q2a_audio_features_device_mel_to, projector, mel_ptr, (clip_stride, ld), n_len, seek,
+                                     "seek", key_len, (self._ref(dst), crp, embd_ptr, C.c_int64(embd_rows_cap)), stream)
 
     def inputs_embeds_device(self, pcm_ptr: int, pcm_stride: int, n_samples, dst: FeatDst, src: EmbedsSrc, projector,
                              embd_ptr: int = 0, embd_rows_cap: int = 0, offsets_ms=None, key_len=None,
                              stream: int | None = None):
         """q2a_inputs_embeds_device: audio_features_device_to with the rows placed by src's input_ids (the k-th feature
         row at the k-th audio token) and the text rows gathered from src's embedding table. Returns (out_len, status)."""
-        i32p = C.POINTER(C.c_int32)
-        ns = np.ascontiguousarray(n_samples, dtype=np.int32)
-        n = len(ns)
-        _of, ofp = self._i32(offsets_ms, n, "offsets_ms")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_inputs_embeds_device(self.h, projector.h if projector is not None else None, p(pcm_ptr),
-                                              C.c_int64(pcm_stride), ns.ctypes.data_as(i32p), ofp, klp, n,
-                                              C.byref(dst) if dst is not None else None,
-                                              C.byref(src) if src is not None else None, p(embd_ptr), C.c_int64(embd_rows_cap),
-                                              ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p), p(stream)))
-        return ol, st
+        return self._features_device(lib().q2a_inputs_embeds_device, projector, pcm_ptr, (pcm_stride,), n_samples, offsets_ms,
+                                     "offsets_ms", key_len, (self._ref(dst), self._ref(src), embd_ptr, C.c_int64(embd_rows_cap)), stream)
 
     def inputs_embeds_device_mel(self, mel_ptr: int, clip_stride: int, ld: int, n_len, dst: FeatDst, src: EmbedsSrc, projector,
                                  embd_ptr: int = 0, embd_rows_cap: int = 0, seek=None, key_len=None,
                                  stream: int | None = None):
         """q2a_inputs_embeds_device_mel: audio_features_device_mel's inputs, inputs_embeds_device's outputs."""
-        i32p = C.POINTER(C.c_int32)
-        nl = np.ascontiguousarray(n_len, dtype=np.int32)
-        n = len(nl)
-        _sk, skp = self._i32(seek, n, "seek")
-        _kl, klp = self._i32(key_len, n, "key_len")
-        st = np.full(n, -1, dtype=np.int32)
-        ol = np.zeros(n, dtype=np.int32)
-        p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
-        _check(lib().q2a_inputs_embeds_device_mel(self.h, projector.h if projector is not None else None, p(mel_ptr),
-                                                  C.c_int64(clip_stride), C.c_int64(ld), nl.ctypes.data_as(i32p), skp, klp, n,
-                                                  C.byref(dst) if dst is not None else None,
-                                                  C.byref(src) if src is not None else None, p(embd_ptr),
-                                                  C.c_int64(embd_rows_cap), ol.ctypes.data_as(i32p), st.ctypes.data_as(i32p),
-                                                  p(stream)))
-        return ol, st
+        return self._features_device(lib().q2a_inputs_embeds_device_mel, projector, mel_ptr, (clip_stride, ld), n_len, seek,
+                                     "seek", key_len, (self._ref(dst), self._ref(src), embd_ptr, C.c_int64(embd_rows_cap)), stream)
 
     def _features_host(self, fn, ptrs, lens, n, second, key_len, projector, embd, rows_cap, raise_on_error):
         i32p = C.POINTER(C.c_int32)

@@ -1,6 +1,6 @@
 """CPU checks of the host-side packer behind q2a_pack_model_ex (no GPU needed: packing is host code).
 
-The blob is self-describing (csrc/q2a_engine.hip `blob_header`): its header records the activation contract, and
+The blob is self-describing (csrc/q2a_blob.h `blob_header`): its header records the activation contract, and
 under Q2A_ACT_BF16 every linear weight is ggml's dequantize_row_* rounded to bf16 — checked here bit
 for bit against a numpy restatement of dequantize_row_q8_0 (ggml-quants.c) for the fused q|k|v matrix of layer 0.
 """
