@@ -537,6 +537,41 @@ int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float 
                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
                                  const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
                                  int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream);
+/* ---- a quantized embedding table: the text rows decoded from ggml blocks on the device ---------------------------------
+ * A GGUF language model's token_embd.weight as it lies in the file: vocab rows of n_cols / block size ggml blocks, row r
+ * at rows + r * row_bytes. The _q calls below are the ids calls with this table as the source of the text rows, src's
+ * embed_table being NULL: row t of the destination becomes the n_cols values ggml's dequantize_row_q4_0 / q8_0 / q4_K /
+ * q5_K / q6_K gives for row input_ids[t] — bit for bit as f32; for fp16 / bf16 destinations that f32 value rounded once
+ * more to nearest even — by a kernel that brings the raw row into LDS and decodes it there. Nothing else differs: the
+ * map, the report words, the order of the launches, the profile class, the N_tot = 0 rule and the activation contract
+ * are the ids calls'. Further checks, made with theirs before anything is launched or written (Q2A_ERR_ARG): qt and
+ * qt->rows non-NULL, rows 16-byte aligned, ggml_type one of the five, reserved 0, vocab >= 1, n_cols == d_out and a
+ * multiple of 256, row_bytes a multiple of 16 and >= q2a_row_size(ggml_type, n_cols) (a Q6_K row of 210 bytes per 256
+ * columns is padded up to the next multiple of 16 unless n_cols % 2048 == 0), src->embed_table NULL. */
+typedef struct {
+    const void * rows;     /* device, 16-byte aligned: row r at rows + r * row_bytes */
+    int32_t ggml_type;     /* 2 Q4_0, 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K */
+    int32_t reserved;      /* 0 */
+    int64_t vocab, n_cols, row_bytes;
+} q2a_embed_qtable;
+/* One row of such a table on the host (pure arithmetic; also exported from libq2a_host.so): y[0 .. n_cols-1] = ggml's
+ * dequantize_row_* of the n_cols / block size blocks at row, ggml's float operations in ggml's order. The value contract
+ * of the _q calls. Q2A_ERR_ARG for another type, a NULL pointer or n_cols < 0; n_cols a multiple of the block size. */
+int q2a_dequantize_row(int ggml_type, const void * row, float * y, int64_t n_cols);
+int q2a_projector_apply_ids_q(q2a_projector * p, const float * x_dev, int64_t rows, const q2a_feat_dst * dst,
+                              const q2a_embeds_src * src, const q2a_embed_qtable * qt, void * stream);
+int q2a_inputs_embeds_device_q(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                               const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                               const q2a_feat_dst * dst, const q2a_embeds_src * src, const q2a_embed_qtable * qt,
+                               float * embd_dev, int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream);
+int q2a_inputs_embeds_device_mel_q(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                   const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                   const q2a_feat_dst * dst, const q2a_embeds_src * src, const q2a_embed_qtable * qt,
+                                   float * embd_dev, int64_t embd_rows_cap, int32_t * out_len, int32_t * status,
+                                   void * stream);
+/* Test hook: the decoding gather alone into dst (d_out columns), as q2a_test_embed_gather; report_dev required. */
+int q2a_test_embed_gather_q(const q2a_embeds_src * src, const q2a_embed_qtable * qt, const q2a_feat_dst * dst, int32_t d_out,
+                            void * stream);
 /* Test hooks. q2a_test_audio_token_rows: the compaction exactly as these calls launch it (map and chunk counts in p's
  * workspace, sized for n_feat rows, 0 <= n_feat <= 2^28), then the n_feat map words copied to row_map_out_dev (device
  * int32 [n_feat]; nothing behind them is written); report_dev (device int32[4], required) receives

@@ -140,56 +140,12 @@ inline int q6k_code(const q2a_block_q6_K * x, int k) {
 // F16: copied. Q4_K: W' = sc_j * q (exact small integers), DX = d, DMIN = dmin, WEXT = (64 m_j, m_j). Q5_K: the same
 // with its 5-bit codes (sc_j * q <= 1953, still an exact fp16 integer). Q6_K: W' = q - 32, DX = d, SC = sc_j.
 // Q8_0: W' = q, DX = d. Q4_0: W' = q - 8, DX = d.
-// one ggml row -> f32 values, as ggml's dequantize_row_* computes them (ggml-quants.c: q8_0 :1734, q4_0 :1694,
-// q4_K :2555-2577 with d1 = d*sc, m1 = dmin*m, y = d1*q - m1)
+// one ggml row -> f32 values: F32 / F16 as stored, the block formats as ggml's dequantize_row_* computes them
+// (q2a_dequantize_row, q2a_format.cpp)
 void dequant_row(const uint8_t * row, int wtype, int K, float * y) {
     if (wtype == Q2A_TYPE_F32) { memcpy(y, row, (size_t) K * 4); return; }
     if (wtype == Q2A_TYPE_F16) { for (int k = 0; k < K; ++k) y[k] = q2a_fp16_to_fp32(((const uint16_t *) row)[k]); return; }
-    if (wtype == Q2A_TYPE_Q8_0) {
-        for (int b = 0; b < K / 32; ++b) {
-            const q2a_block_q8_0 * x = (const q2a_block_q8_0 *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int l = 0; l < 32; ++l) y[b * 32 + l] = x->qs[l] * d;
-        }
-    } else if (wtype == Q2A_TYPE_Q4_0) {
-        for (int b = 0; b < K / 32; ++b) {
-            const q2a_block_q4_0 * x = (const q2a_block_q4_0 *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int l = 0; l < 16; ++l) {
-                y[b * 32 + l] = ((x->qs[l] & 0xF) - 8) * d;
-                y[b * 32 + 16 + l] = ((x->qs[l] >> 4) - 8) * d;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q4_K) {
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q4_K * x = (const q2a_block_q4_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
-            for (int j = 0; j < 8; ++j) {
-                uint8_t sc, m;
-                scale_min_k4(j, x->scales, &sc, &m);
-                const float d1 = d * sc, m1 = dmin * m;
-                const uint8_t * q = x->qs + 32 * (j / 2);
-                for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * ((j & 1) ? (q[l] >> 4) : (q[l] & 0xF)) - m1;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q5_K) {   // dequantize_row_q5_K, ggml-quants.c:2763-2788
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q5_K * x = (const q2a_block_q5_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
-            for (int j = 0; j < 8; ++j) {
-                uint8_t sc, m;
-                scale_min_k4(j, x->scales, &sc, &m);
-                const float d1 = d * sc, m1 = dmin * m;
-                for (int l = 0; l < 32; ++l) y[b * 256 + 32 * j + l] = d1 * q5k_code(x, j, l) - m1;
-            }
-        }
-    } else if (wtype == Q2A_TYPE_Q6_K) {   // dequantize_row_q6_K, ggml-quants.c:2977-3006: (d * sc) * q
-        for (int b = 0; b < K / 256; ++b) {
-            const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
-            const float d = q2a_fp16_to_fp32(x->d);
-            for (int k = 0; k < 256; ++k) y[b * 256 + k] = d * x->scales[k / 16] * (int8_t) (q6k_code(x, k) - 32);
-        }
-    }
+    q2a_dequantize_row(wtype, row, y, K);
 }
 
 uint16_t f32_to_bf16(float f) {   // round to nearest even (finite inputs)

@@ -5,10 +5,13 @@
 //                               launches; no workgroup waits for another one's progress.
 //   k_embed_gather              row t of the destination := row input_ids[t] of the table, a byte copy in 16-byte
 //                               pieces; audio positions are left to the GEMM's epilogue.
+//   k_qrow_gather               the same from a table of ggml blocks (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K): the raw row through
+//                               LDS, decoded there to ggml's dequantize_row_* values, stored as f32 / fp16 / bf16.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "q2a_format.h"
 #include "q2a_internal.h"
 
 namespace {
@@ -125,6 +128,196 @@ __global__ __launch_bounds__(256) void k_embed_gather(const IdT * ids, int n, in
     }
 }
 
+// ---- the decoding gather ---------------------------------------------------------------------------------------------
+// One wave per token, as k_embed_gather; a row is decoded in passes of QSEG columns (a pass starts on a 16-byte piece
+// of the row for every format: 8 Q6_K blocks are 105 pieces). A pass:
+//   1. the raw blocks of the pass, global -> registers -> the wave's LDS strip in 16-byte pieces, every load issued
+//      before the first use (clamped index, no load under a branch);
+//   2. the scale table of the pass, one entry per scale group, built once from the block headers in LDS: Q4_K / Q5_K
+//      (d * sc, dmin * m) per 32 columns out of the 6-bit packing, Q6_K d * sc per 16 columns, Q8_0 / Q4_0 d per block.
+//      All of these products are exact in f32;
+//   3. the decode: lane l of step k owns the 16 / ES consecutive columns (64 k + l) * 16 / ES .. of the pass — one
+//      16-byte store per lane, 1024 contiguous bytes per wave store. Consecutive columns of one scale group are
+//      consecutive code bytes under one nibble / bit-pair selector in every format, so a lane reads 4 code bytes per 4
+//      columns (plus 4 high-bit bytes for Q5_K / Q6_K) and one table entry, and the two halves of a code byte are taken
+//      by different lanes (32 columns apart in Q4_K / Q5_K, 64 in Q6_K, 16 in Q4_0) that read the same LDS word.
+// The LDS strip is the wave's own: no workgroup barrier, the waves of a workgroup do not wait for each other.
+constexpr int QSEG = 4096;
+
+template <int TYPE> struct qfmt;   // BB bytes per block of BC columns; a table entry of TW floats per TC columns
+template <> struct qfmt<Q2A_TYPE_Q4_K> { static constexpr int BB = 144, BC = 256, TC = 32, TW = 2; };
+template <> struct qfmt<Q2A_TYPE_Q5_K> { static constexpr int BB = 176, BC = 256, TC = 32, TW = 2; };
+template <> struct qfmt<Q2A_TYPE_Q6_K> { static constexpr int BB = 210, BC = 256, TC = 16, TW = 1; };
+template <> struct qfmt<Q2A_TYPE_Q8_0> { static constexpr int BB = 34, BC = 32, TC = 32, TW = 1; };
+template <> struct qfmt<Q2A_TYPE_Q4_0> { static constexpr int BB = 18, BC = 32, TC = 32, TW = 1; };
+
+// LDS traffic of one wave, ordered for all its lanes: what was written in front is seen by every lane behind
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float h2f(uint32_t h) { return (float) __builtin_bit_cast(_Float16, (uint16_t) h); }   // exact, subnormals too
+// four consecutive bytes at a 4-byte / a 2-byte aligned LDS address (Q6_K, Q8_0 and Q4_0 blocks are only 2-byte aligned)
+__device__ __forceinline__ uint32_t lds4(const uint8_t * p) { return *(const uint32_t *) p; }
+__device__ __forceinline__ uint32_t lds2x2(const uint8_t * p) {
+    const uint16_t * q = (const uint16_t *) p;
+    return (uint32_t) q[0] | ((uint32_t) q[1] << 16);
+}
+
+// the scale table of `cols` columns of blocks at L
+template <int TYPE>
+__device__ __forceinline__ void q_build_tab(const uint8_t * L, float * tab, int cols, int lane) {
+    using F = qfmt<TYPE>;
+    for (int e = lane; e < cols / F::TC; e += 64) {
+        if constexpr (TYPE == Q2A_TYPE_Q4_K || TYPE == Q2A_TYPE_Q5_K) {
+            // get_scale_min_k4 (ggml-quants.c:1898) of sub-block j on the header words {d | dmin << 16, scales[0..11]}
+            const int b = e >> 3, j = e & 7, sh = 8 * (j & 3);
+            const uint32_t * hw = (const uint32_t *) (L + b * F::BB);
+            const uint32_t dd = hw[0], s0 = (hw[1] >> sh) & 0xFF, s1 = (hw[2] >> sh) & 0xFF, s2 = (hw[3] >> sh) & 0xFF;
+            const uint32_t sc = j < 4 ? (s0 & 63) : ((s2 & 0xF) | ((s0 >> 6) << 4));
+            const uint32_t m = j < 4 ? (s1 & 63) : ((s2 >> 4) | ((s1 >> 6) << 4));
+            ((float2 *) tab)[e] = float2{h2f(dd & 0xFFFF) * (float) sc, h2f(dd >> 16) * (float) m};
+        } else if constexpr (TYPE == Q2A_TYPE_Q6_K) {
+            const uint8_t * blk = L + (e >> 4) * F::BB;
+            tab[e] = h2f(*(const uint16_t *) (blk + 208)) * (float) ((const int8_t *) blk)[192 + (e & 15)];
+        } else {
+            tab[e] = h2f(*(const uint16_t *) (L + e * F::BB));
+        }
+    }
+}
+
+// columns c .. c + 3 of the pass (c a multiple of 4), ggml's values
+template <int TYPE>
+__device__ __forceinline__ void q_decode4(const uint8_t * L, const float * tab, int c, float * y) {
+    using F = qfmt<TYPE>;
+    if constexpr (TYPE == Q2A_TYPE_Q4_K || TYPE == Q2A_TYPE_Q5_K) {
+        // sub-block j: nibble j & 1 of qs[32 (j / 2) + l]; Q5_K adds bit j of qh[l] as bit 4. y = d1 * q - m1: d1 * q is
+        // exact, so the fused form rounds once where ggml's subtraction does
+        const int b = c >> 8, j = (c >> 5) & 7, l = c & 31;
+        const uint8_t * blk = L + b * F::BB;
+        const float2 dm = ((const float2 *) tab)[c >> 5];
+        uint32_t wq = (lds4(blk + (TYPE == Q2A_TYPE_Q5_K ? 48 : 16) + 32 * (j >> 1) + l) >> (4 * (j & 1))) & 0x0F0F0F0Fu;
+        if constexpr (TYPE == Q2A_TYPE_Q5_K) wq |= ((lds4(blk + 16 + l) >> j) & 0x01010101u) << 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i] = __builtin_fmaf(dm.x, (float) ((wq >> (8 * i)) & 0xFF), -dm.y);
+    } else if constexpr (TYPE == Q2A_TYPE_Q6_K) {
+        // run r of half h: nibble r / 2 of ql[64 h + 32 (r & 1) + l], bits 2 r .. 2 r + 1 of qh[32 h + l]; (d * sc) * (q - 32)
+        const int b = c >> 8, h = (c >> 7) & 1, r = (c >> 5) & 3, l = c & 31;
+        const uint8_t * blk = L + b * F::BB;
+        const float ds = tab[c >> 4];
+        const uint32_t lo = (lds2x2(blk + 64 * h + 32 * (r & 1) + l) >> (4 * (r >> 1))) & 0x0F0F0F0Fu;
+        const uint32_t hi = (lds2x2(blk + 128 + 32 * h + l) >> (2 * r)) & 0x03030303u;
+        const uint32_t wq = lo | (hi << 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i] = ds * (float) ((int) ((wq >> (8 * i)) & 0xFF) - 32);
+    } else if constexpr (TYPE == Q2A_TYPE_Q8_0) {
+        const int b = c >> 5, l = c & 31;
+        const float d = tab[b];
+        const uint32_t wq = lds2x2(L + b * F::BB + 2 + l);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i] = (float) (int8_t) (wq >> (8 * i)) * d;
+    } else {
+        // Q4_0: columns 0..15 of a block are the low nibbles of qs[0..15], columns 16..31 the high ones
+        const int b = c >> 5, l = c & 31;
+        const float d = tab[b];
+        const uint32_t wq = (lds2x2(L + b * F::BB + 2 + (l & 15)) >> (4 * (l >> 4))) & 0x0F0F0F0Fu;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i] = (float) ((int) ((wq >> (8 * i)) & 0xFF) - 8) * d;
+    }
+}
+
+// f32 -> the 16 bits of a fp16 / bf16 destination, round to nearest even (the _to calls' rule; finite inputs for bf16)
+template <int DT>
+__device__ __forceinline__ uint32_t q_cvt16(float f) {
+    if constexpr (DT == Q2A_DT_F16) {
+        // the f32 value first, in a register of its own: folded into the conversion (v_fma_mixlo_f16 d, q, 0) the product
+        // of a zero and a negative factor came out as +0 where ggml stores -0
+        asm volatile("" : "+v"(f));
+        return __builtin_bit_cast(uint16_t, (_Float16) f);
+    }
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// ids: int64 (wide) or int32, loaded by the wave-uniform width. row16 / out_ld16: strides in 16-byte units.
+template <int TYPE, int DT>
+__global__ __launch_bounds__(256) void k_qrow_gather(const void * ids, int wide, int n, int64_t audio_id, const uint4 * rows,
+                                                        int64_t vocab, int64_t row16, int n_cols, uint4 * out, int64_t out_ld16,
+                                                        int32_t * report) {
+    using F = qfmt<TYPE>;
+    constexpr int EPL = DT == Q2A_DT_F32 ? 4 : 8;   // columns per lane and step: one 16-byte store
+    constexpr int RAW16 = (QSEG / F::BC * F::BB + 15) / 16, NLD = (RAW16 + 63) / 64;
+    __shared__ uint4 raw_s[4][RAW16];
+    __shared__ float tab_s[4][QSEG / F::TC * F::TW];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+    const int t = blockIdx.x * 4 + w;
+    if (t >= n) return;
+    const int64_t id = wide ? ((const int64_t *) ids)[t] : (int64_t) ((const int32_t *) ids)[t];
+    if (id == audio_id) return;
+    if (id < 0 || id >= vocab) {
+        if (lane == 0) { atomicAdd(report + 2, 1); atomicOr(report + 3, 2); }
+        return;
+    }
+    uint4 * raw = raw_s[w];
+    float * tab = tab_s[w];
+    const uint8_t * L = (const uint8_t *) raw;
+    const uint4 * src = rows + id * row16;
+    uint4 * dst = out + (int64_t) t * out_ld16;
+    for (int c0 = 0; c0 < n_cols; c0 += QSEG) {
+        const int cols = n_cols - c0 < QSEG ? n_cols - c0 : QSEG;
+        const int seg16 = (cols / F::BC * F::BB + 15) / 16;
+        const uint4 * sp = src + (int64_t) (c0 / QSEG) * (QSEG / F::BC * F::BB / 16);
+        // (the LDS writes are clamped like the loads, a lane past the end rewriting the last piece with its own bytes:
+        // under a bound of their own, the compiler moved each load in behind it, one wait per piece)
+        uint4 v[NLD];
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int k = lane + 64 * i;
+            v[i] = sp[k < seg16 ? k : seg16 - 1];
+        }
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int k = lane + 64 * i;
+            raw[k < seg16 ? k : seg16 - 1] = v[i];
+        }
+        wave_lds_sync();
+        q_build_tab<TYPE>(L, tab, cols, lane);
+        wave_lds_sync();
+        uint4 * dp = dst + c0 / EPL;
+        for (int c = lane * EPL; c < cols; c += 64 * EPL) {
+            float y[EPL];
+            q_decode4<TYPE>(L, tab, c, y);
+            uint4 o;
+            if constexpr (EPL == 4) {
+                o = uint4{__builtin_bit_cast(uint32_t, y[0]), __builtin_bit_cast(uint32_t, y[1]), __builtin_bit_cast(uint32_t, y[2]),
+                          __builtin_bit_cast(uint32_t, y[3])};
+            } else {
+                q_decode4<TYPE>(L, tab, c + 4, y + 4);
+                o = uint4{q_cvt16<DT>(y[0]) | (q_cvt16<DT>(y[1]) << 16), q_cvt16<DT>(y[2]) | (q_cvt16<DT>(y[3]) << 16),
+                          q_cvt16<DT>(y[4]) | (q_cvt16<DT>(y[5]) << 16), q_cvt16<DT>(y[6]) | (q_cvt16<DT>(y[7]) << 16)};
+            }
+            dp[c / EPL] = o;
+        }
+        wave_lds_sync();   // the next pass overwrites the strip
+    }
+}
+
+template <int TYPE, int DT>
+void launch_gather_q(const q2a_embed_gather_q_args & a, hipStream_t s) {
+    const int n = (int) a.n_tokens;
+    hipLaunchKernelGGL((k_qrow_gather<TYPE, DT>), dim3((unsigned) ((n + 3) / 4)), dim3(256), 0, s, a.ids, a.width == 8 ? 1 : 0, n, a.audio_id,
+                       (const uint4 *) a.rows, a.vocab, a.row_bytes / 16, (int) a.n_cols, (uint4 *) a.out, a.out_ld_bytes / 16, a.report);
+}
+template <int TYPE>
+void launch_gather_q_dt(const q2a_embed_gather_q_args & a, hipStream_t s) {
+    if (a.out_dt == Q2A_DT_F32) launch_gather_q<TYPE, Q2A_DT_F32>(a, s);
+    else if (a.out_dt == Q2A_DT_F16) launch_gather_q<TYPE, Q2A_DT_F16>(a, s);
+    else launch_gather_q<TYPE, Q2A_DT_BF16>(a, s);
+}
+
 }  // namespace
 
 hipError_t q2a_launch_audio_token_rows(const q2a_ids_args & a, hipStream_t s) {
@@ -157,5 +350,25 @@ hipError_t q2a_launch_embed_gather(const q2a_embed_gather_args & a, hipStream_t 
     else
         hipLaunchKernelGGL(k_embed_gather<int32_t>, grid, dim3(256), 0, s, (const int32_t *) a.ids, n, a.audio_id, (const uint4 *) a.table,
                            a.vocab, a.table_ld_bytes / 16, (uint4 *) a.out, a.out_ld_bytes / 16, row16, a.report);
+    return hipGetLastError();
+}
+
+hipError_t q2a_launch_embed_gather_q(const q2a_embed_gather_q_args & a, hipStream_t s) {
+    const int t = a.ggml_type;
+    if (t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K && t != Q2A_TYPE_Q6_K) return hipErrorInvalidValue;
+    if (a.out_dt != Q2A_DT_F32 && a.out_dt != Q2A_DT_F16 && a.out_dt != Q2A_DT_BF16) return hipErrorInvalidValue;
+    const int es = a.out_dt == Q2A_DT_F32 ? 4 : 2;
+    if (!a.ids || (a.width != 4 && a.width != 8) || a.n_tokens < 1 || a.n_tokens > Q2A_IDS_MAX_TOKENS || !a.rows || a.vocab < 1 || !a.out ||
+        !a.report || a.n_cols < 256 || a.n_cols % 256 || a.n_cols > (1 << 24) || a.row_bytes % 16 ||
+        a.row_bytes < (int64_t) q2a_row_size(t, a.n_cols) || a.out_ld_bytes % 16 || a.out_ld_bytes < a.n_cols * es ||
+        ((uintptr_t) a.rows & 15) || ((uintptr_t) a.out & 15))
+        return hipErrorInvalidValue;
+    switch (t) {
+        case Q2A_TYPE_Q4_0: launch_gather_q_dt<Q2A_TYPE_Q4_0>(a, s); break;
+        case Q2A_TYPE_Q8_0: launch_gather_q_dt<Q2A_TYPE_Q8_0>(a, s); break;
+        case Q2A_TYPE_Q4_K: launch_gather_q_dt<Q2A_TYPE_Q4_K>(a, s); break;
+        case Q2A_TYPE_Q5_K: launch_gather_q_dt<Q2A_TYPE_Q5_K>(a, s); break;
+        default: launch_gather_q_dt<Q2A_TYPE_Q6_K>(a, s); break;
+    }
     return hipGetLastError();
 }

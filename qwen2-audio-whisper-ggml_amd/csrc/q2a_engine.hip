@@ -609,8 +609,8 @@ clip_input mel_input(const float * mel, int64_t clip_stride, int64_t ld, const i
 // clips packed (q2a_packed_out_rows) as f32 into embd [rows_cap][D] and / or, through the projector, into feat
 // [rows_cap][d_out] (packed_sink); the features as dst's type into dst's rows, clip c's from row clip_row[c] on (host
 // [B]; NULL: packed), embd [rows_cap][D] still the packed f32 rows (rows_sink); or into dst's rows where ids->input_ids
-// holds the audio token, the text rows gathered from ids->embed_table (ids_sink). All but the first are the
-// audio-feature tail of a variable-length encode.
+// holds the audio token, the text rows gathered from ids->embed_table or decoded from the ggml blocks of qtab (ids_sink).
+// All but the first are the audio-feature tail of a variable-length encode.
 struct out_sink {
     enum { WINDOWS, PACKED, ROWS, IDS } kind;
     float * out;
@@ -620,6 +620,7 @@ struct out_sink {
     const q2a_feat_dst * dst;
     const int32_t * clip_row;
     const q2a_embeds_src * ids;
+    const q2a_embed_qtable * qtab;   // NULL: the dense table of ids, if any
     bool features() const { return kind != WINDOWS; }
     bool to_dst() const { return kind == ROWS || kind == IDS; }
 };
@@ -638,9 +639,9 @@ out_sink rows_sink(const q2a_feat_dst * dst, const int32_t * clip_row, float * e
     k.kind = out_sink::ROWS; k.dst = dst; k.clip_row = clip_row; k.embd = embd; k.rows_cap = rows_cap;
     return k;
 }
-out_sink ids_sink(const q2a_feat_dst * dst, const q2a_embeds_src * ids, float * embd, int64_t rows_cap) {
+out_sink ids_sink(const q2a_feat_dst * dst, const q2a_embeds_src * ids, float * embd, int64_t rows_cap, const q2a_embed_qtable * qtab = nullptr) {
     out_sink k{};
-    k.kind = out_sink::IDS; k.dst = dst; k.ids = ids; k.embd = embd; k.rows_cap = rows_cap;
+    k.kind = out_sink::IDS; k.dst = dst; k.ids = ids; k.embd = embd; k.rows_cap = rows_cap; k.qtab = qtab;
     return k;
 }
 
@@ -973,6 +974,35 @@ int feat_dst_check(const q2a_projector * p, const q2a_feat_dst * dst) {
 // ---- inputs_embeds: the row map from input_ids and the text-row gather (q2a_embeds.hip) ---------------------------
 int dt_size(int dtype) { return dtype == Q2A_DT_F32 ? 4 : 2; }
 
+// where the text rows of an ids call come from: src's dense table (or none), or a table of ggml blocks (the _q calls)
+struct text_rows {
+    const q2a_embeds_src * src;
+    const q2a_embed_qtable * qtab;
+    bool any() const { return qtab || src->embed_table; }
+};
+
+// a q2a_embed_qtable beside a checked src and destination of d_out columns (include/q2a_encoder.h)
+int embed_qtable_check(const q2a_embed_qtable * qt, const q2a_embeds_src & src, int d_out) {
+    if (!qt) { set_err("inputs_embeds: the quantized table is required"); return Q2A_ERR_ARG; }
+    if (src.embed_table) { set_err("inputs_embeds: a quantized table goes with embed_table NULL"); return Q2A_ERR_ARG; }
+    const int t = qt->ggml_type;
+    if ((t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K && t != Q2A_TYPE_Q6_K) || qt->reserved != 0) {
+        set_err("inputs_embeds: quantized table of ggml type %d (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K), reserved %d", t, qt->reserved);
+        return Q2A_ERR_ARG;
+    }
+    if (qt->n_cols != d_out || qt->n_cols % 256 != 0 || qt->vocab < 1) {
+        set_err("inputs_embeds: quantized table of %lld columns (d_out %d, a multiple of 256), vocab %lld >= 1", (long long) qt->n_cols,
+                d_out, (long long) qt->vocab);
+        return Q2A_ERR_ARG;
+    }
+    if (!qt->rows || ((uintptr_t) qt->rows & 15) || qt->row_bytes % 16 != 0 || qt->row_bytes < (int64_t) q2a_row_size(t, qt->n_cols)) {
+        set_err("inputs_embeds: quantized table: rows 16-byte aligned, row_bytes %lld a multiple of 16 and >= %lld",
+                (long long) qt->row_bytes, (long long) q2a_row_size(t, qt->n_cols));
+        return Q2A_ERR_ARG;
+    }
+    return Q2A_OK;
+}
+
 // a q2a_embeds_src against a checked destination of d_out columns (include/q2a_encoder.h)
 int embeds_src_check(const q2a_embeds_src * src, const q2a_feat_dst & dst, int d_out) {
     if (!src) { set_err("inputs_embeds: src is required"); return Q2A_ERR_ARG; }
@@ -1003,10 +1033,16 @@ q2a_ids_args ids_args(const void * ids, int width, int64_t n_tokens, int64_t aud
     return {ids, width, n_tokens, audio_id, n_feat, o.chunk_count, o.map, report ? report : o.report};
 }
 
-// the text rows of a checked src into dst (nothing without a table); the report words 2 and 3 must already be written
-hipError_t launch_embeds_gather(const q2a_embeds_src & src, const q2a_feat_dst & dst, int d_out, int32_t * report, hipStream_t s) {
-    if (!src.embed_table) return hipSuccess;
+// the text rows of a checked source into dst (nothing without a table); the report words 2 and 3 must already be written
+hipError_t launch_embeds_gather(const text_rows & tr, const q2a_feat_dst & dst, int d_out, int32_t * report, hipStream_t s) {
+    const q2a_embeds_src & src = *tr.src;
     const int es = dt_size(dst.dtype);
+    if (const q2a_embed_qtable * qt = tr.qtab) {
+        const q2a_embed_gather_q_args ga{src.input_ids, src.ids_width, src.n_tokens, src.audio_token_id, qt->rows, qt->ggml_type, qt->vocab,
+                                         qt->n_cols, qt->row_bytes, dst.base, dst.ld * es, dst.dtype, report};
+        return q2a_launch_embed_gather_q(ga, s);
+    }
+    if (!src.embed_table) return hipSuccess;
     const q2a_embed_gather_args ga{src.input_ids, src.ids_width, src.n_tokens, src.audio_token_id, src.embed_table, src.vocab,
                                    src.table_ld * es, dst.base, dst.ld * es, (int64_t) d_out * es, report};
     return q2a_launch_embed_gather(ga, s);
@@ -1033,6 +1069,8 @@ int features_check(const q2a_engine * e, const clip_facts & f, const int32_t * k
         if (int rc = feat_dst_check(proj, k.dst)) return rc;
         if (k.kind == out_sink::IDS)
             if (int rc = embeds_src_check(k.ids, *k.dst, proj->d_out)) return rc;
+        if (k.kind == out_sink::IDS && k.qtab)
+            if (int rc = embed_qtable_check(k.qtab, *k.ids, proj->d_out)) return rc;
     } else {
         if (!k.feat && !k.embd) { set_err("audio features: feat and embd are both NULL"); return Q2A_ERR_ARG; }
         if (proj ? !k.feat : k.feat != nullptr) { set_err("audio features: feat goes with a projector, and only with one"); return Q2A_ERR_ARG; }
@@ -1105,7 +1143,8 @@ int encode(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_
         int32_t * report = ids->report_dev ? ids->report_dev : po.report;
         PLAUNCH(e, s, Q2A_PROF_POOL, q2a_launch_audio_token_rows(ids_args(ids->input_ids, ids->ids_width, ids->n_tokens, ids->audio_token_id,
                                                                           rows.N_out, po, report), s));
-        if (ids->embed_table) PLAUNCH(e, s, Q2A_PROF_POOL, launch_embeds_gather(*ids, *sink.dst, proj->d_out, report, s));
+        const text_rows tr{ids, sink.qtab};
+        if (tr.any()) PLAUNCH(e, s, Q2A_PROF_POOL, launch_embeds_gather(tr, *sink.dst, proj->d_out, report, s));
     }
     // (packed with every clip skipped: no rows, nothing to run; the pool kernel below writes the zeros. The
     // audio-feature tail writes valid rows only: without any, nothing is launched behind the metadata)
@@ -1413,12 +1452,30 @@ int q2a_inputs_embeds_device(q2a_engine * e, q2a_projector * p, const float * pc
                          ids_sink(dst, src, embd_dev, embd_rows_cap), out_len, status, stream);
 }
 
+int q2a_inputs_embeds_device_q(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
+                               const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
+                               const q2a_feat_dst * dst, const q2a_embeds_src * src, const q2a_embed_qtable * qt,
+                               float * embd_dev, int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    if (!qt) { set_err("inputs_embeds: the quantized table is required"); return Q2A_ERR_ARG; }
+    return encode_device(e, ENC_PACKED, p, pcm_input(pcm_dev, pcm_stride, n_samples, n_clips, offsets_ms), key_len,
+                         ids_sink(dst, src, embd_dev, embd_rows_cap, qt), out_len, status, stream);
+}
+
 int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
                                  const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
                                  const q2a_feat_dst * dst, const q2a_embeds_src * src, float * embd_dev,
                                  int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
     return encode_device(e, ENC_PACKED, p, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len,
                          ids_sink(dst, src, embd_dev, embd_rows_cap), out_len, status, stream);
+}
+
+int q2a_inputs_embeds_device_mel_q(q2a_engine * e, q2a_projector * p, const float * mel_dev, int64_t clip_stride, int64_t ld,
+                                   const int32_t * n_len, const int32_t * seek, const int32_t * key_len, int n_clips,
+                                   const q2a_feat_dst * dst, const q2a_embeds_src * src, const q2a_embed_qtable * qt,
+                                   float * embd_dev, int64_t embd_rows_cap, int32_t * out_len, int32_t * status, void * stream) {
+    if (!qt) { set_err("inputs_embeds: the quantized table is required"); return Q2A_ERR_ARG; }
+    return encode_device(e, ENC_PACKED, p, mel_input(mel_dev, clip_stride, ld, n_len, seek, n_clips), key_len,
+                         ids_sink(dst, src, embd_dev, embd_rows_cap, qt), out_len, status, stream);
 }
 
 // ---- the host entry points -------------------------------------------------------------------------------------
@@ -2155,11 +2212,14 @@ int q2a_projector_apply_to(q2a_projector * p, const float * x, int64_t rows, con
     return Q2A_OK;
 }
 
-int q2a_projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const q2a_embeds_src * src,
-                            void * stream) {
+// q2a_projector_apply_ids / _q: the text rows from src's dense table, or from qt where the call takes one
+static int projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const q2a_embeds_src * src,
+                               const q2a_embed_qtable * qt, bool quant, void * stream) {
     if (!p || !x || !dst || rows <= 0 || rows > (1 << 30) / 4) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     if (int rc = feat_dst_check(p, dst)) return rc;
     if (int rc = embeds_src_check(src, *dst, p->d_out)) return rc;
+    if (quant)
+        if (int rc = embed_qtable_check(qt, *src, p->d_out)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = call_stream(stream);
     const int M = (int) rows, K = p->d_in;
@@ -2167,7 +2227,7 @@ int q2a_projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, co
     if (int rc = proj_workspace(p, rows, s, o, true, src->n_tokens)) return rc;
     int32_t * report = src->report_dev ? src->report_dev : o.report;
     LAUNCH(q2a_launch_audio_token_rows(ids_args(src->input_ids, src->ids_width, src->n_tokens, src->audio_token_id, M, o, report), s));
-    LAUNCH(launch_embeds_gather(*src, *dst, p->d_out, report, s));
+    LAUNCH(launch_embeds_gather(text_rows{src, qt}, *dst, p->d_out, report, s));
     if (p->blk == 0) {
         const int64_t n = (int64_t) M * K;
         hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
@@ -2178,6 +2238,16 @@ int q2a_projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, co
     }
     LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, o.map), Q2A_EPI_STORE_ROWS, p->gblk, s));
     return Q2A_OK;
+}
+
+int q2a_projector_apply_ids(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const q2a_embeds_src * src,
+                            void * stream) {
+    return projector_apply_ids(p, x, rows, dst, src, nullptr, false, stream);
+}
+
+int q2a_projector_apply_ids_q(q2a_projector * p, const float * x, int64_t rows, const q2a_feat_dst * dst, const q2a_embeds_src * src,
+                              const q2a_embed_qtable * qt, void * stream) {
+    return projector_apply_ids(p, x, rows, dst, src, qt, true, stream);
 }
 
 int q2a_test_audio_token_rows(q2a_projector * p, const void * ids_dev, int32_t ids_width, int64_t n_tokens, int64_t audio_token_id,
@@ -2204,7 +2274,18 @@ int q2a_test_embed_gather(const q2a_embeds_src * src, const q2a_feat_dst * dst, 
     if (int rc = embeds_src_check(src, *dst, d_out)) return rc;
     hipStream_t s = call_stream(stream);
     HIP_TRY(hipMemsetAsync(src->report_dev, 0, 16, s));
-    LAUNCH(launch_embeds_gather(*src, *dst, d_out, src->report_dev, s));
+    LAUNCH(launch_embeds_gather(text_rows{src, nullptr}, *dst, d_out, src->report_dev, s));
+    return Q2A_OK;
+}
+
+int q2a_test_embed_gather_q(const q2a_embeds_src * src, const q2a_embed_qtable * qt, const q2a_feat_dst * dst, int32_t d_out, void * stream) {
+    if (!src || !qt || !dst || d_out < 1 || !src->report_dev) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    if (int rc = feat_dst_check_cols(d_out, dst)) return rc;
+    if (int rc = embeds_src_check(src, *dst, d_out)) return rc;
+    if (int rc = embed_qtable_check(qt, *src, d_out)) return rc;
+    hipStream_t s = call_stream(stream);
+    HIP_TRY(hipMemsetAsync(src->report_dev, 0, 16, s));
+    LAUNCH(launch_embeds_gather(text_rows{src, qt}, *dst, d_out, src->report_dev, s));
     return Q2A_OK;
 }
 

@@ -210,6 +210,64 @@ extern "C" int64_t q2a_audio_token_rows(const void * ids_host, int32_t ids_width
     return count;
 }
 
+// One ggml row -> f32, ggml's dequantize_row_* float operations in ggml's order (ggml-quants.c: q4_0 :1694, q8_0 :1734,
+// q4_K :2555-2577 with d1 = d * sc, m1 = dmin * m, y = d1 * q - m1; q5_K :2763-2788; q6_K :2977-3006, (d * sc) * q).
+// The value contract of the quantized embedding gather (q2a_embeds.hip) and of the bf16-contract weight pack.
+static inline void scale_min_k4(int j, const uint8_t * q, uint8_t * d, uint8_t * m);
+extern "C" int q2a_dequantize_row(int ggml_type, const void * row, float * y, int64_t n_cols) {
+    const size_t rs = q2a_row_size(ggml_type, n_cols);
+    if (!row || !y || n_cols < 0 || (n_cols > 0 && rs == 0)) return Q2A_ERR_ARG;
+    if (ggml_type == Q2A_TYPE_Q8_0) {
+        for (int64_t b = 0; b < n_cols / 32; ++b) {
+            const q2a_block_q8_0 * x = (const q2a_block_q8_0 *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d);
+            for (int l = 0; l < 32; ++l) y[b * 32 + l] = x->qs[l] * d;
+        }
+    } else if (ggml_type == Q2A_TYPE_Q4_0) {
+        for (int64_t b = 0; b < n_cols / 32; ++b) {
+            const q2a_block_q4_0 * x = (const q2a_block_q4_0 *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d);
+            for (int l = 0; l < 16; ++l) {
+                y[b * 32 + l] = ((x->qs[l] & 0xF) - 8) * d;
+                y[b * 32 + 16 + l] = ((x->qs[l] >> 4) - 8) * d;
+            }
+        }
+    } else if (ggml_type == Q2A_TYPE_Q4_K || ggml_type == Q2A_TYPE_Q5_K) {
+        const bool q5 = ggml_type == Q2A_TYPE_Q5_K;
+        for (int64_t b = 0; b < n_cols / 256; ++b) {
+            // (block_q5_K begins like block_q4_K: d, dmin, scales[12]; then qh[32] in front of its qs)
+            const q2a_block_q4_K * x = (const q2a_block_q4_K *) ((const uint8_t *) row + b * (q5 ? sizeof(q2a_block_q5_K) : sizeof(q2a_block_q4_K)));
+            const uint8_t * qh = x->qs, * qs = q5 ? x->qs + 32 : x->qs;
+            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
+            for (int j = 0; j < 8; ++j) {
+                uint8_t sc, m;
+                scale_min_k4(j, x->scales, &sc, &m);
+                const float d1 = d * sc, m1 = dmin * m;
+                const uint8_t * q = qs + 32 * (j / 2);
+                for (int l = 0; l < 32; ++l) {
+                    const int v = ((j & 1) ? (q[l] >> 4) : (q[l] & 0xF)) + (q5 ? ((qh[l] >> j) & 1) << 4 : 0);
+                    y[b * 256 + 32 * j + l] = d1 * v - m1;
+                }
+            }
+        }
+    } else if (ggml_type == Q2A_TYPE_Q6_K) {
+        for (int64_t b = 0; b < n_cols / 256; ++b) {
+            const q2a_block_q6_K * x = (const q2a_block_q6_K *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d);
+            for (int k = 0; k < 256; ++k) {
+                // per 128 weights, four runs of 32 over two 32-byte rows of nibbles and one of 2-bit pairs
+                const int h = k / 128, r = (k % 128) / 32, l = k % 32;
+                const uint8_t n = x->ql[64 * h + 32 * (r & 1) + l];
+                const int q = ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
+                y[b * 256 + k] = d * x->scales[k / 16] * (int8_t) (q - 32);
+            }
+        }
+    } else {
+        return Q2A_ERR_ARG;
+    }
+    return Q2A_OK;
+}
+
 static double hz_to_mel_slaney(double f) {
     const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp;
     const double logstep = std::log(6.4) / 27.0;

@@ -361,3 +361,21 @@ struct q2a_embed_gather_args {
     int32_t * report;
 };
 hipError_t q2a_launch_embed_gather(const q2a_embed_gather_args & a, hipStream_t s);
+// The same from a table of ggml blocks (include/q2a_encoder.h, q2a_embed_qtable): row t of out := the n_cols values of
+// ggml's dequantize_row_* of table row ids[t], as out_dt (Q2A_DT_*); the ids, the report and what is never written as
+// above. hipErrorInvalidValue for another type, n_cols % 256 != 0, row_bytes short of q2a_row_size or no multiple of 16,
+// a misaligned table or destination, out_ld_bytes short of a row or no multiple of 16.
+struct q2a_embed_gather_q_args {
+    const void * ids;
+    int width;
+    int64_t n_tokens;
+    int64_t audio_id;
+    const void * rows;           // 16-byte aligned
+    int ggml_type;               // Q2A_TYPE_Q4_0 / Q8_0 / Q4_K / Q5_K / Q6_K
+    int64_t vocab, n_cols, row_bytes;
+    void * out;                  // 16-byte aligned
+    int64_t out_ld_bytes;        // a multiple of 16
+    int out_dt;
+    int32_t * report;
+};
+hipError_t q2a_launch_embed_gather_q(const q2a_embed_gather_q_args & a, hipStream_t s);

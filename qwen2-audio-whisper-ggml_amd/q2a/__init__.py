@@ -36,6 +36,8 @@ EXPORTS = (
     "q2a_audio_features_device_mel_to",
     "q2a_audio_token_rows", "q2a_projector_apply_ids", "q2a_inputs_embeds_device", "q2a_inputs_embeds_device_mel",
     "q2a_test_audio_token_rows", "q2a_test_embed_gather",
+    "q2a_dequantize_row", "q2a_projector_apply_ids_q", "q2a_inputs_embeds_device_q", "q2a_inputs_embeds_device_mel_q",
+    "q2a_test_embed_gather_q",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -94,6 +96,67 @@ def embeds_src(ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int,
                table_ld: int = 0, report_ptr: int = 0) -> EmbedsSrc:
     p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
     return EmbedsSrc(p(ids_ptr), ids_width, 0, n_tokens, audio_token_id, p(table_ptr), vocab, table_ld, p(report_ptr))
+
+
+# ggml types of a quantized embedding table (include/q2a_encoder.h, q2a_embed_qtable): (bytes, columns) of a block
+TYPE_Q4_0, TYPE_Q8_0, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 2, 8, 12, 13, 14
+_QBLOCK = {TYPE_Q4_0: (18, 32), TYPE_Q8_0: (34, 32), TYPE_Q4_K: (144, 256), TYPE_Q5_K: (176, 256), TYPE_Q6_K: (210, 256)}
+
+
+def quant_row_size(ggml_type: int, n_cols: int) -> int:
+    """Bytes of one row of n_cols columns of a block format (ggml_row_size)."""
+    bb, bc = _QBLOCK[ggml_type]
+    if n_cols % bc:
+        raise ValueError(f"n_cols {n_cols}: a multiple of {bc}")
+    return n_cols // bc * bb
+
+
+class EmbedQTable(C.Structure):
+    """q2a_embed_qtable: an embedding table of ggml blocks on the device."""
+    _fields_ = [("rows", C.c_void_p), ("ggml_type", C.c_int32), ("reserved", C.c_int32), ("vocab", C.c_int64),
+                ("n_cols", C.c_int64), ("row_bytes", C.c_int64)]
+
+
+class QuantTable:
+    """A quantized embedding table for Engine.inputs_embeds(embed_table=...) and the _q calls: rows, a CUDA uint8 tensor
+    [vocab][row_bytes] (row_bytes a multiple of 16 and >= quant_row_size(ggml_type, n_cols), 16-byte aligned) holding
+    each row's ggml blocks (Q4_0, Q8_0, Q4_K, Q5_K or Q6_K) as they lie in a GGUF file's token_embd.weight. The tensor is
+    kept alive by the object; .desc is the q2a_embed_qtable of the C calls."""
+
+    def __init__(self, rows, ggml_type: int, n_cols: int):
+        import torch
+        if ggml_type not in _QBLOCK:
+            raise ValueError(f"ggml type {ggml_type}: Q4_0 (2), Q8_0 (8), Q4_K (12), Q5_K (13) or Q6_K (14)")
+        if n_cols < 256 or n_cols % 256:
+            raise ValueError(f"n_cols {n_cols}: a multiple of 256")
+        if not (hasattr(rows, "is_cuda") and rows.is_cuda and rows.dtype == torch.uint8 and rows.dim() == 2 and rows.is_contiguous()
+                and rows.shape[0] >= 1 and rows.shape[1] % 16 == 0 and rows.shape[1] >= quant_row_size(ggml_type, n_cols)
+                and rows.data_ptr() % 16 == 0):
+            raise ValueError("rows: a contiguous, 16-byte aligned CUDA uint8 tensor [vocab][row_bytes], row_bytes a multiple of "
+                             f"16 and >= {quant_row_size(ggml_type, n_cols)}")
+        self.rows, self.ggml_type, self.n_cols = rows, ggml_type, n_cols
+        self.vocab, self.row_bytes = int(rows.shape[0]), int(rows.shape[1])
+        self.desc = EmbedQTable(C.c_void_p(rows.data_ptr()), ggml_type, 0, self.vocab, n_cols, self.row_bytes)
+
+    @classmethod
+    def from_host(cls, data, ggml_type: int, n_cols: int, device="cuda"):
+        """From the bytes of the rows back to back on the host (a numpy uint8 array or buffer of vocab * quant_row_size
+        bytes, as in the model file): each row padded up to a multiple of 16 bytes, then copied to the device."""
+        import torch
+        rs = quant_row_size(ggml_type, n_cols)
+        raw = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+        if rs == 0 or raw.size == 0 or raw.size % rs:
+            raise ValueError(f"{raw.size} bytes are no whole number of rows of {rs} bytes")
+        rows = np.zeros((raw.size // rs, (rs + 15) // 16 * 16), dtype=np.uint8)
+        rows[:, :rs] = raw.reshape(-1, rs)
+        return cls(torch.from_numpy(rows).to(device), ggml_type, n_cols)
+
+    @classmethod
+    def from_tensor(cls, t, device="cuda"):
+        """From a q2a.ggmlfile.Tensor of one of the five block types: ne = (n_cols, vocab), .data its bytes."""
+        if len(t.ne) != 2:
+            raise ValueError("an embedding table has two dimensions")
+        return cls.from_host(t.data, int(t.type), int(t.ne[0]), device)
 
 
 _lib = None
@@ -212,6 +275,15 @@ def lib() -> C.CDLL:
                                                        vp, C.c_int64, i32p, i32p, vp]
             L.q2a_test_audio_token_rows.argtypes = [vp, vp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp]
             L.q2a_test_embed_gather.argtypes = [srcp, dstp, C.c_int32, vp]
+        if hasattr(L, "q2a_inputs_embeds_device_q"):   # the text rows decoded from a table of ggml blocks
+            dstp, srcp, qtp = C.POINTER(FeatDst), C.POINTER(EmbedsSrc), C.POINTER(EmbedQTable)
+            L.q2a_dequantize_row.argtypes = [C.c_int, vp, vp, C.c_int64]
+            L.q2a_projector_apply_ids_q.argtypes = [vp, vp, C.c_int64, dstp, srcp, qtp, vp]
+            L.q2a_inputs_embeds_device_q.argtypes = [vp, vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, dstp, srcp, qtp, vp,
+                                                     C.c_int64, i32p, i32p, vp]
+            L.q2a_inputs_embeds_device_mel_q.argtypes = [vp, vp, vp, C.c_int64, C.c_int64, i32p, i32p, i32p, C.c_int, dstp, srcp,
+                                                         qtp, vp, C.c_int64, i32p, i32p, vp]
+            L.q2a_test_embed_gather_q.argtypes = [srcp, qtp, dstp, C.c_int32, vp]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
         L.q2a_projector_close.argtypes = [vp]
@@ -517,6 +589,23 @@ class Engine:
         return self._features_device(lib().q2a_inputs_embeds_device_mel, projector, mel_ptr, (clip_stride, ld), n_len, seek,
                                      "seek", key_len, (self._ref(dst), self._ref(src), embd_ptr, C.c_int64(embd_rows_cap)), stream)
 
+    def inputs_embeds_device_q(self, pcm_ptr: int, pcm_stride: int, n_samples, dst: FeatDst, src: EmbedsSrc, qtable, projector,
+                               embd_ptr: int = 0, embd_rows_cap: int = 0, offsets_ms=None, key_len=None,
+                               stream: int | None = None):
+        """q2a_inputs_embeds_device_q: inputs_embeds_device with the text rows decoded from qtable (a QuantTable or an
+        EmbedQTable); src carries no dense table."""
+        return self._features_device(lib().q2a_inputs_embeds_device_q, projector, pcm_ptr, (pcm_stride,), n_samples, offsets_ms,
+                                     "offsets_ms", key_len,
+                                     (self._ref(dst), self._ref(src), _qt_ref(qtable), embd_ptr, C.c_int64(embd_rows_cap)), stream)
+
+    def inputs_embeds_device_mel_q(self, mel_ptr: int, clip_stride: int, ld: int, n_len, dst: FeatDst, src: EmbedsSrc, qtable,
+                                   projector, embd_ptr: int = 0, embd_rows_cap: int = 0, seek=None, key_len=None,
+                                   stream: int | None = None):
+        """q2a_inputs_embeds_device_mel_q: inputs_embeds_device_mel's inputs, inputs_embeds_device_q's outputs."""
+        return self._features_device(lib().q2a_inputs_embeds_device_mel_q, projector, mel_ptr, (clip_stride, ld), n_len, seek,
+                                     "seek", key_len,
+                                     (self._ref(dst), self._ref(src), _qt_ref(qtable), embd_ptr, C.c_int64(embd_rows_cap)), stream)
+
     def _features_host(self, fn, ptrs, lens, n, second, key_len, projector, embd, rows_cap, raise_on_error):
         i32p = C.POINTER(C.c_int32)
         _kl, klp = self._i32(key_len, n, "key_len")
@@ -650,7 +739,7 @@ class Engine:
         return (out, ol, emb) if return_embd else (out, ol)
 
     def inputs_embeds(self, input_features, feature_attention_mask, input_ids, audio_token_id: int, projector,
-                      embed_tokens=None, out=None, check: bool = True):
+                      embed_tokens=None, out=None, check: bool = True, embed_table=None):
         """The language model's inputs_embeds in one call (q2a_inputs_embeds_device_mel, on torch's current stream):
         embed_tokens[input_ids] with the k-th audio feature row stored at the k-th position whose id is audio_token_id —
         Qwen2AudioForConditionalGeneration's embedding pass, cast and masked_scatter, without a host copy of input_ids.
@@ -659,7 +748,9 @@ class Engine:
         input_ids: a contiguous CUDA int32 or int64 tensor [B][S] or [n]; embed_tokens: the embedding weight [vocab][d_out]
         of out's dtype on that device (rows may be strided), or None: text rows keep what out holds; out: a contiguous
         CUDA tensor input_ids.shape + (d_out,) of float32 / float16 / bfloat16 (None: allocated, embed_tokens' dtype, or
-        float32 zeros without a table). Returns (inputs_embeds, out_len [B], report): report is a CUDA int32[4] tensor —
+        float32 zeros without a table). embed_table: a QuantTable of d_out columns on that device in place of embed_tokens
+        (also accepted as embed_tokens): the text rows are its rows as ggml dequantizes them, stored as out's dtype
+        (None: float32, what llama_batch.embd takes). Returns (inputs_embeds, out_len [B], report): report is a CUDA int32[4] tensor —
         audio tokens found, feature rows, text ids outside [0, vocab), flags (bit 0: found != rows, bit 1: bad ids). With
         check=True the four words are read (one synchronising copy) and a mismatch or a bad id raises ValueError;
         check=False reads nothing on the host."""
@@ -675,6 +766,12 @@ class Engine:
             raise ValueError("input_ids: at most 2^24 tokens")
         d_out = projector.d_out
         dts = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
+        if isinstance(embed_tokens, QuantTable):
+            embed_tokens, embed_table = None, embed_tokens if embed_table is None else embed_table
+        qt = embed_table
+        if qt is not None and not (isinstance(qt, QuantTable) and embed_tokens is None and qt.n_cols == d_out
+                                   and qt.rows.device == ids.device):
+            raise ValueError(f"embed_table: a QuantTable of {d_out} columns on input_ids' device, without embed_tokens")
         tab = embed_tokens
         if tab is not None and not (hasattr(tab, "is_cuda") and tab.is_cuda and tab.device == ids.device and tab.dim() == 2
                                     and tab.shape[1] == d_out and tab.dtype in dts and tab.stride(1) == 1 and tab.shape[0] >= 1
@@ -710,8 +807,13 @@ class Engine:
         src = embeds_src(ids.data_ptr(), ids.element_size(), n_tok, int(audio_token_id),
                          tab.data_ptr() if tab is not None else 0, tab.shape[0] if tab is not None else 0,
                          tab.stride(0) if tab is not None else 0, report.data_ptr())
-        ol, _ = self.inputs_embeds_device_mel(x.data_ptr(), self.info.n_mels * L, L, [L] * B, dst, src, projector, key_len=kl,
-                                              stream=torch.cuda.current_stream(x.device).cuda_stream)
+        cs = torch.cuda.current_stream(x.device).cuda_stream
+        if qt is not None:
+            ol, _ = self.inputs_embeds_device_mel_q(x.data_ptr(), self.info.n_mels * L, L, [L] * B, dst, src, qt, projector,
+                                                    key_len=kl, stream=cs)
+        else:
+            ol, _ = self.inputs_embeds_device_mel(x.data_ptr(), self.info.n_mels * L, L, [L] * B, dst, src, projector, key_len=kl,
+                                                  stream=cs)
         if check:
             found, rows, bad, flags = (int(v) for v in report.cpu())
             if flags:
@@ -837,6 +939,7 @@ def _host() -> C.CDLL:
         _host_lib.q2a_feat_rows.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int64, C.POINTER(C.c_int32)]
         _host_lib.q2a_audio_token_rows.restype = C.c_int64
         _host_lib.q2a_audio_token_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64]
+        _host_lib.q2a_dequantize_row.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
     return _host_lib
 
 
@@ -926,6 +1029,37 @@ def test_embed_gather(src: EmbedsSrc, dst: FeatDst, d_out: int, stream=None):
 
 
 test_embed_gather.__test__ = False   # (a library hook, not a test)
+
+
+def _qt_ref(qtable):
+    if qtable is None:
+        return None
+    return C.byref(qtable.desc if isinstance(qtable, QuantTable) else qtable)
+
+
+def test_embed_gather_q(src: EmbedsSrc, qtable, dst: FeatDst, d_out: int, stream=None):
+    """q2a_test_embed_gather_q: the decoding gather of the _q calls alone (qtable: a QuantTable or an EmbedQTable)."""
+    _check(lib().q2a_test_embed_gather_q(C.byref(src) if src is not None else None, _qt_ref(qtable),
+                                         C.byref(dst) if dst is not None else None, d_out, C.c_void_p(stream) if stream else None))
+
+
+test_embed_gather_q.__test__ = False   # (a library hook, not a test)
+
+
+def dequantize_row(ggml_type: int, row, n_cols: int) -> np.ndarray:
+    """ggml's dequantize_row_* of one row of blocks (q2a_dequantize_row): row, a numpy uint8 array or buffer of at least
+    quant_row_size(ggml_type, n_cols) bytes -> float32 [n_cols], the values the _q calls store. Host arithmetic through
+    lib/libq2a_host.so: needs no GPU."""
+    raw = np.ascontiguousarray(np.frombuffer(row, dtype=np.uint8) if not isinstance(row, np.ndarray) else row.reshape(-1).view(np.uint8))
+    if ggml_type not in _QBLOCK or raw.size < quant_row_size(ggml_type, n_cols):
+        raise ValueError("dequantize_row: one of the five block types and a whole row of it")
+    y = np.empty(n_cols, dtype=np.float32)
+    rc = _host().q2a_dequantize_row(ggml_type, raw.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), C.c_int64(n_cols))
+    if rc != 0:
+        err = Q2AError(f"q2a error {rc}: invalid arguments to q2a_dequantize_row")
+        err.rc = int(rc)
+        raise err
+    return y
 
 
 def audio_token_runs(input_ids, audio_token_id: int) -> tuple[np.ndarray, np.ndarray]:
@@ -1070,6 +1204,12 @@ class Projector:
         _check(lib().q2a_projector_apply_ids(self.h, C.c_void_p(x_ptr), rows, C.byref(dst) if dst is not None else None,
                                              C.byref(src) if src is not None else None,
                                              C.c_void_p(stream) if stream else None))
+
+    def apply_ids_q(self, x_ptr: int, rows: int, dst: FeatDst, src: EmbedsSrc, qtable, stream=None):
+        """q2a_projector_apply_ids_q: apply_ids with the text rows decoded from qtable (a QuantTable or an EmbedQTable)."""
+        _check(lib().q2a_projector_apply_ids_q(self.h, C.c_void_p(x_ptr), rows, C.byref(dst) if dst is not None else None,
+                                               C.byref(src) if src is not None else None, _qt_ref(qtable),
+                                               C.c_void_p(stream) if stream else None))
 
     def test_audio_token_rows(self, ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int, n_feat: int,
                               row_map_ptr: int, report_ptr: int, stream=None):
