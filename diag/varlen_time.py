@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Whole-step time of the variable-length encode against the padded encode.
 
-    python diag/varlen_time.py [--clips 64] [--wt q4_k] [--rounds 4] [--steps 3] [--out FILE]
+    python diag/varlen_time.py [--clips 64] [--wt q4_k] [--act reference|bf16] [--rounds 4] [--steps 3] [--out FILE]
 
 Full-size model, `--clips` 30 s clips resident in HBM; the key lengths are passed explicitly, so the same audio serves
 every case. Cases: every key length 1500, 500 and 250, and one mixed batch (lengths drawn once from 100..1500, seed 0).
@@ -10,6 +10,8 @@ then the variable-length one (q2a_encode_device_varlen), `--steps` encodes each 
 off: wall ms per step. Medians over the rounds and the spread (max - min) of either entry point per case. A last pass
 with the engine's per-class timers on (q2a_profile_*, HIP events around every launch; its sum is not a step time) gives
 the Q2A_PROF_* classes per step for both entry points, and from them the GEMMs' TF/s at the case's row count.
+--act bf16: the bf16-activation contract with q2a_set_bf16_key_lengths on, and the plain entry point
+(q2a_encode_device, the V^T attention kernel; it ignores the key lengths) measured as a third alternative in every round.
 Prints one JSON line (and writes it to --out)."""
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=64)
     ap.add_argument("--wt", default="q4_k")
+    ap.add_argument("--act", default="reference", choices=["reference", "bf16"])
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--lens", default="1500,500,250")
@@ -45,7 +48,8 @@ def main():
 
     os.makedirs(args.workdir, exist_ok=True)
     model = bench.make_model(args.wt, args.workdir, min(16, os.cpu_count() or 8))
-    eng = q2a.Engine(model, device=0)
+    bf16 = args.act == "bf16"
+    eng = q2a.Engine(model, device=0, act=q2a.ACT_BF16 if bf16 else q2a.ACT_REFERENCE, bf16_key_lengths=bf16)
     info = eng.info
     D, L, T = info.n_audio_state, info.n_audio_layer, info.n_audio_ctx
     B = args.clips
@@ -61,6 +65,8 @@ def main():
     cnt = (C.c_int64 * 11)()
     h = C.c_void_p(eng.h)
     entry = {"padded": eng.encode_device_padded, "varlen": eng.encode_device_varlen}
+    if bf16:
+        entry["plain"] = lambda p, stride, n, o, key_len=None: eng.encode_device(p, stride, n, o)
 
     def steps(which, kl):
         for _ in range(args.steps):
@@ -71,7 +77,7 @@ def main():
         for which in entry:
             entry[which](pcm.data_ptr(), bench.N_SAMPLES, ns, out.data_ptr(), key_len=kl)
     torch.cuda.synchronize()
-    wall = {name: {"padded": [], "varlen": []} for name in cases}
+    wall = {name: {which: [] for which in entry} for name in cases}
     for _ in range(args.rounds):
         for name, kl in cases.items():
             for which in entry:
@@ -94,10 +100,10 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
     F = 4 * D
     shapes = {"gemm_qkv": (3 * D, D), "gemm_o": (D, D), "gemm_fc1": (F, D), "gemm_fc2": (D, F)}
-    res = {"clips": B, "wt": args.wt, "steps_per_measurement": args.steps, "rounds": args.rounds, "cases": {}}
+    res = {"clips": B, "wt": args.wt, "act": args.act, "steps_per_measurement": args.steps, "rounds": args.rounds, "cases": {}}
     for name, kl in cases.items():
         m_tot, _ = q2a.varlen_rows(kl, T)
-        rows = {"padded": B * T, "varlen": m_tot}
+        rows = {"padded": B * T, "varlen": m_tot, "plain": B * T}
         tf = {which: {g: round(2.0 * rows[which] * n * k * L / (classes[name][which][g] * 1e-3) / 1e12, 1)
                       for g, (n, k) in shapes.items() if classes[name][which][g] > 0} for which in entry}
         res["cases"][name] = {

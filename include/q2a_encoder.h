@@ -94,6 +94,15 @@ q2a_engine * q2a_open_shared(const q2a_engine * base);
 /* Encode windows with under 1 s of audio after the offset too (default off: they are skipped, Q2A_CLIP_SKIPPED,
  * like the reference). whisper_full uses it when duration_ms overrides the length check (qwen2-whisper.cpp:2357). */
 int q2a_set_force_encode(q2a_engine * e, int on);
+/* bf16 activation contract (Q2A_ACT_BF16) only, Q2A_ERR_ARG for any other engine: serve the padded and the
+ * variable-length kinds (default off: they answer Q2A_ERR_UNSUPPORTED). With it on, q2a_encode_{device,host}_padded,
+ * q2a_encode_{device,host}_varlen, q2a_encode_{device,host}_mel with kind PADDED or VARLEN, q2a_test_block_len and
+ * q2a_test_block_varlen run on the engine with their documented arguments, checks and results; every block of such a
+ * call writes V row-major and runs the key-length form of the bf16 attention kernel, which gives a clip with
+ * key_len = n_audio_ctx the plain bf16 encode's bytes. The plain entry points are unchanged either way.
+ * q2a_audio_features_* and q2a_inputs_embeds_* keep answering Q2A_ERR_UNSUPPORTED on a bf16 engine: the projector has
+ * no bf16 mode yet. */
+int q2a_set_bf16_key_lengths(q2a_engine * e, int on);
 
 void q2a_close(q2a_engine * e);
 int q2a_get_info(const q2a_engine * e, q2a_info * info);
@@ -151,7 +160,8 @@ int q2a_valid_lengths(int n_samples, int offset_ms, int n_audio_ctx, int32_t * e
  *   out_dev     [n_clips][n_out][n_audio_state] f32: rows >= out_len[c] of clip c are written as zeros (a skipped
  *               clip's rows are all zeros)
  * Everything else is as in q2a_encode_device_ex (same front end, GEMMs and LayerNorms over all n_audio_ctx rows: the
- * padded rows are computed and ignored). Reference activation contract only: Q2A_ERR_UNSUPPORTED for Q2A_ACT_BF16. */
+ * padded rows are computed and ignored). Reference activation contract, and Q2A_ACT_BF16 engines that opted in with
+ * q2a_set_bf16_key_lengths (Q2A_ERR_UNSUPPORTED without it). */
 int q2a_encode_device_padded(q2a_engine * e, const float * pcm_dev, int64_t pcm_stride, const int32_t * n_samples,
                              const int32_t * offsets_ms, const int32_t * key_len, int n_clips, float * out_dev,
                              int32_t * out_len, int32_t * status, void * stream);
@@ -176,8 +186,9 @@ int q2a_encode_host_padded(q2a_engine * e, const float * const * pcm, const int3
  * between a clip's length and the end of its last partly valid block (the front end's output for the padding, carried
  * through the layers) travel with the clip — at most 15 rows, computed as queries, never read as keys.
  *
- * Not covered: the whisper_* API, q2a_group_*, the ggml backend and the bf16 activation contract
- * (Q2A_ERR_UNSUPPORTED); the front end is not restricted to the valid frames. The output of these entry points is not
+ * Not covered: the whisper_* API, q2a_group_*, the ggml backend, and the bf16 activation contract unless the engine
+ * opted in with q2a_set_bf16_key_lengths (Q2A_ERR_UNSUPPORTED; its kernel's online softmax is per query, so the same
+ * 16-row rounding carries over unchanged); the front end is not restricted to the valid frames. The output of these entry points is not
  * packed: q2a_audio_features_* below return the valid rows alone, one clip after the other. */
 int64_t q2a_varlen_rows(const int32_t * key_len, int n_clips, int n_audio_ctx, int32_t * row_start);
 
@@ -214,7 +225,7 @@ int q2a_mel_valid_lengths(int n_len, int seek, int n_audio_ctx, int32_t * enc_le
 
 /* kind         Q2A_ENCODE_PLAIN: q2a_encode_device_ex behind the mel (all n_audio_ctx keys; key_len and out_len are
  *              not read or written); Q2A_ENCODE_PADDED / Q2A_ENCODE_VARLEN: q2a_encode_device_padded / _varlen behind
- *              it (Q2A_ERR_UNSUPPORTED for Q2A_ACT_BF16, nothing written)
+ *              it (Q2A_ERR_UNSUPPORTED for Q2A_ACT_BF16 without q2a_set_bf16_key_lengths, nothing written)
  * mel_dev      device f32, clip c at mel_dev + c * clip_stride, [n_mels][ld]; ld, seek and the pointer need no
  *              alignment beyond a float's
  * clip_stride  floats between clips: >= n_mels * ld, or 0: every clip reads the same array (the windows of one
@@ -363,7 +374,8 @@ int q2a_test_gemm_regime(q2a_engine * e, int which, int epi, int M);
 int q2a_test_attention(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                        float * out_dev, void * stream);
 /* q2a_test_attention / q2a_test_block with per-clip key lengths (host array [n_clips], 1 <= key_len[c] <= n_audio_ctx,
- * uploaded by the call): the key-length instantiation of the attention kernel. Reference activation contract only. */
+ * uploaded by the call): the key-length instantiation of the attention kernel. Reference activation contract only
+ * (q2a_test_block_len / _varlen: also a bf16 engine with q2a_set_bf16_key_lengths on). */
 int q2a_test_attention_len(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                            const int32_t * key_len, float * out_dev, void * stream);
 int q2a_test_block_len(q2a_engine * e, int layer, float * x_dev, int n_clips, const int32_t * key_len, void * stream);
@@ -372,6 +384,13 @@ int q2a_test_block_len(q2a_engine * e, int layer, float * x_dev, int n_clips, co
 int q2a_test_attention_varlen(q2a_engine * e, const float * q_dev, const float * k_dev, const float * v_dev, int n_clips,
                               const int32_t * key_len, float * out_dev, void * stream);
 int q2a_test_block_varlen(q2a_engine * e, int layer, float * x_dev, int n_clips, const int32_t * key_len, void * stream);
+/* The bf16 contract's attention kernels alone, on any engine, with or without q2a_set_bf16_key_lengths. kind is a
+ * Q2A_ENCODE_* value: PLAIN runs the plain bf16 kernel on a V^T image the call builds (key_len not read), PADDED its
+ * key-length form on the windows [n_clips*T][D], VARLEN its packed form on [M_tot][D] rows (q2a_varlen_rows over
+ * key_len). q, k, v f32, rounded to bf16 by the call (q already scaled by 1/sqrt(d_head)); out_dev f32: the kernel's
+ * value before its bf16 rounding. The checks of q2a_test_attention_len. */
+int q2a_test_attention_bf16(q2a_engine * e, int kind, const float * q_dev, const float * k_dev, const float * v_dev,
+                            int n_clips, const int32_t * key_len, float * out_dev, void * stream);
 
 /* ---- downstream consumer: the Qwen2-Audio multi-modal projector ------------------------
  * audio_features = Linear(d_model -> text hidden size, bias)(embd_enc) — transformers' Qwen2AudioMultiModalProjector

@@ -77,6 +77,18 @@ struct attn_lds_g {
 // of lane half hi is (r&3) + 8(r>>2) + 4hi, so register r then holds key 16(r>>3) + 8hi + (r&7): the 8 keys a lane
 // half feeds the P.V MFMA as one B fragment are contiguous, and their V^T operand is ONE 16-B LDS read instead of
 // two 8-B reads and a register shuffle (softmax is order-free over the keys of a tile)
+// a * b; S: as one scalar v_mul_f32 whatever the compiler would pair (the key-length ping-pong forms carry no packed
+// f32 instruction; the product is the same IEEE one)
+template <bool S>
+__device__ __forceinline__ float mul1(float a, float b) {
+    if constexpr (S) {
+        float r;
+        asm("v_mul_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+        return r;
+    } else {
+        return a * b;
+    }
+}
 __device__ __forceinline__ int kperm(int c) { return (c & ~12) | ((c & 4) << 1) | ((c & 8) >> 1); }
 // max of x over lanes l and l ^ 32: v_permlane32_swap exchanges the two wave halves in a VALU slot (no LDS round
 // trip as ds_bpermute, no lgkmcnt wait); one of the two results is the lane's own value
@@ -559,14 +571,45 @@ __global__ __launch_bounds__(256, 3) void k_attn_t(const q2a_attn_args p) {
 // stage by A in its VALU segment 2t+5 and by B in its VALU segment 2t+4 (one half each), from registers loaded two
 // segments earlier. Per element the arithmetic of k_attn: S = Kh.Qh + Kl.Qh + Kh.Ql in the same MFMA order, one
 // online-softmax update per 64 keys, P and V fp16 (bf16 in the bf16-activation mode) into the P.V MFMA.
-template <bool BF>
-__global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
+//
+// KL (bf16 contract): per-clip key lengths, with V row-major [rows][D] like K (q2a_attn_args.v_rows) in place of the
+// V^T image, which packed rows cannot address. Tk = clamp(key_len[clip], 1, T), uniform per workgroup: the tile count,
+// the K / V row clamp and the last tile's mask take Tk where the plain form takes T (rows >= Tk of K and V are never
+// read); the Q-row clamp and the store guard keep T. A workgroup whose 256 queries all lie at or past Tk stores zeros
+// and leaves before its first barrier; a dead wave of a live workgroup stages and passes every barrier like the rest.
+// PK (with KL): the packed rows of the variable-length encode (rowbase = row_start[clip], T = the segment's rows, the
+// query tiles per (clip, head) from r_max; a workgroup whose first query is >= T leaves at once).
+// V in LDS, KL form: a [key][d] image of 64 unpadded 128-B rows staged by the same register path as K, its P.V A
+// fragment (d = 32dt + col, keys 16sp' + 8hi .. +7) read by two ds_read_b64_tr_b16: in each 16-lane group lane 4q + pp
+// supplies the 8 bytes of key row 8hi + q (+ 4 for the second read), columns 32dt + 16(col >> 4) + 4pp .. +3, and
+// receives column (lane & 15) of the group's 4 x 16 block: keys +0..3 (+4..7) of its own d — the values, in the
+// order, of the V^T image's one 16-B read, so the MFMAs see the same operands.
+// Bank model: the 64-B half hf of key row r sits at half hf ^ ((r >> 1) & 1) of the row.
+//   transposed read, per 32-lane half (32 x 8 B = the 64 banks once): rows 8hi + q (+4), q = 0..3, one 64-B half
+//   each; rows of one parity (q & 1) share a 128-B bank half and differ in q >> 1, so the swizzle puts them on the
+//   two different 64-B quarters: four rows, four distinct quarters — conflict-free. The swizzle is a lane constant
+//   (every other term of the row number is a multiple of 4): one address register per dt, the rest immediates.
+//   staging write (ds_write_b128, 16-lane groups): the swizzle is applied to the SOURCE address — the thread that
+//   writes LDS granule g of row r loads global granule g ^ 4((r >> 1) & 1) — so a wave's 64 writes are 1 KiB of
+//   consecutive LDS bytes, every 16-lane group 256 consecutive bytes: conflict-free; and 8 threads still cover one
+//   whole 128-B global row.
+// Same bits: the MFMA shape, the order of the MFMAs over d and over keys and the softmax update are the plain form's;
+// masked keys have P = exp2(-1e30 ...) = 0 against a finite V row (the clamp's copy of row Tk-1) where the V^T image
+// has zero pad columns: the same +0 into the accumulator. So a clip with key_len = T gets the plain kernel's bytes,
+// and a row's bits depend neither on the padded / packed form nor on the clips it is batched with (the only
+// cross-query term, __any(alpha != 1), skips a multiplication by exactly 1).
+// Its own instantiation: the !KL forms compile as before.
+template <bool BF, bool KL = false, bool PK = false>
+__global__ __launch_bounds__(512, KL ? 4 : 2) void k_attn_pp(const q2a_attn_args p) {
+    static_assert(!KL || BF, "key lengths on the ping-pong kernel: bf16 contract (the reference contract has k_attn_t)");
+    static_assert(!PK || KL, "the packed layout carries key lengths");
+    constexpr bool VR = KL;                   // V row-major, transposed LDS reads
     constexpr float QL2E = BF ? L2E : 1.0f;   // reference-contract Q arrives pre-multiplied by log2(e)
     typedef attn_lds<false> LY;
     // V^T rows padded to 144 B like K's (16-B granules in order: conflict-free for the 16-lane groups of a b128 read,
     // one base register + immediates; an XOR swizzle needs an address register per granule and costs the 4th wave)
     // so the 8 keys of a P.V B fragment (K rows permuted by kperm, as in k_attn_g) are ONE ds_read_b128
-    constexpr int KROW = LY::KROW, VROW = LY::KROW;
+    constexpr int KROW = LY::KROW, VROW = VR ? 128 : LY::KROW;
     constexpr int KIMG = KT * KROW, VIMG = 64 * VROW;
     constexpr int NK = BF ? 1 : 2;                 // K images per stage (hi, lo)
     constexpr int STAGE = NK * KIMG + VIMG;
@@ -576,14 +619,40 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
     __shared__ __attribute__((aligned(16))) char lds[NST * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int grp = wave >> 2, gt = tid & 255;     // group A (0) / B (1), thread index within the group
-    const int T = p.T, D = p.D;
-    const int nq = (T + 255) / 256, total = (int) gridDim.x;
+    int T = p.T;   // rows of this clip (PK: its segment's, below)
+    const int D = p.D;
+    const int nq = ((PK ? p.r_max : T) + 255) / 256, total = (int) gridDim.x;
     const int L = (int) blockIdx.x;
     const int w = (total & 7) ? L : (L & 7) * (total >> 3) + (L >> 3);
     const int qt = w % nq, h = (w / nq) % p.H, clip = w / (nq * p.H);
     const int q0 = qt * 256 + wave * 32;
-    const int64_t rowbase = (int64_t) clip * T;
+    int64_t rowbase = (int64_t) clip * T;
+    if constexpr (PK) {
+        const int r0 = p.row_start[clip];
+        rowbase = r0;
+        T = p.row_start[clip + 1] - r0;
+        if (qt * 256 >= T) return;   // no such rows (a clip with no rows at all: every workgroup of it)
+    }
     const int hi = lane >> 5, col = lane & 31;
+    int Tk = T;   // keys of this clip
+    if constexpr (KL) {
+        Tk = min(max(p.key_len[clip], 1), T);   // (the callers check 1 <= key_len <= T; the row clamp relies on it)
+        if (!PK && qt * 256 >= Tk) {   // every query of the workgroup lies in the padding: zeros, before the first barrier
+            const int q = q0 + col;
+            if (q < T) {
+                const int64_t orow = (rowbase + q) * D + h * 64;
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int d = dt * 32 + 8 * g + 4 * hi;
+                        if (p.outH) *(uint2 *) (p.outH + orow + d) = make_uint2(0u, 0u);   // (bf16 zeros)
+                        else *(float4 *) (p.outF + orow + d) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    }
+            }
+            return;
+        }
+    }
 
     half8 qh[4], ql[4];
     {
@@ -596,7 +665,8 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
             ql[s] = BF ? qh[s] : *(const half8 *) (sl + 16 * s);
         }
     }
-    const q2a_half * vt_base = p.vt + ((int64_t) clip * p.H + h) * 64 * p.TP;
+    const q2a_half * k_base = p.kh + rowbase * D + h * 64;   // (VR staging)
+    const q2a_half * vt_base = VR ? p.vt + rowbase * D + h * 64 : p.vt + ((int64_t) clip * p.H + h) * 64 * p.TP;
     // staging: this group's half of a tile, CPT 16-B chunks per thread. Chunk c of the tile (0 .. CH-1): image
     // c / 512 (Kh, [Kl,] V^T), row (c % 512) / 8, 16-B piece c % 8.
     uint4 rg[CPT];
@@ -606,9 +676,14 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
 #pragma unroll
         for (int u = 0; u < CPT; ++u) {
             const int c = chunk_of(u), img = c >> 9, r = (c >> 3) & 63, pc = c & 7;
-            if (img < NK) {
+            if constexpr (VR) {
+                // K and V rows alike, one address computation and no branch (group A stages K, group B V; a branch
+                // per image sends rg to scratch). V: the granule whose LDS place is pc (the swizzle on the source)
+                const q2a_half * src = img ? vt_base : k_base;
+                rg[u] = *(const uint4 *) (src + (int64_t) min(kb0 + r, Tk - 1) * D + ((img ? pc ^ ((r & 2) << 1) : pc) * 8));
+            } else if (img < NK) {
                 const q2a_half * src = img == 0 ? p.kh : p.kl;
-                rg[u] = *(const uint4 *) (src + (rowbase + min(kb0 + r, T - 1)) * D + h * 64 + pc * 8);
+                rg[u] = *(const uint4 *) (src + (rowbase + min(kb0 + r, Tk - 1)) * D + h * 64 + pc * 8);
             } else {
                 rg[u] = *(const uint4 *) (vt_base + (int64_t) r * p.TP + kb0 + pc * 8);
             }
@@ -619,7 +694,9 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
 #pragma unroll
         for (int u = 0; u < CPT; ++u) {
             const int c = chunk_of(u), img = c >> 9, r = (c >> 3) & 63, pc = c & 7;
-            if (img < NK) {
+            if constexpr (VR) {
+                *(uint4 *) (st + (img ? NK * KIMG + r * VROW : r * KROW) + pc * 16) = make_uint4(rg[u].x, rg[u].y, rg[u].z, rg[u].w);
+            } else if (img < NK) {
                 *(uint4 *) (st + img * KIMG + r * KROW + LY::k(r, pc)) = rg[u];
             } else {
                 // (two 8-B stores: written as one uint4 here the compiler merges both branches and moves rg to scratch)
@@ -633,6 +710,21 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // LDS writes done; global prefetch stays in flight
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+    };
+
+    // VR: this lane's part of a transposed read, d-tile 0: key row 8hi + q, q = (col & 15) >> 2, the 8 bytes of columns
+    // 16(col >> 4) + 4(col & 3) .. +3 in the row's swizzled half; d-tile dt at vrofs ^ 64dt
+    typedef short s4_t __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) s4_t * lds_s4p;
+    const int vq = (col & 15) >> 2;
+    const uint32_t vrofs = (uint32_t) ((8 * hi + vq) * VROW + ((vq >> 1) << 6) + ((col >> 4) << 5) + ((col & 3) << 3));
+    // the P.V A fragment of d-tile dt: keys 8hi .. 8hi + 7 of the 16 key rows at `rows`
+    auto vr_frag = [&](const char * rows, int dt) __attribute__((always_inline)) -> half8 {
+        const uint32_t a = (uint32_t) (uintptr_t) (const __attribute__((address_space(3))) char *) rows + (vrofs ^ (64u * dt));
+        const s4_t lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p) (uintptr_t) a);
+        const s4_t hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4p) (uintptr_t) (a + 4 * VROW));
+        const short8_t v8 = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+        return __builtin_bit_cast(half8, v8);
     };
 
     f16v o[2], sc[2];
@@ -650,7 +742,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
+                    for (int r = 0; r < 16; ++r) o[dt][r] = mul1<KL>(o[dt][r], alpha);
             }
             const char * vt_img = lds + ((t - 1) % NST) * STAGE + NK * KIMG;
 #pragma unroll
@@ -660,7 +752,9 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
                     const int vr = dt * 32 + col;
 #pragma unroll
                     for (int sp = 0; sp < 2; ++sp) {   // keys 32kb + 16sp + 8hi .. +7
-                        const half8 va = *(const half8 *) (vt_img + vr * VROW + (4 * kb + 2 * sp + hi) * 16);
+                        half8 va;
+                        if constexpr (VR) va = vr_frag(vt_img + (32 * kb + 16 * sp) * VROW, dt);
+                        else va = *(const half8 *) (vt_img + vr * VROW + (4 * kb + 2 * sp + hi) * 16);
                         o[dt] = mma32<BF>(va, pf[kb][sp], o[dt]);
                     }
                 }
@@ -688,12 +782,12 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
     };
     // VALU segment V(t): online-softmax update of tile t's scores -> pf, alpha (applied at the next P.V)
     auto valu_seg = [&](int t, int ntiles) __attribute__((always_inline)) {
-        if (t == ntiles - 1) {   // keys >= T exist only in the last tile (key of reg r: 16(r>>3) + 8hi + (r&7))
+        if (t == ntiles - 1) {   // keys >= Tk exist only in the last tile (key of reg r: 16(r>>3) + 8hi + (r&7))
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (t * KT + kb * 32 + 16 * (r >> 3) + 8 * hi + (r & 7) >= T) sc[kb][r] = -1e30f;
+                    if (t * KT + kb * 32 + 16 * (r >> 3) + 8 * hi + (r & 7) >= Tk) sc[kb][r] = -1e30f;
         }
         float mx0 = sc[0][0], mx1 = sc[1][0];
 #pragma unroll
@@ -716,7 +810,7 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
         m_run = m_new;
     };
 
-    const int ntiles = (T + KT - 1) / KT;
+    const int ntiles = (Tk + KT - 1) / KT;
     // prologue: tiles 0, 1, 2 into the three stages, every thread a share of each
     {
         // prologue staging by every thread: tile t's 2 halves = all CH chunks, 512 threads
@@ -728,10 +822,13 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
 #pragma unroll
             for (int u = 0; u < CH / 512; ++u) {
                 const int c = u * 512 + tid, img = c >> 9, r = (c >> 3) & 63, pc = c & 7;
-                if (img < NK) {
+                if constexpr (VR) {
+                    *(uint4 *) (st + (img ? NK * KIMG + r * VROW : r * KROW) + pc * 16) =
+                        *(const uint4 *) ((img ? vt_base : k_base) + (int64_t) min(kb0 + r, Tk - 1) * D + ((img ? pc ^ ((r & 2) << 1) : pc) * 8));
+                } else if (img < NK) {
                     const q2a_half * src = img == 0 ? p.kh : p.kl;
                     *(uint4 *) (st + img * KIMG + r * KROW + LY::k(r, pc)) =
-                        *(const uint4 *) (src + (rowbase + min(kb0 + r, T - 1)) * D + h * 64 + pc * 8);
+                        *(const uint4 *) (src + (rowbase + min(kb0 + r, Tk - 1)) * D + h * 64 + pc * 8);
                 } else {
                     *(uint4 *) (st + NK * KIMG + r * VROW + pc * 16) =
                         *(const uint4 *) (vt_base + (int64_t) r * p.TP + kb0 + pc * 8);
@@ -773,8 +870,8 @@ __global__ __launch_bounds__(512, 2) void k_attn_pp(const q2a_attn_args p) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d = dt * 32 + 8 * g + 4 * hi;
-                float v0 = o[dt][4 * g + 0] * inv, v1 = o[dt][4 * g + 1] * inv;
-                float v2 = o[dt][4 * g + 2] * inv, v3 = o[dt][4 * g + 3] * inv;
+                float v0 = mul1<KL>(o[dt][4 * g + 0], inv), v1 = mul1<KL>(o[dt][4 * g + 1], inv);
+                float v2 = mul1<KL>(o[dt][4 * g + 2], inv), v3 = mul1<KL>(o[dt][4 * g + 3], inv);
                 if (p.outH) {
                     // rounded to f32 first (no one-step fp16 rounding of the product): the fp16 output is the fp16 of
                     // the f32 output, bit for bit
@@ -798,11 +895,14 @@ bool q2a_attention_wants_vlo() { return true; }
 namespace {
 hipError_t launch_attention(const q2a_attn_args & a, hipStream_t s) {
     if (a.D != a.H * 64 || a.TP < ((a.T + KT - 1) / KT) * KT) return hipErrorInvalidValue;
-    if (a.key_len && (a.bf16 || !a.v_rows)) return hipErrorInvalidValue;   // key lengths: k_attn_t<true, *, true> only
+    if (a.key_len && !a.v_rows) return hipErrorInvalidValue;   // key lengths: the row-major-V kernels only
     if (a.bf16) {
-        // bf16 contract: the 8-wave ping-pong kernel (33 -> 30 ms/step at 64 clips against the 4-wave form)
-        if (!a.outH) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_attn_pp<true>, dim3(((a.T + 255) / 256) * a.H * a.n_clips), dim3(512), 0, s, a);
+        // bf16 contract: the 8-wave ping-pong kernel (33 -> 30 ms/step at 64 clips against the 4-wave form); with key
+        // lengths its KL form on row-major V (the grid stays a function of T and n_clips), without them V^T
+        if ((!a.outH && !a.outF) || (!a.key_len && a.v_rows)) return hipErrorInvalidValue;
+        const dim3 grid(((a.T + 255) / 256) * a.H * a.n_clips);
+        if (a.key_len) hipLaunchKernelGGL((k_attn_pp<true, true>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL(k_attn_pp<true>, grid, dim3(512), 0, s, a);
     } else {
         if (!a.vtl) return hipErrorInvalidValue;
         // 32 queries per wave, or 16 when that grid would leave CUs idle (one clip: 240 workgroups of 128 queries on
@@ -838,8 +938,8 @@ hipError_t Q2A_ATTN_LAUNCH(const q2a_attn_args & a, hipStream_t s) {
     return launch_attention(b, s);
 }
 
-// The launcher with per-clip key lengths: key_len != NULL selects k_attn_t<true, NQB, true> (hipErrorInvalidValue with
-// the bf16 contract or the V^T layout), NULL is q2a_launch_attention. Reads the fields up to key_len only: the packed
+// The launcher with per-clip key lengths: key_len != NULL selects k_attn_t<true, NQB, true>, under the bf16 contract
+// k_attn_pp<true, true> (hipErrorInvalidValue with the V^T layout), NULL is q2a_launch_attention. Reads the fields up to key_len only: the packed
 // fields behind it were appended later still.
 hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s) {
     q2a_attn_args b;
@@ -858,10 +958,17 @@ hipError_t q2a_launch_attention_len(const q2a_attn_args & a, hipStream_t s) {
 // a query's bits depend on is the KL form's. Its own instantiation again.
 // The packed launcher (the variable-length encode): k_attn_t<true, NQB, true, true> over ceil(r_max / QWG) query tiles
 // per (clip, head) — the grid follows the call's longest segment, not the window — in the XCD-contiguous order of the
-// other forms; the 64-query form when the 128-query grid would leave CUs idle (the same bits).
+// other forms; the 64-query form when the 128-query grid would leave CUs idle (the same bits). bf16 contract:
+// k_attn_pp<true, true, true> over ceil(r_max / 256) query tiles per (clip, head).
 hipError_t q2a_launch_attention_varlen(const q2a_attn_args & a, hipStream_t s) {
-    if (a.D != a.H * 64 || a.bf16 || !a.v_rows || !a.vtl || !a.key_len || !a.row_start) return hipErrorInvalidValue;
+    if (a.D != a.H * 64 || !a.v_rows || !a.key_len || !a.row_start) return hipErrorInvalidValue;
     if (a.n_clips <= 0 || a.r_max <= 0 || a.r_max > a.T) return hipErrorInvalidValue;
+    if (a.bf16) {
+        if (!a.outH && !a.outF) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_attn_pp<true, true, true>), dim3(((a.r_max + 255) / 256) * a.H * a.n_clips), dim3(512), 0, s, a);
+        return hipGetLastError();
+    }
+    if (!a.vtl) return hipErrorInvalidValue;
     const int n2 = ((a.r_max + 127) / 128) * a.H * a.n_clips;
     if (n2 < q2a_cu_count())
         hipLaunchKernelGGL((k_attn_t<true, 1, true, true>), dim3(((a.r_max + 63) / 64) * a.H * a.n_clips), dim3(256), 0, s, a);

@@ -127,6 +127,11 @@ struct q2a_engine {
     int TP = 0;
     int dy_ld = 0;
     bool force_encode = false;   // encode windows with under 1 s of audio too (whisper_full with duration_ms set)
+    // bf16 contract: the padded and variable-length kinds are served (q2a_set_bf16_key_lengths). Their calls write V
+    // row-major into vt, over the V^T image's zero pad columns T .. TP-1: vt_pad_dirty until the next plain call has
+    // cleared them again (k_zero_vt_pad)
+    bool bf16_key_lengths = false;
+    bool vt_pad_dirty = false;
     // Q4_K fc1 -> fc2 operand path (q2a_test_fc1_path; the three produce identical Q8_K codes):
     //   0 (default) fc1 writes its fp16 pre-activation, the Q8_K quantizer applies the GELU table on the way
     //   1 GELU in the fc1 epilogue, then the fp16-input quantizer
@@ -354,6 +359,7 @@ int reserve(q2a_engine * e, int B) {
     } else if (e->f32) {
         e->attF = (float *) (b + o_att);
     }
+    e->vt_pad_dirty = false;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return Q2A_OK;
 }
@@ -439,13 +445,30 @@ hipError_t launch_attention(q2a_attn_args & at, const block_rows & rows, hipStre
     return rows.row_start ? q2a_launch_attention_varlen(at, s) : rows.key_len ? q2a_launch_attention_len(at, s) : q2a_launch_attention(at, s);
 }
 
+// V^T [rows][TP]: the pad columns T .. TP-1 := 0 (what the workspace's clearing left there, and the plain bf16 attention
+// reads as zero-weight keys, after a key-length call has written V rows over the image)
+__global__ void k_zero_vt_pad(q2a_half * vt, int64_t rows, int T, int TP) {
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    const int np = TP - T;
+    if (i < rows * np) vt[(i / np) * TP + T + i % np] = (q2a_half) 0;
+}
+hipError_t launch_zero_vt_pad(q2a_half * vt, int64_t rows, int T, int TP, hipStream_t s) {
+    if (TP <= T || rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_zero_vt_pad, dim3((unsigned) ((rows * (TP - T) + 255) / 256)), dim3(256), 0, s, vt, rows, T, TP);
+    return hipGetLastError();
+}
+
 // ---- the four weight GEMMs of a block: their arguments, built here for run_block and for q2a_test_gemm_epi alike
 // (outputs into the workspace; the hook replaces the output pointers only)
-q2a_gemm_args qkv_gemm(const q2a_engine * e, int l, int M) {
+// the V layout of a block: row-major like K (v_rows) under the reference contract, and under the bf16 contract exactly
+// when the call carries key lengths (its key-length attention reads rows; the plain bf16 encode keeps V^T)
+int v_rows_of(const q2a_engine * e, bool lens) { return !e->bf16 || lens ? 1 : 0; }
+
+q2a_gemm_args qkv_gemm(const q2a_engine * e, int l, int M, bool lens = false) {
     q2a_gemm_args a = gemm_base(e, l, 0, e->actD, M);
     a.bias = e->lv<const float *>(l, L_BQKV);
     a.qh = e->qh; a.ql = e->ql; a.kh = e->kh; a.kl = e->kl; a.vt = e->vt; a.vtl = e->vtl;
-    a.v_rows = e->bf16 ? 0 : 1;   // reference contract: V hi / lo row-major like K (bf16 contract: V^T)
+    a.v_rows = v_rows_of(e, lens);
     // ggml_scale(Q, 1/sqrt(dh)) (:2054); the reference-contract attention also wants log2(e) folded in (its
     // softmax runs in log2 units): one f32 multiply by fl(log2 e)/8, 2^-3 being exact
     a.qscale = (1.0f / sqrtf((float) (e->d.D / e->d.H))) * (e->bf16 ? 1.0f : Q2A_LOG2E);
@@ -505,14 +528,21 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
     q2a_ln_args ln{X, M, d.D, e->lv<const float *>(l, L_LN1W), e->lv<const float *>(l, L_LN1B), mode, e->actD, e->dyD, e->aextD, e->dy_ld};
     PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln, s));
     LAUNCH(tap(0, e->actD, d.D));
+    const bool lens = rows.key_len != nullptr;
+    if (e->bf16 && lens) {
+        e->vt_pad_dirty = true;
+    } else if (e->bf16 && e->vt_pad_dirty) {
+        LAUNCH(launch_zero_vt_pad(e->vt, (int64_t) e->cap_clips * d.H * 64, d.T, e->TP, s));
+        e->vt_pad_dirty = false;
+    }
     {
-        const q2a_gemm_args a = qkv_gemm(e, l, M);
+        const q2a_gemm_args a = qkv_gemm(e, l, M, lens);
         PLAUNCH(e, s, Q2A_PROF_GEMM_QKV, q2a_launch_gemm(a, Q2A_EPI_QKV, e->gblk, s));
     }
     {
         q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, rows.B, d.T, d.D, d.H, e->TP, nullptr, nullptr, e->bf16 ? 1 : 0};
         at.vtl = e->vtl;
-        at.v_rows = e->bf16 ? 0 : 1;
+        at.v_rows = v_rows_of(e, lens);
         if (mode == 0 || mode == 4) at.outH = e->actD; else at.outF = e->attF;
         PLAUNCH(e, s, Q2A_PROF_ATTN, launch_attention(at, rows, s));
         if (mode == 3) {
@@ -788,7 +818,10 @@ int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, 
     const meta_rows dev(e->meta, B);
     rows = block_rows{B, B * e->d.T, e->X, nullptr, nullptr, 0};
     if (kind == ENC_PLAIN) return Q2A_OK;
-    if (e->bf16) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    if (e->bf16 && !e->bf16_key_lengths) {
+        set_err("key lengths: reference activation contract only (bf16: q2a_set_bf16_key_lengths)");
+        return Q2A_ERR_UNSUPPORTED;
+    }
     for (int c = 0; c < B; ++c)
         if (key_len[c] < 1 || key_len[c] > e->d.T) { set_err("clip %d: key_len %d outside 1..%d", c, key_len[c], e->d.T); return Q2A_ERR_ARG; }
     const bool packed = kind == ENC_PACKED;
@@ -865,10 +898,12 @@ hipError_t launch_gather_rows(const float * X, float * Xp, const int32_t * row_s
     return hipGetLastError();
 }
 
-// the key-length kinds exist for the reference activation contract only
-int lens_supported(const q2a_engine * e, encode_kind kind) {
-    if (kind == ENC_PLAIN || !e->bf16) return Q2A_OK;
-    set_err("%s: reference activation contract only", kind == ENC_PADDED ? "padded encode" : "variable-length encode");
+// the key-length kinds exist for the reference activation contract, and for the bf16 contract where the engine opted in
+// (q2a_set_bf16_key_lengths); the feature sinks (feats) for the reference contract alone: the projector has no bf16 mode
+int lens_supported(const q2a_engine * e, encode_kind kind, bool feats) {
+    if (kind == ENC_PLAIN || !e->bf16 || (e->bf16_key_lengths && !feats)) return Q2A_OK;
+    set_err("%s: reference activation contract only%s", feats ? "audio features" : kind == ENC_PADDED ? "padded encode" : "variable-length encode",
+            feats ? "" : " (bf16: q2a_set_bf16_key_lengths)");
     return Q2A_ERR_UNSUPPORTED;
 }
 
@@ -1119,7 +1154,7 @@ int encode(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_
     const bool feats = sink.features();
     if (B <= 0 || !in.data || !in.len || (feats ? kind != ENC_PACKED : !sink.out) || (kind != ENC_PLAIN && !kl)) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     if (in.offset_ms < 0) { set_err("offset_ms must be >= 0"); return Q2A_ERR_ARG; }
-    int rc = lens_supported(e, kind);
+    int rc = lens_supported(e, kind, feats);
     if (rc) return rc;
     const clip_facts facts = resolve_clips(e, in);
     if (feats && (rc = features_check(e, facts, kl, sink, proj))) return rc;
@@ -1315,6 +1350,13 @@ int q2a_set_force_encode(q2a_engine * e, int on) {
     return Q2A_OK;
 }
 
+int q2a_set_bf16_key_lengths(q2a_engine * e, int on) {
+    if (!e) return Q2A_ERR_ARG;
+    if (!e->bf16) { set_err("q2a_set_bf16_key_lengths: not a bf16-activation engine"); return Q2A_ERR_ARG; }
+    e->bf16_key_lengths = on != 0;
+    return Q2A_OK;
+}
+
 void q2a_close(q2a_engine * e) {
     if (!e) return;
     (void) hipSetDevice(e->device);
@@ -1348,9 +1390,10 @@ int q2a_reserve(q2a_engine * e, int max_clips, int64_t max_samples) {
 
 // the prologue of every encode and feature entry point: arguments, activation contract, and for the key-length kinds
 // the key lengths into kl (the caller's, checked, or the input's own valid lengths)
-static int call_prologue(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_t * key_len, std::vector<int32_t> & kl) {
+static int call_prologue(q2a_engine * e, encode_kind kind, const clip_input & in, const int32_t * key_len, std::vector<int32_t> & kl,
+                         bool feats = false) {
     if (!e || !in.len || in.B <= 0) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
-    if (int rc = lens_supported(e, kind)) return rc;
+    if (int rc = lens_supported(e, kind, feats)) return rc;
     return kind == ENC_PLAIN ? Q2A_OK : key_lens(e, in, key_len, kl);
 }
 
@@ -1366,7 +1409,7 @@ static bool kind_of(int kind, encode_kind & ek) {
 static int encode_device(q2a_engine * e, encode_kind kind, q2a_projector * p, const clip_input & in, const int32_t * key_len,
                          const out_sink & sink, int32_t * out_len, int32_t * status, void * stream) {
     std::vector<int32_t> kl;
-    if (int rc = call_prologue(e, kind, in, key_len, kl)) return rc;
+    if (int rc = call_prologue(e, kind, in, key_len, kl, sink.features())) return rc;
     if (!in.data) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
     // (without dst a _to call would be the f32 one's "embd alone")
     if (sink.to_dst() && !(p && sink.dst)) { set_err("audio features: the _to calls need a projector and a destination"); return Q2A_ERR_ARG; }
@@ -1647,7 +1690,7 @@ int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, con
 static int features_host(q2a_engine * e, q2a_projector * p, const host_clips & h, const int32_t * key_len, float * feat, float * embd,
                          int64_t rows_cap, int32_t * out_len, int32_t * status) {
     std::vector<int32_t> klv;
-    if (int rc = call_prologue(e, ENC_PACKED, h.in, key_len, klv)) return rc;
+    if (int rc = call_prologue(e, ENC_PACKED, h.in, key_len, klv, true)) return rc;
     const int32_t * kl = klv.data();
     const int n_clips = h.in.B;
     if (!h.ptr) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
@@ -2065,6 +2108,8 @@ int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x, int
 static int test_attention(q2a_engine * e, encode_kind kind, const float * q, const float * k, const float * v, int n_clips,
                           const int32_t * key_len, float * out, void * stream) {
     if (!e || n_clips <= 0 || (kind != ENC_PLAIN && !key_len) || (kind == ENC_PACKED && (!q || !k || !v || !out))) return Q2A_ERR_ARG;
+    // (the reference contract's kernels, whatever q2a_set_bf16_key_lengths says: the bf16 ones have q2a_test_attention_bf16)
+    if (e->bf16 && kind != ENC_PLAIN) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
@@ -2098,6 +2143,53 @@ int q2a_test_attention_len(q2a_engine * e, const float * q, const float * k, con
 int q2a_test_attention_varlen(q2a_engine * e, const float * q, const float * k, const float * v, int n_clips,
                               const int32_t * key_len, float * out, void * stream) {
     return test_attention(e, ENC_PACKED, q, k, v, n_clips, key_len, out, stream);
+}
+
+// v [clips*T][D] f32 -> the bf16 V^T image [clip][head][64][TP], pad columns T .. TP-1 zero
+__global__ void k_vt_bf16(const float * v, q2a_half * vt, int T, int TP, int D, int64_t n) {
+    const int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = (int) (i % TP);
+    const int64_t cd = i / TP;   // clip * D + head * 64 + d
+    const float x = t < T ? v[((cd / D) * T + t) * D + cd % D] : 0.f;
+    vt[i] = __builtin_bit_cast(_Float16, (__bf16) x);
+}
+
+// the bf16 contract's attention alone, on any engine and whatever q2a_set_bf16_key_lengths says: q (already scaled), k, v
+// rounded to bf16; out f32, the kernel's value before its bf16 rounding. ENC_PLAIN: k_attn_pp<true> on the V^T image
+// built here; the other kinds its key-length forms on V rows (windows, or the packed rows of q2a_varlen_rows)
+int q2a_test_attention_bf16(q2a_engine * e, int kind, const float * q, const float * k, const float * v, int n_clips,
+                            const int32_t * key_len, float * out, void * stream) {
+    encode_kind ek;
+    if (!e || !kind_of(kind, ek) || !q || !k || !v || !out || n_clips <= 0 || (ek != ENC_PLAIN && !key_len)) return Q2A_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = call_stream(stream);
+    int rc = reserve(e, n_clips);
+    if (rc) return rc;
+    block_rows rows;
+    const bool opted = e->bf16_key_lengths;
+    e->bf16_key_lengths = true;
+    rc = hook_rows(e, ek, key_len, n_clips, s, rows);
+    e->bf16_key_lengths = opted;
+    if (rc) return rc;
+    const dims & d = e->d;
+    const int64_t n = (int64_t) rows.M * d.D;
+    const dim3 g((unsigned) ((n + 255) / 256)), b(256);
+    hipLaunchKernelGGL(k_to_bf16, g, b, 0, s, q, e->qh, n);
+    hipLaunchKernelGGL(k_to_bf16, g, b, 0, s, k, e->kh, n);
+    if (ek == ENC_PLAIN) {
+        const int64_t nt = (int64_t) n_clips * d.D * e->TP;
+        hipLaunchKernelGGL(k_vt_bf16, dim3((unsigned) ((nt + 255) / 256)), b, 0, s, v, e->vt, d.T, e->TP, d.D, nt);
+    } else {
+        hipLaunchKernelGGL(k_to_bf16, g, b, 0, s, v, e->vt, n);
+        e->vt_pad_dirty = true;
+    }
+    LAUNCH(hipGetLastError());
+    q2a_attn_args at{e->qh, e->qh, e->kh, e->kh, e->vt, n_clips, d.T, d.D, d.H, e->TP, nullptr, out, 1};
+    at.vtl = nullptr;
+    at.v_rows = ek == ENC_PLAIN ? 0 : 1;
+    LAUNCH(launch_attention(at, rows, s));
+    return Q2A_OK;
 }
 
 // ---- downstream consumer: the Qwen2-Audio multi-modal projector ---------------------------

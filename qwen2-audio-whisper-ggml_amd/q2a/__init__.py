@@ -27,7 +27,7 @@ EXPORTS = (
     "q2a_valid_lengths", "q2a_encode_device_padded", "q2a_encode_host_padded", "q2a_test_attention_len",
     "q2a_test_block_len",
     "q2a_varlen_rows", "q2a_encode_device_varlen", "q2a_encode_host_varlen", "q2a_test_attention_varlen",
-    "q2a_test_block_varlen", "q2a_test_operand", "q2a_test_gemm_epi", "q2a_test_gemm_regime",
+    "q2a_test_block_varlen", "q2a_set_bf16_key_lengths", "q2a_test_attention_bf16", "q2a_test_operand", "q2a_test_gemm_epi", "q2a_test_gemm_regime",
     "q2a_mel_valid_lengths", "q2a_encode_device_mel", "q2a_encode_host_mel", "q2a_test_frontend_mel",
     "whisper_set_mel", "whisper_set_mel_with_state",
     "q2a_packed_out_rows", "q2a_audio_features_device", "q2a_audio_features_device_mel", "q2a_audio_features_host",
@@ -227,7 +227,10 @@ def lib() -> C.CDLL:
                          ("q2a_encode_device_varlen", [vp, vp, C.c_int64, i32p, i32p, i32p, C.c_int, vp, i32p, i32p, vp]),
                          ("q2a_encode_host_varlen", [vp, C.POINTER(vp), i32p, i32p, i32p, C.c_int, vp, i32p, i32p]),
                          ("q2a_test_attention_varlen", [vp, vp, vp, vp, C.c_int, i32p, vp, vp]),
-                         ("q2a_test_block_varlen", [vp, C.c_int, vp, C.c_int, i32p, vp])):
+                         ("q2a_test_block_varlen", [vp, C.c_int, vp, C.c_int, i32p, vp]),
+                         # the bf16 contract's key-length kinds: the opt-in and the attention hook
+                         ("q2a_set_bf16_key_lengths", [vp, C.c_int]),
+                         ("q2a_test_attention_bf16", [vp, C.c_int, vp, vp, vp, C.c_int, i32p, vp, vp])):
             if hasattr(L, name):
                 getattr(L, name).argtypes = at
         if hasattr(L, "q2a_test_operand"):   # (optional like the hooks above)
@@ -304,7 +307,9 @@ class Engine:
     """One encoder engine on one HIP device (the analogue of a whisper_context + whisper_state)."""
 
     def __init__(self, model_path: str | None = None, device: int = 0, device_blob: int | None = None,
-                 blob_size: int | None = None, act: int = ACT_REFERENCE):
+                 blob_size: int | None = None, act: int = ACT_REFERENCE, bf16_key_lengths: bool = False):
+        """bf16_key_lengths: a bf16-activation engine serves the padded and variable-length kinds too
+        (set_bf16_key_lengths)."""
         L = lib()
         if device_blob is not None:   # the blob carries its own activation contract
             h = L.q2a_open_device_blob(C.c_void_p(device_blob), C.c_int64(blob_size), device)
@@ -315,6 +320,14 @@ class Engine:
         self.h = h
         self.info = Info()
         _check(L.q2a_get_info(self.h, C.byref(self.info)))
+        if bf16_key_lengths:
+            self.set_bf16_key_lengths(True)
+
+    def set_bf16_key_lengths(self, on: bool = True):
+        """q2a_set_bf16_key_lengths: let this bf16-activation engine serve encode_*_padded, encode_*_varlen, the mel
+        kinds "padded" / "varlen" (encode_features) and test_block_len / test_block_varlen. Off (the default) they
+        raise rc -6. Raises for an engine of the reference contract."""
+        _check(lib().q2a_set_bf16_key_lengths(self.h, 1 if on else 0))
 
     def close(self):
         if self.h:
@@ -911,6 +924,15 @@ class Engine:
         _check(lib().q2a_test_attention_varlen(self.h, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
                                                kl.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(out_ptr),
                                                C.c_void_p(stream) if stream else None))
+
+    def test_attention_bf16(self, kind, q_ptr, k_ptr, v_ptr, n_clips, key_len, out_ptr, stream=None):
+        """q2a_test_attention_bf16: the bf16 contract's attention alone. kind: ENCODE_PLAIN (the plain kernel, key_len
+        may be None), ENCODE_PADDED (windows) or ENCODE_VARLEN (packed rows); q, k, v and out are f32."""
+        kl = None if key_len is None else np.ascontiguousarray(key_len, dtype=np.int32)
+        assert kl is None or len(kl) == n_clips
+        _check(lib().q2a_test_attention_bf16(self.h, kind, C.c_void_p(q_ptr), C.c_void_p(k_ptr), C.c_void_p(v_ptr), n_clips,
+                                             None if kl is None else kl.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             C.c_void_p(out_ptr), C.c_void_p(stream) if stream else None))
 
     def test_block_varlen(self, layer, x_ptr, n_clips, key_len, stream=None):
         kl = np.ascontiguousarray(key_len, dtype=np.int32)
