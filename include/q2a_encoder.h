@@ -100,8 +100,9 @@ int q2a_set_force_encode(q2a_engine * e, int on);
  * q2a_test_block_varlen run on the engine with their documented arguments, checks and results; every block of such a
  * call writes V row-major and runs the key-length form of the bf16 attention kernel, which gives a clip with
  * key_len = n_audio_ctx the plain bf16 encode's bytes. The plain entry points are unchanged either way.
- * q2a_audio_features_* and q2a_inputs_embeds_* keep answering Q2A_ERR_UNSUPPORTED on a bf16 engine: the projector has
- * no bf16 mode yet. */
+ * q2a_audio_features_* and q2a_inputs_embeds_* run on such an engine with a projector of the same contract
+ * (q2a_projector_open_ex with Q2A_ACT_BF16); Q2A_ERR_UNSUPPORTED, with nothing launched or written, without this opt-in
+ * or with a reference-contract projector (and for a bf16 projector on a reference-contract engine). */
 int q2a_set_bf16_key_lengths(q2a_engine * e, int on);
 
 void q2a_close(q2a_engine * e);
@@ -398,9 +399,22 @@ int q2a_test_attention_bf16(q2a_engine * e, int kind, const float * q_dev, const
  * reference has no projector). Weights: a projector file in the ggml container (multi_modal_projector.linear.weight
  * [d_out][d_in] F16 / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0, .bias [d_out] F32; bin/q2a_tool gen-projector + quantize). Numerics: a ggml
  * MUL_MAT of that weight type (activations per vec_dot_type, exact products, fp32 accumulation) + bias in f32.
- * d_out % 128 == 0; d_in % 256 == 0 (F16 weights: % 64), else q2a_projector_open fails. */
+ * d_out % 128 == 0; d_in % 256 == 0 (F16 weights: % 64), else q2a_projector_open fails.
+ *
+ * q2a_projector_open_ex: the same with an activation contract. Q2A_ACT_REFERENCE is q2a_projector_open. Q2A_ACT_BF16, for
+ * any of the six weight types under the same shape rules: the weight is dequantized with ggml's dequantize_row_* values
+ * (F16: the fp16 values), rounded to bf16 to nearest even and kept [d_out][d_in] without block scales, the layout of a
+ * bf16 engine's linears. Value contract of every call on such a projector:
+ *   y[m][n] = fl32(acc + bias[n]), acc = the f32 accumulation of the exact products bf16(x[m][k]) * bf16(w[n][k]) in the
+ *   GEMM's canonical K order (bf16 MFMA, every tile regime the same order); the 16-bit destination types of the _to /
+ *   _ids calls round that f32 once more, to nearest even.
+ * The operand is x rounded to bf16 (nearest even): no activation quantizer runs and the workspace holds no block scales.
+ * An unknown act returns NULL and sets the error. q2a_projector_get_act: the contract p was opened with (Q2A_ERR_ARG for
+ * NULL). */
 typedef struct q2a_projector q2a_projector;
 q2a_projector * q2a_projector_open(const char * path, int device);
+q2a_projector * q2a_projector_open_ex(const char * path, int device, int act);
+int q2a_projector_get_act(const q2a_projector * p);
 void q2a_projector_close(q2a_projector * p);
 int q2a_projector_get_dims(const q2a_projector * p, int * d_in, int * d_out, int * wtype);
 /* y_dev [rows][d_out] f32 = x_dev [rows][d_in] f32 (device) projected; asynchronous on `stream` (NULL = own stream).
@@ -432,7 +446,8 @@ int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int n_audio_ct
  *               or with q2a_packed_out_rows from the key lengths passed in
  * pcm_dev / mel_dev and their arguments, key_len (NULL: the derived lengths), status, the 1 s rule (PCM only) and stream
  * are those of q2a_encode_device_varlen / q2a_encode_device_mel. Every check — theirs, the output arguments above, p on
- * the engine's device with d_in = n_audio_state (Q2A_ERR_ARG), the reference activation contract (Q2A_ERR_UNSUPPORTED) —
+ * the engine's device with d_in = n_audio_state (Q2A_ERR_ARG), the activation contracts (Q2A_ERR_UNSUPPORTED for a bf16
+ * engine without q2a_set_bf16_key_lengths, and for a projector whose contract is not the engine's, p NULL excepted) —
  * is made before anything is launched or written. Rows at or past N_tot are never written; with no valid row at all
  * (every clip skipped, or every key length 1) the call returns Q2A_OK and launches nothing behind the metadata upload.
  * The activation operand lives in p's workspace: q2a_projector_apply's one-stream rule covers these calls too.
@@ -492,8 +507,9 @@ int64_t q2a_feat_rows(const int32_t * out_len, const int32_t * clip_row, int n_c
  * embd_rows_cap. Every check of the f32 calls, q2a_projector_apply_to's checks of dst and q2a_feat_rows' checks of the
  * ranges (over the clips that are encoded) are made before anything is launched or written. The device row map is built
  * inside the call by one small kernel from the call's single metadata upload (clip_row rides in it) and lives in p's
- * workspace; with clip_row NULL there is no map and no extra launch. Reference activation contract only
- * (Q2A_ERR_UNSUPPORTED otherwise). The host variants stay f32. */
+ * workspace; with clip_row NULL there is no map and no extra launch. The activation contracts as above: the engine's and
+ * the projector's must be equal, a bf16 engine must have q2a_set_bf16_key_lengths on (Q2A_ERR_UNSUPPORTED otherwise,
+ * nothing launched or written). The host variants stay f32. */
 int q2a_audio_features_device_to(q2a_engine * e, q2a_projector * p, const float * pcm_dev, int64_t pcm_stride,
                                  const int32_t * n_samples, const int32_t * offsets_ms, const int32_t * key_len, int n_clips,
                                  const q2a_feat_dst * dst, const int32_t * clip_row, float * embd_dev, int64_t embd_rows_cap,
@@ -603,8 +619,9 @@ int q2a_test_embed_gather(const q2a_embeds_src * src, const q2a_feat_dst * dst, 
 /* Test hook: the pool kernel of these calls alone, with the engine's final-LayerNorm weights, on caller rows.
  *   x_dev      packed [M_tot][n_audio_state] f32 (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx)
  *   embd_dev   [N_tot][n_audio_state] f32 (q2a_packed_out_rows over key_len), or NULL
- *   codes_dev, dy_dev, aext_dev, ld   the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0) for those N_tot rows in
- *              q2a_test_operand's layouts, ld >= N_tot; codes_dev NULL: no operand is written
+ *   codes_dev, dy_dev, aext_dev, ld   the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0, 4 bf16: the f32 row rounded to
+ *              nearest even, [N_tot][n_audio_state], no dy / aext) for those N_tot rows in q2a_test_operand's layouts,
+ *              ld >= N_tot (modes 1, 2); codes_dev NULL: no operand is written
  * The checks of q2a_test_block_varlen; nothing outside rows 0 .. N_tot-1 of any output is written. */
 int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
                           void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream);

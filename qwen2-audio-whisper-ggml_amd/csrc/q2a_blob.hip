@@ -446,16 +446,24 @@ uint64_t q2a_pack_layout(int wtype, int N, int K, uint64_t off[6]) {
     return o;
 }
 
-int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6]) {
-    const uint64_t o = q2a_pack_layout(wtype, N, K, off);
+int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6], int act) {
+    uint64_t o = q2a_pack_layout(wtype, N, K, off);
     if (!o) return Q2A_ERR_UNSUPPORTED;
+    if (act) {   // bf16 weights: the W section alone (expand_rows reads no other offset)
+        for (int i = 0; i < A_COUNT; ++i) off[i] = 0;
+        o = ((uint64_t) N * K * 2 + 255) & ~uint64_t(255);
+    }
     out.assign(o, 0);
     const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     std::vector<std::thread> th;
     for (unsigned t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() { expand_rows(raw, wtype, K, N, (int) ((int64_t) N * t / nt), (int) ((int64_t) N * (t + 1) / nt), out.data(), off, 0); });
+        th.emplace_back([&, t]() { expand_rows(raw, wtype, K, N, (int) ((int64_t) N * t / nt), (int) ((int64_t) N * (t + 1) / nt), out.data(), off, 0, act); });
     for (auto & x : th) x.join();
     return Q2A_OK;
+}
+
+int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6]) {
+    return q2a_pack_linear(raw, wtype, N, K, out, off, Q2A_ACT_REFERENCE);
 }
 
 namespace {

@@ -161,6 +161,7 @@ struct q2a_projector {
     int device = 0;
     hipStream_t stream = nullptr;
     int d_in = 0, d_out = 0, wtype = 0, blk = 0, gblk = 0;   // blk: activation block, gblk: the GEMM's block mode
+    int act = Q2A_ACT_REFERENCE;    // Q2A_ACT_BF16: bf16 weight and operand, blk 0, gblk Q2A_BLK_BF16
     void * wdev = nullptr;          // q2a_pack_linear layout
     uint64_t off[A_COUNT] = {};
     float * bias = nullptr;
@@ -898,12 +899,12 @@ hipError_t launch_gather_rows(const float * X, float * Xp, const int32_t * row_s
     return hipGetLastError();
 }
 
-// the key-length kinds exist for the reference activation contract, and for the bf16 contract where the engine opted in
-// (q2a_set_bf16_key_lengths); the feature sinks (feats) for the reference contract alone: the projector has no bf16 mode
+// the key-length kinds, the feature sinks (feats) among them, exist for the reference activation contract, and for the
+// bf16 contract where the engine opted in (q2a_set_bf16_key_lengths)
 int lens_supported(const q2a_engine * e, encode_kind kind, bool feats) {
-    if (kind == ENC_PLAIN || !e->bf16 || (e->bf16_key_lengths && !feats)) return Q2A_OK;
-    set_err("%s: reference activation contract only%s", feats ? "audio features" : kind == ENC_PADDED ? "padded encode" : "variable-length encode",
-            feats ? "" : " (bf16: q2a_set_bf16_key_lengths)");
+    if (kind == ENC_PLAIN || !e->bf16 || e->bf16_key_lengths) return Q2A_OK;
+    set_err("%s: reference activation contract only (bf16: q2a_set_bf16_key_lengths)",
+            feats ? "audio features" : kind == ENC_PADDED ? "padded encode" : "variable-length encode");
     return Q2A_ERR_UNSUPPORTED;
 }
 
@@ -921,8 +922,8 @@ struct proj_operand {
     int32_t * chunk_count;
     int32_t * report;
 };
-// the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0 (q2a_ln_args' modes)
-int proj_mode(const q2a_projector * p) { return p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
+// the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0, and 4 bf16 for a bf16 projector (q2a_ln_args' modes)
+int proj_mode(const q2a_projector * p) { return p->act == Q2A_ACT_BF16 ? 4 : p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
 
 // grows the workspace (after everything queued on s: calls on one handle are ordered on one stream) and cuts it up
 int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o, bool with_map = false, int64_t ids_tokens = 0) {
@@ -949,6 +950,23 @@ int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand 
     o.map = with_map ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes) : nullptr;
     o.chunk_count = ids_tokens > 0 ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes + map_bytes) : nullptr;
     o.report = ids_tokens > 0 ? (int32_t *) ((char *) p->ws + a_bytes + dy_bytes + ae_bytes + map_bytes + cc_bytes) : nullptr;
+    return Q2A_OK;
+}
+
+// the operand of the q2a_projector_apply* calls from the caller's f32 rows x [M][d_in]: the fp16 or (bf16 projector) bf16
+// cast, or the weight type's activation quantizer
+int proj_operand_from(const q2a_projector * p, const float * x, int M, const proj_operand & o, hipStream_t s) {
+    const int mode = proj_mode(p);
+    if (mode == 0 || mode == 4) {
+        const int64_t n = (int64_t) M * p->d_in;
+        const dim3 grid((unsigned) ((n + 255) / 256)), blk(256);
+        if (mode == 4) hipLaunchKernelGGL(k_to_bf16, grid, blk, 0, s, x, o.A, n);
+        else hipLaunchKernelGGL(k_to_half, grid, blk, 0, s, x, o.A, n);
+        LAUNCH(hipGetLastError());
+    } else {
+        q2a_quant_args qa{x, nullptr, M, p->d_in, mode, o.A, o.dy, o.aext, o.ld};
+        LAUNCH(q2a_launch_quant_act(qa, s));
+    }
     return Q2A_OK;
 }
 
@@ -1114,6 +1132,12 @@ int features_check(const q2a_engine * e, const clip_facts & f, const int32_t * k
         set_err("audio features: projector on device %d with d_in %d, engine on device %d with n_audio_state %d", proj->device,
                 proj->d_in, e->device, e->d.D);
         return Q2A_ERR_ARG;
+    }
+    // one activation contract for the pair: the pool kernel writes the projector's operand, the engine's numerics end in it
+    if (proj && proj->act != (e->bf16 ? Q2A_ACT_BF16 : Q2A_ACT_REFERENCE)) {
+        set_err("audio features: %s engine with a %s projector (q2a_projector_open_ex)", e->bf16 ? "bf16" : "reference-contract",
+                proj->act == Q2A_ACT_BF16 ? "bf16" : "reference-contract");
+        return Q2A_ERR_UNSUPPORTED;
     }
     const int B = (int) f.ok.size();
     std::vector<int32_t> ol(B);
@@ -2047,7 +2071,7 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
 // the audio-feature tail's pool kernel alone, straight from the caller's packed rows into the caller's buffers
 int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
                           void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream) {
-    if (!e || !x_dev || n_clips <= 0 || !key_len || mode < 0 || mode > 2) return Q2A_ERR_ARG;
+    if (!e || !x_dev || n_clips <= 0 || !key_len || mode < 0 || mode == 3 || mode > 4) return Q2A_ERR_ARG;
     if (!codes_dev) mode = -1;   // no operand: the f32 rows alone
     if (mode < 0 && !embd_dev) return Q2A_ERR_ARG;
     if ((mode == 1 && (!dy_dev || !aext_dev || e->d.D % 256)) || (mode == 2 && (!dy_dev || e->d.D % 32))) return Q2A_ERR_ARG;
@@ -2058,7 +2082,7 @@ int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_c
     block_rows rows;
     if ((rc = hook_rows(e, ENC_PACKED, key_len, n_clips, s, rows, true))) return rc;
     if (rows.N_out == 0) return Q2A_OK;
-    if (mode > 0 && ld < rows.N_out) { set_err("ld %d below the %d output rows", ld, rows.N_out); return Q2A_ERR_ARG; }
+    if ((mode == 1 || mode == 2) && ld < rows.N_out) { set_err("ld %d below the %d output rows", ld, rows.N_out); return Q2A_ERR_ARG; }
     const meta_rows dev(e->meta, n_clips);
     q2a_pool_pack_args pa{x_dev, n_clips, e->d.D, rows.N_out, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B),
                           dev.row_start, dev.out_start, embd_dev, mode, (q2a_half *) codes_dev, dy_dev, (q2a_half *) aext_dev, ld};
@@ -2199,7 +2223,12 @@ int q2a_test_attention_bf16(q2a_engine * e, int kind, const float * q, const flo
 // ggml MUL_MAT of that weight type: activations converted per vec_dot_type (fp16 RNE for F16, Q8_K for Q4_K, Q8_0 for
 // Q8_0 / Q4_0), exact products, fp32 accumulation in the canonical K order, then + bias in f32 — on the same GEMM.
 // (struct q2a_projector and the GEMM arguments: with the engine above, the audio-feature tail of encode() runs them too)
-q2a_projector * q2a_projector_open(const char * path, int device) {
+q2a_projector * q2a_projector_open(const char * path, int device) { return q2a_projector_open_ex(path, device, Q2A_ACT_REFERENCE); }
+
+// Q2A_ACT_BF16: the weight as a bf16 engine's linears (q2a_pack_linear with act), the bf16 x bf16 GEMM, no block scales
+q2a_projector * q2a_projector_open_ex(const char * path, int device, int act) {
+    if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("projector: unknown activation mode %d", act); return nullptr; }
+    const bool bf16 = act == Q2A_ACT_BF16;
     char err[256] = {0};
     q2a_model_file * mf = q2a_model_file_read(path, err, sizeof(err));
     if (!mf) { set_err("projector %s: %s", path ? path : "(null)", err); return nullptr; }
@@ -2218,12 +2247,14 @@ q2a_projector * q2a_projector_open(const char * path, int device) {
         return fail(Q2A_ERR_UNSUPPORTED, "d_out must be a multiple of 128, d_in of 256 (F16 weights: of 64)");
     std::vector<uint8_t> packed;
     uint64_t off[A_COUNT];
-    if (q2a_pack_linear(mf->data + wt->offset, wt->type, N, K, packed, off) != Q2A_OK)
+    if (q2a_pack_linear(mf->data + wt->offset, wt->type, N, K, packed, off, act) != Q2A_OK)
         return fail(Q2A_ERR_UNSUPPORTED, "weight type not supported (F16, Q4_K, Q5_K, Q6_K, Q8_0, Q4_0)");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) { (void) hipGetLastError(); return fail(Q2A_ERR_HIP, "no such HIP device"); }
     q2a_projector * p = new q2a_projector();
-    p->device = device; p->d_in = K; p->d_out = N; p->wtype = wt->type; p->blk = blk_of(wt->type); p->gblk = gblk_of(wt->type);
+    p->device = device; p->d_in = K; p->d_out = N; p->wtype = wt->type; p->act = act;
+    p->blk = bf16 ? 0 : blk_of(wt->type);
+    p->gblk = bf16 ? Q2A_BLK_BF16 : gblk_of(wt->type);
     for (int i = 0; i < A_COUNT; ++i) p->off[i] = off[i];
     std::vector<uint16_t> gtab(65536);
     q2a_make_gelu_table(gtab.data());
@@ -2263,21 +2294,16 @@ int q2a_projector_get_dims(const q2a_projector * p, int * d_in, int * d_out, int
     return Q2A_OK;
 }
 
+int q2a_projector_get_act(const q2a_projector * p) { return p ? p->act : Q2A_ERR_ARG; }
+
 int q2a_projector_apply(q2a_projector * p, const float * x, int64_t rows, float * y, void * stream) {
     if (!p || !x || !y || rows <= 0 || rows > (1 << 30) / 4) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = call_stream(stream);
-    const int M = (int) rows, K = p->d_in;
+    const int M = (int) rows;
     proj_operand o;
     if (int rc = proj_workspace(p, rows, s, o)) return rc;
-    if (p->blk == 0) {
-        const int64_t n = (int64_t) M * K;
-        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
-        LAUNCH(hipGetLastError());
-    } else {
-        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
-        LAUNCH(q2a_launch_quant_act(qa, s));
-    }
+    if (int rc = proj_operand_from(p, x, M, o, s)) return rc;
     LAUNCH(q2a_launch_gemm(proj_gemm(p, M, o, y), Q2A_EPI_STORE_F, p->gblk, s));
     return Q2A_OK;
 }
@@ -2289,17 +2315,10 @@ int q2a_projector_apply_to(q2a_projector * p, const float * x, int64_t rows, con
     if (!row_map && rows > dst->n_rows) { set_err("feature destination: %lld rows into n_rows %lld", (long long) rows, (long long) dst->n_rows); return Q2A_ERR_ARG; }
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = call_stream(stream);
-    const int M = (int) rows, K = p->d_in;
+    const int M = (int) rows;
     proj_operand o;
     if (int rc = proj_workspace(p, rows, s, o)) return rc;
-    if (p->blk == 0) {
-        const int64_t n = (int64_t) M * K;
-        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
-        LAUNCH(hipGetLastError());
-    } else {
-        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
-        LAUNCH(q2a_launch_quant_act(qa, s));
-    }
+    if (int rc = proj_operand_from(p, x, M, o, s)) return rc;
     LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, row_map), Q2A_EPI_STORE_ROWS, p->gblk, s));
     return Q2A_OK;
 }
@@ -2314,20 +2333,13 @@ static int projector_apply_ids(q2a_projector * p, const float * x, int64_t rows,
         if (int rc = embed_qtable_check(qt, *src, p->d_out)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = call_stream(stream);
-    const int M = (int) rows, K = p->d_in;
+    const int M = (int) rows;
     proj_operand o;
     if (int rc = proj_workspace(p, rows, s, o, true, src->n_tokens)) return rc;
     int32_t * report = src->report_dev ? src->report_dev : o.report;
     LAUNCH(q2a_launch_audio_token_rows(ids_args(src->input_ids, src->ids_width, src->n_tokens, src->audio_token_id, M, o, report), s));
     LAUNCH(launch_embeds_gather(text_rows{src, qt}, *dst, p->d_out, report, s));
-    if (p->blk == 0) {
-        const int64_t n = (int64_t) M * K;
-        hipLaunchKernelGGL(k_to_half, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, o.A, n);
-        LAUNCH(hipGetLastError());
-    } else {
-        q2a_quant_args qa{x, nullptr, M, K, proj_mode(p), o.A, o.dy, o.aext, o.ld};
-        LAUNCH(q2a_launch_quant_act(qa, s));
-    }
+    if (int rc = proj_operand_from(p, x, M, o, s)) return rc;
     LAUNCH(q2a_launch_gemm(proj_gemm_to(p, M, o, *dst, o.map), Q2A_EPI_STORE_ROWS, p->gblk, s));
     return Q2A_OK;
 }

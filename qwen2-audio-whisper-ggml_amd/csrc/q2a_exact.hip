@@ -708,7 +708,7 @@ __global__ __launch_bounds__(256) void k_pool_ln_varlen(const q2a_pool_varlen_ar
 
 // k_pool_ln_varlen's valid rows packed one clip after the other, each written as f32 and / or as the A operand of the
 // GEMM that follows (q2a_pool_pack_args): the f32 row is pool_ln_regs', the operand the LayerNorm kernels' conversion of
-// it (k_to_half's cast, quant_q8k_block(s), quant_q80_block), so both equal what k_pool_ln_varlen, a gather of the valid
+// it (k_to_half's cast, quant_q8k_block(s), quant_q80_block, MODE 4: k_to_bf16's cast), so both equal what k_pool_ln_varlen, a gather of the valid
 // rows and the quantizer launch give. One wave per destination row n. Its clip c is the number of entries
 // out_start[1 .. n_clips] at or below n (out_start never decreases; a clip without rows is stepped over), counted 64
 // entries at a time with one load and a ballot; the row's loads are all issued before its arithmetic.
@@ -758,6 +758,9 @@ __device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
             if (MODE == 0) {
                 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
                 *(h4_t *) o = h4_t{(_Float16) v[u].x, (_Float16) v[u].y, (_Float16) v[u].z, (_Float16) v[u].w};
+            } else if (MODE == 4) {   // bf16 operand: the LayerNorm kernels' mode-4 conversion (RNE), one 8-B store
+                typedef __bf16 b4_t __attribute__((ext_vector_type(4)));
+                *(b4_t *) o = b4_t{(__bf16) v[u].x, (__bf16) v[u].y, (__bf16) v[u].z, (__bf16) v[u].w};
             } else if (MODE == 1) {
                 quant_q8k_block(v[u], lane, o, p.dy + (int64_t) u * p.dy_ld + n, p.aext + ((int64_t) u * p.dy_ld + n) * 16);
             } else {
@@ -770,6 +773,17 @@ __device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
 template <int MODE>
 __global__ __launch_bounds__(256) void k_poolnorm_pack(const q2a_pool_pack_args p) {
     pool_pack_rows<MODE, 0>(p);
+}
+
+// the bf16 operand (MODE 4, a bf16 projector behind a bf16-activation engine): a kernel of its own whose f32 arithmetic
+// is compiled to scalar instructions (no packed-f32 forms), the operations and their order unchanged
+#ifdef __HIP_DEVICE_COMPILE__
+#define Q2A_SCALAR_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define Q2A_SCALAR_F32   // (the host pass knows no such feature)
+#endif
+__global__ __launch_bounds__(256) Q2A_SCALAR_F32 void k_poolnorm_pack_bf16(const q2a_pool_pack_args p) {
+    pool_pack_rows<4, 0>(p);
 }
 
 // rows of D = 1280 (the model width) into a Q8_K operand: 8 rows per 512-thread workgroup
@@ -887,7 +901,7 @@ hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t
 
 hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048 || a.n_clips < 1 || a.N_tot < 1 || !a.X || !a.row_start || !a.out_start) return hipErrorInvalidValue;
-    if (a.mode < -1 || a.mode > 2 || (a.mode < 0 ? !a.embd : !a.outH)) return hipErrorInvalidValue;
+    if (a.mode < -1 || a.mode == 3 || a.mode > 4 || (a.mode < 0 ? !a.embd : !a.outH)) return hipErrorInvalidValue;
     if (a.mode == 1 && (a.D % 256 || !a.dy || !a.aext || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
     if (a.mode == 2 && (a.D % 32 || !a.dy || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
     const dim3 grid((a.N_tot + 3) / 4), blk(256);
@@ -895,6 +909,7 @@ hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s) {
     else if (a.mode == 1) hipLaunchKernelGGL(k_poolnorm_pack<1>, grid, blk, 0, s, a);
     else if (a.mode == 2) hipLaunchKernelGGL(k_poolnorm_pack<2>, grid, blk, 0, s, a);
     else if (a.mode == 0) hipLaunchKernelGGL(k_poolnorm_pack<0>, grid, blk, 0, s, a);
+    else if (a.mode == 4) hipLaunchKernelGGL(k_poolnorm_pack_bf16, grid, blk, 0, s, a);
     else hipLaunchKernelGGL(k_poolnorm_pack<-1>, grid, blk, 0, s, a);
     return hipGetLastError();
 }

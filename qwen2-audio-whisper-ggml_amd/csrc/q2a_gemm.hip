@@ -1422,7 +1422,8 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
     const int pcol = 16 * (q & 1) + 8 * (q >> 1);    // column of this lane's 16-B piece within a 32-column pair
     if constexpr (EPI == Q2A_EPI_STORE_ROWS) {
         // fl32(acc + bias) — STORE_F's value with store_bias — as f32, fp16 or bf16 (p.out_dt, wave-uniform: one scalar
-        // branch per tile, so the twelve tile instantiations serve the three types) into destination row
+        // branch per tile, so the sixteen tile instantiations, the four bf16 x bf16 ones among them, serve the three types)
+        // into destination row
         // row_map[m] (NULL: m) of out_rows, rows outside [0, n_rows) dropped. Whole 128-B lines per store, as the
         // branches below: after line_pair a lane stores rows 16i + (l & 7) and 16i + 8 + (l & 7), so those two row
         // indices are what it reads, once per 16-row block and for all column tiles, before the first value is formed.
@@ -1992,8 +1993,9 @@ q2a_gemm_plan q2a_gemm_plan_of(const q2a_gemm_args & a, int epi, int blk, int cu
     const q2a_gemm_plan none{Q2A_REGIME_NONE, 0, 0};
     if (epi == Q2A_EPI_STORE_ROWS) {
         // STORE_F's decision for the same arguments (the K order and the accumulators are then STORE_F's), in the weight
-        // modes a projector has; never split, never grouped
-        if (!(blk == 0 || blk == 256 || blk == 32 || blk == Q2A_BLK_Q6K) || a.ksplit > 1 || a.ngroup == 2) return none;
+        // modes a projector has (bf16 x bf16 for a projector of the bf16 contract); never split, never grouped
+        if (!(blk == 0 || blk == 256 || blk == 32 || blk == Q2A_BLK_Q6K || blk == Q2A_BLK_BF16) || a.ksplit > 1 || a.ngroup == 2)
+            return none;
         epi = Q2A_EPI_STORE_F;
     }
     const bool big = wide_tiles(a.M, a.N);
@@ -2084,7 +2086,9 @@ hipError_t launch_epi(const q2a_gemm_args & a, int blk, hipStream_t s) {
                       EPI == Q2A_EPI_STORE_F || EPI == Q2A_EPI_STORE_ROWS) {
             if (blk == Q2A_BLK_Q6K) return launch_cfg<128, 128, 2, 2, EPI, Q2A_BLK_Q6K>(a, s);
         }
-        if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_STORE_F) {
+        // (STORE_ROWS: the four bf16 tiles with the row-map epilogue; launch_pipe8 gives it the plain 8-phase grid)
+        if constexpr (EPI == Q2A_EPI_QKV || EPI == Q2A_EPI_RESID || EPI == Q2A_EPI_GELU_H || EPI == Q2A_EPI_STORE_F ||
+                      EPI == Q2A_EPI_STORE_ROWS) {
             if (blk == Q2A_BLK_BF16) {
                 constexpr int B16 = Q2A_BLK_BF16;
                 if (p8) return launch_pipe8<EPI, B16>(a, pl, s);

@@ -278,6 +278,11 @@ hipError_t q2a_launch_gelu_quant_q8k(const q2a_half * XH, int M, int K, const ui
 #ifdef __cplusplus
 #include <vector>
 int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6]);
+// act = Q2A_ACT_BF16: the bf16-activation engines' form of a linear instead, W [N][K] alone — the dequantized weight
+// (ggml's dequantize_row_* values) rounded to bf16 to nearest even, no scale sections (off[1..5] = 0). An overload and
+// not a defaulted argument: the plugin's object is also linked into programs built apart from the library, and one
+// compiled before `act` existed must still find the six-argument symbol in this libq2a.so.
+int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6], int act);
 // the section offsets of q2a_pack_linear's layout (W [N][K] fp16 | dx | dmin | wext | beta | gamma, the per-block
 // sections block-major [K/blk][N](x16 for wext)) and its total bytes (0 = unsupported type or shape)
 uint64_t q2a_pack_layout(int wtype, int N, int K, uint64_t off[6]);
@@ -308,8 +313,8 @@ struct q2a_pool_varlen_args {
 hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t s);
 // The same rows packed, and the next GEMM's A operand with them: destination row n = out_start[c] + j (j < key_len[c] / 2)
 // pools packed rows row_start[c] + 2j, + 1 with k_pool_ln's operations in its order and writes the f32 row to embd[n]
-// (NULL: not written) and its conversion (mode 0 fp16, 1 Q8_K, 2 Q8_0: q2a_ln_args' layouts, computed from that f32
-// value) to outH / dy / aext (mode -1: none). N_tot = out_start[n_clips] (q2a_packed_out_rows); nothing outside rows
+// (NULL: not written) and its conversion (mode 0 fp16, 1 Q8_K, 2 Q8_0, 4 bf16 RNE: q2a_ln_args' layouts, computed from
+// that f32 value) to outH / dy / aext (mode -1: none; modes 0 and 4 write outH alone). N_tot = out_start[n_clips] (q2a_packed_out_rows); nothing outside rows
 // 0 .. N_tot-1 of any output is written.
 struct q2a_pool_pack_args {
     const float * X;             // [M_tot][D] packed

@@ -38,6 +38,7 @@ EXPORTS = (
     "q2a_test_audio_token_rows", "q2a_test_embed_gather",
     "q2a_dequantize_row", "q2a_projector_apply_ids_q", "q2a_inputs_embeds_device_q", "q2a_inputs_embeds_device_mel_q",
     "q2a_test_embed_gather_q",
+    "q2a_projector_open_ex", "q2a_projector_get_act",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -289,6 +290,9 @@ def lib() -> C.CDLL:
             L.q2a_test_embed_gather_q.argtypes = [srcp, qtp, dstp, C.c_int32, vp]
         L.q2a_projector_open.restype = vp
         L.q2a_projector_open.argtypes = [C.c_char_p, C.c_int]
+        L.q2a_projector_open_ex.restype = vp
+        L.q2a_projector_open_ex.argtypes = [C.c_char_p, C.c_int, C.c_int]
+        L.q2a_projector_get_act.argtypes = [vp]
         L.q2a_projector_close.argtypes = [vp]
         L.q2a_projector_get_dims.argtypes = [vp, i32p, i32p, i32p]
         L.q2a_projector_apply.argtypes = [vp, vp, C.c_int64, vp, vp]
@@ -836,7 +840,7 @@ class Engine:
 
     def test_pool_operand(self, mode, x_ptr, n_clips, key_len, embd_ptr=0, codes_ptr=0, dy_ptr=0, aext_ptr=0, ld=0, stream=None):
         """q2a_test_pool_operand: the audio-feature calls' pool kernel alone on packed caller rows x [M_tot][D] ->
-        embd [N_tot][D] f32 and / or the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0) in test_operand's layouts."""
+        embd [N_tot][D] f32 and / or the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0, 4 bf16) in test_operand's layouts."""
         kl = np.ascontiguousarray(key_len, dtype=np.int32)
         assert len(kl) == n_clips
         p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
@@ -1199,12 +1203,17 @@ class Group:
 
 class Projector:
     """The Qwen2-Audio multi-modal projector (Linear d_model -> text hidden, bias) on the GPU: the consumer of embd_enc
-    (include/q2a_encoder.h, q2a_projector_*). No CPU fallback."""
+    (include/q2a_encoder.h, q2a_projector_*). No CPU fallback.
 
-    def __init__(self, path: str, device: int = 0):
-        self.h = lib().q2a_projector_open(path.encode(), device)
+    act=ACT_BF16 (q2a_projector_open_ex): the weight rounded to bf16, the operand x rounded to bf16, bf16 MFMA with f32
+    accumulation and the f32 bias add; the projector a bf16-activation engine's audio_features / inputs_embeds take (the
+    engine with set_bf16_key_lengths on). The contract is in .act."""
+
+    def __init__(self, path: str, device: int = 0, act: int = ACT_REFERENCE):
+        self.h = lib().q2a_projector_open_ex(path.encode(), device, act)
         if not self.h:
             raise Q2AError(lib().q2a_last_error().decode())
+        self.act = lib().q2a_projector_get_act(self.h)
         a, b, w = C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().q2a_projector_get_dims(self.h, C.byref(a), C.byref(b), C.byref(w)))
         self.d_in, self.d_out, self.wtype = a.value, b.value, w.value
