@@ -318,15 +318,17 @@ int q2a_test_fc1_path(q2a_engine * e, int path);
  * arguments and dispatch of the encoder block and q2a_test_linear. The engine supplies the device, the stream and the
  * GELU table only: M and K are free (any model file serves), within the launchers' own limits.
  *   producer  Q2A_OPERAND_LN         LayerNorm(x; g, b) + conversion: x f32 [M][K], g, b f32 [K], K % 4 == 0, K <= 2048;
- *                                    mode 0 fp16, 1 Q8_K, 2 Q8_0, 3 the F32 files' split [M][3K] = hi | lo | hi, 4 bf16
+ *                                    mode 0 fp16, 1 Q8_K, 2 Q8_0, 3 the F32 files' split [M][3K] = hi | lo | hi, 4 bf16,
+ *                                    5 Q8_K with raw 16-sums (the operand of Q2_K weights; K % 256 == 0)
  *             Q2A_OPERAND_QUANT_F32  quantizer of f32 rows x [M][K] (the O-projection operand; K > 2048: the 1024-wide
- *                                    segments of the fc2 operand), mode 1 or 2, K % 256 == 0, K <= 8192
+ *                                    segments of the fc2 operand), mode 1, 2 or 5, K % 256 == 0, K <= 8192
  *             Q2A_OPERAND_QUANT_H16  the same on fp16 rows x [M][K]
- *             Q2A_OPERAND_GELU_Q8K   GELU table + Q8_K of fp16 pre-activation rows x [M][K], mode 1, M * K < 2^31
+ *             Q2A_OPERAND_GELU_Q8K   GELU table + Q8_K of fp16 pre-activation rows x [M][K], mode 1 or 5, M * K < 2^31
  *   out       [M][K] 2-byte elements (mode 3: [M][3K]): fp16 / bf16 values, or the integer codes held in fp16
- *   dy        modes 1, 2: the block scales, block-major f32 [K/256 or K/32][ld], block bf of row m at dy[bf * ld + m]
+ *   dy        modes 1, 2, 5: the block scales, block-major f32 [K/256 or K/32][ld], block bf of row m at dy[bf * ld + m]
  *   aext      mode 1: the block-sum operand, fp16 [K/256][ld][16] — for each of the 8 32-wide sub-blocks the pair
- *             (hi, lo), bsum32 = 64 hi + lo, 0 <= lo < 64
+ *             (hi, lo), bsum32 = 64 hi + lo, 0 <= lo < 64; mode 5: the sums of the 16 16-wide sub-blocks themselves
+ *             (|s| <= 2032, exact in fp16), codes and dy being mode 1's bit for bit
  *   ld        leading dimension of dy and aext, >= M
  * Nothing outside rows 0 .. M-1 of out, dy and aext is written. g, b, dy, aext may be NULL where the mode has no use
  * for them. Q2A_ERR_ARG for anything else. */
@@ -575,17 +577,18 @@ int q2a_inputs_embeds_device_mel(q2a_engine * e, q2a_projector * p, const float 
 /* ---- a quantized embedding table: the text rows decoded from ggml blocks on the device ---------------------------------
  * A GGUF language model's token_embd.weight as it lies in the file: vocab rows of n_cols / block size ggml blocks, row r
  * at rows + r * row_bytes. The _q calls below are the ids calls with this table as the source of the text rows, src's
- * embed_table being NULL: row t of the destination becomes the n_cols values ggml's dequantize_row_q4_0 / q8_0 / q4_K /
- * q5_K / q6_K gives for row input_ids[t] — bit for bit as f32; for fp16 / bf16 destinations that f32 value rounded once
+ * embed_table being NULL: row t of the destination becomes the n_cols values ggml's dequantize_row_q4_0 / q8_0 / q2_K / q3_K /
+ * q4_K / q5_K / q6_K gives for row input_ids[t] — bit for bit as f32; for fp16 / bf16 destinations that f32 value rounded once
  * more to nearest even — by a kernel that brings the raw row into LDS and decodes it there. Nothing else differs: the
  * map, the report words, the order of the launches, the profile class, the N_tot = 0 rule and the activation contract
  * are the ids calls'. Further checks, made with theirs before anything is launched or written (Q2A_ERR_ARG): qt and
- * qt->rows non-NULL, rows 16-byte aligned, ggml_type one of the five, reserved 0, vocab >= 1, n_cols == d_out and a
+ * qt->rows non-NULL, rows 16-byte aligned, ggml_type one of the seven, reserved 0, vocab >= 1, n_cols == d_out and a
  * multiple of 256, row_bytes a multiple of 16 and >= q2a_row_size(ggml_type, n_cols) (a Q6_K row of 210 bytes per 256
- * columns is padded up to the next multiple of 16 unless n_cols % 2048 == 0), src->embed_table NULL. */
+ * columns is padded up to the next multiple of 16 unless n_cols % 2048 == 0; likewise Q2_K's 84 and Q3_K's 110: n_cols % 1024
+ * and % 2048), src->embed_table NULL. */
 typedef struct {
     const void * rows;     /* device, 16-byte aligned: row r at rows + r * row_bytes */
-    int32_t ggml_type;     /* 2 Q4_0, 8 Q8_0, 12 Q4_K, 13 Q5_K, 14 Q6_K */
+    int32_t ggml_type;     /* 2 Q4_0, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K */
     int32_t reserved;      /* 0 */
     int64_t vocab, n_cols, row_bytes;
 } q2a_embed_qtable;
@@ -619,9 +622,9 @@ int q2a_test_embed_gather(const q2a_embeds_src * src, const q2a_feat_dst * dst, 
 /* Test hook: the pool kernel of these calls alone, with the engine's final-LayerNorm weights, on caller rows.
  *   x_dev      packed [M_tot][n_audio_state] f32 (q2a_varlen_rows over key_len, 1 <= key_len[c] <= n_audio_ctx)
  *   embd_dev   [N_tot][n_audio_state] f32 (q2a_packed_out_rows over key_len), or NULL
- *   codes_dev, dy_dev, aext_dev, ld   the operand of `mode` (0 fp16, 1 Q8_K, 2 Q8_0, 4 bf16: the f32 row rounded to
+ *   codes_dev, dy_dev, aext_dev, ld   the operand of `mode` (0 fp16, 1 Q8_K, 5 its raw-16-sum form, 2 Q8_0, 4 bf16: the f32 row rounded to
  *              nearest even, [N_tot][n_audio_state], no dy / aext) for those N_tot rows in q2a_test_operand's layouts,
- *              ld >= N_tot (modes 1, 2); codes_dev NULL: no operand is written
+ *              ld >= N_tot (modes 1, 2, 5); codes_dev NULL: no operand is written
  * The checks of q2a_test_block_varlen; nothing outside rows 0 .. N_tot-1 of any output is written. */
 int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
                           void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream);

@@ -71,13 +71,19 @@ inline void mat_dims(const dims & d, int which, int & N, int & K) {
 }
 // the activation block of a weight type (its vec_dot_type's: Q8_K for the k-quants, Q8_0 for Q8_0 / Q4_0), 0 = fp16
 inline int blk_of(int wtype) {
-    return (wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K || wtype == Q2A_TYPE_Q6_K) ? 256
+    return (wtype == Q2A_TYPE_Q2_K || wtype == Q2A_TYPE_Q3_K || wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K ||
+            wtype == Q2A_TYPE_Q6_K) ? 256
            : (wtype == Q2A_TYPE_Q8_0 || wtype == Q2A_TYPE_Q4_0) ? 32 : 0;
 }
 // the GEMM's block mode: the activation block, but for Q6_K (per-16 integer scales inside the 256-block)
 inline int gblk_of(int wtype) { return wtype == Q2A_TYPE_Q6_K ? Q2A_BLK_Q6K : blk_of(wtype); }
-// Q4_K's device layout (sc*q weights, min operand, block-ratio arrays): Q4_K and Q5_K
-inline bool kq_minmax(int wtype) { return wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K; }
+// Q4_K's device layout (scale-folded integer weights, min operand, block-ratio arrays): Q4_K, Q5_K, Q2_K and Q3_K
+inline bool kq_minmax(int wtype) {
+    return wtype == Q2A_TYPE_Q4_K || wtype == Q2A_TYPE_Q5_K || wtype == Q2A_TYPE_Q2_K || wtype == Q2A_TYPE_Q3_K;
+}
+// the Q8_K operand's min part is the sixteen raw 16-sums (against WEXT = the sixteen 4-bit mins) instead of the eight
+// 32-sums as (hi, lo) pairs: Q2_K, whose sub-blocks are 16 wide
+inline bool kq_sum16(int wtype) { return wtype == Q2A_TYPE_Q2_K; }
 
 // the device layout of a model: every offset of `h` (false: too many layers)
 bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act);

@@ -139,7 +139,7 @@ inline int q6k_code(const q2a_block_q6_K * x, int k) {
 // Expand rows [r0, r1) of a ggml weight matrix into the blob arrays (rows offset by dst_row0).
 // F16: copied. Q4_K: W' = sc_j * q (exact small integers), DX = d, DMIN = dmin, WEXT = (64 m_j, m_j). Q5_K: the same
 // with its 5-bit codes (sc_j * q <= 1953, still an exact fp16 integer). Q6_K: W' = q - 32, DX = d, SC = sc_j.
-// Q8_0: W' = q, DX = d. Q4_0: W' = q - 8, DX = d.
+// Q8_0: W' = q, DX = d. Q4_0: W' = q - 8, DX = d. Q2_K / Q3_K: Q4_K's arrays with 16-wide sub-blocks (below).
 // one ggml row -> f32 values: F32 / F16 as stored, the block formats as ggml's dequantize_row_* computes them
 // (q2a_dequantize_row, q2a_format.cpp)
 void dequant_row(const uint8_t * row, int wtype, int K, float * y) {
@@ -211,6 +211,36 @@ void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1
                         const int v = q5 ? q5k_code(x5, j, l) : (j & 1) ? (q[l] >> 4) : (q[l] & 0xF);
                         wr[b * 256 + 32 * j + l] = q2a_fp32_to_fp16(d != 0.0f ? (float) (sc * v) : 0.0f);
                     }
+                }
+            }
+        } else if (wtype == Q2A_TYPE_Q2_K || wtype == Q2A_TYPE_Q3_K) {
+            // the Q4_K layout with 16-wide sub-blocks. Q2_K: W' = (sc_j & 15) * q (0 .. 45), WEXT = the sixteen mins
+            // sc_j >> 4 against the operand's sixteen raw 16-sums. Q3_K: W' = (sc_j - 32) * (q - 4) (-124 .. 128), no min
+            // term: DMIN, GAMMA and WEXT are zeros (d may be negative; nothing below depends on its sign)
+            const bool q3 = wtype == Q2A_TYPE_Q3_K;
+            const int nb = K / 256;
+            float * dx = (float *) (blob + a[A_DX]);
+            float * dm = (float *) (blob + a[A_DMIN]);
+            float * be = (float *) (blob + a[A_BETA]);
+            float * ga = (float *) (blob + a[A_GAMMA]);
+            uint16_t * we = (uint16_t *) (blob + a[A_WEXT]);
+            float dprev = 1.0f;
+            for (int b = 0; b < nb; ++b) {
+                const q2a_block_q2_K * x2 = (const q2a_block_q2_K *) row + b;
+                const q2a_block_q3_K * x3 = (const q2a_block_q3_K *) row + b;
+                const float d = q2a_fp16_to_fp32(q3 ? x3->d : x2->d), dmin = q3 ? 0.0f : q2a_fp16_to_fp32(x2->dmin);
+                const float deff = d != 0.0f ? d : 1.0f;   // d = 0: dx = 1 with zero weights, as Q4_K
+                const size_t bi = (size_t) b * Ntot + n;
+                dx[bi] = deff;
+                dm[bi] = dmin;
+                be[bi] = dprev / deff;
+                ga[bi] = q3 ? 0.0f : -(dmin / deff);
+                dprev = deff;
+                for (int j = 0; j < 16; ++j) we[bi * 16 + j] = q2a_fp32_to_fp16(q3 ? 0.0f : (float) (x2->scales[j] >> 4));
+                for (int k = 0; k < 256; ++k) {
+                    const int v = q3 ? (q2a_q3k_scale(x3, k / 16) - 32) * (q2a_q3k_code(x3, k) - 4)
+                                     : (x2->scales[k / 16] & 0xF) * q2a_q2k_code(x2, k);
+                    wr[b * 256 + k] = q2a_fp32_to_fp16(d != 0.0f ? (float) v : 0.0f);
                 }
             }
         } else if (wtype == Q2A_TYPE_Q6_K) {
@@ -489,6 +519,16 @@ __device__ __forceinline__ int q6k_code_d(const q2a_block_q6_K * x, int k) {   /
     return ((r & 2) ? (n >> 4) : (n & 0xF)) | (((x->qh[32 * h + l] >> (2 * r)) & 3) << 4);
 }
 
+__device__ __forceinline__ int q2k_code_d(const q2a_block_q2_K * x, int k) {   // as q2a_q2k_code
+    return (x->qs[32 * (k / 128) + k % 32] >> (2 * ((k % 128) / 32))) & 3;
+}
+__device__ __forceinline__ int q3k_code_d(const q2a_block_q3_K * x, int k) {   // as q2a_q3k_code
+    return ((x->qs[32 * (k / 128) + k % 32] >> (2 * ((k % 128) / 32))) & 3) | (((x->hmask[k % 32] >> (k / 32)) & 1) << 2);
+}
+__device__ __forceinline__ int q3k_scale_d(const q2a_block_q3_K * x, int j) {   // as q2a_q3k_scale
+    return (j < 8 ? x->scales[j] & 0xF : x->scales[j - 8] >> 4) | (((x->scales[8 + j % 4] >> (2 * (j / 4))) & 3) << 4);
+}
+
 struct expand_args {
     const uint8_t * raw;    // ggml rows [nrows][row_size]
     uint8_t * blob;         // device layout
@@ -501,7 +541,8 @@ struct expand_args {
 __global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
 #pragma clang fp contract(off)
     const int n = blockIdx.x, t = threadIdx.x, k = blockIdx.y * 256 + t;
-    const size_t rs = p.wtype == Q2A_TYPE_Q4_K ? (size_t) p.K / 256 * 144 : p.wtype == Q2A_TYPE_Q5_K ? (size_t) p.K / 256 * 176
+    const size_t rs = p.wtype == Q2A_TYPE_Q2_K ? (size_t) p.K / 256 * 84 : p.wtype == Q2A_TYPE_Q3_K ? (size_t) p.K / 256 * 110
+                    : p.wtype == Q2A_TYPE_Q4_K ? (size_t) p.K / 256 * 144 : p.wtype == Q2A_TYPE_Q5_K ? (size_t) p.K / 256 * 176
                     : p.wtype == Q2A_TYPE_Q6_K ? (size_t) p.K / 256 * 210 : p.wtype == Q2A_TYPE_Q8_0 ? (size_t) p.K / 32 * 34
                     : p.wtype == Q2A_TYPE_Q4_0 ? (size_t) p.K / 32 * 18 : p.wtype == Q2A_TYPE_F16 ? (size_t) p.K * 2 : (size_t) p.K * 4;
     const uint8_t * row = p.raw + (size_t) n * rs;
@@ -540,6 +581,36 @@ __global__ __launch_bounds__(256) void k_expand_rows(const expand_args p) {
                 scale_min_k4_d(t / 2, x->scales, sj, mj);
                 ((uint16_t *) (p.blob + p.a[A_WEXT]))[bi * 16 + t] = f2h((t & 1) ? (float) mj : 64.0f * (float) mj);
             }
+            return;
+        }
+    } else if (p.wtype == Q2A_TYPE_Q2_K || p.wtype == Q2A_TYPE_Q3_K) {
+        const bool q3 = p.wtype == Q2A_TYPE_Q3_K;
+        const int b = k / 256, kk = k % 256;
+        const q2a_block_q2_K * x2 = (const q2a_block_q2_K *) row + b;
+        const q2a_block_q3_K * x3 = (const q2a_block_q3_K *) row + b;
+        const float d = h2f(q3 ? x3->d : x2->d), dmin = q3 ? 0.0f : h2f(x2->dmin);
+        const int sc = q3 ? q3k_scale_d(x3, kk / 16) - 32 : x2->scales[kk / 16] & 0xF;
+        const int q = q3 ? q3k_code_d(x3, kk) - 4 : q2k_code_d(x2, kk);
+        if (p.act) {   // dequantize_row_q3_K: (d * (sc - 32)) * (q - 4); _q2_K: d * (sc & 15) * q - dmin * (sc >> 4)
+            const float dl = d * (float) sc;
+            val = dl * (float) q;
+            if (!q3) val = val - dmin * (float) (x2->scales[kk / 16] >> 4);
+        } else {
+            W[(size_t) n * p.K + k] = d != 0.0f ? f2h((float) (sc * q)) : (uint16_t) 0;
+            const size_t bi = (size_t) b * p.Ntot + n;
+            const float deff = d != 0.0f ? d : 1.0f;
+            if (t == 0) {
+                float dprev = 1.0f;
+                if (b > 0) {
+                    const float dp = q3 ? h2f((x3 - 1)->d) : h2f((x2 - 1)->d);
+                    dprev = dp != 0.0f ? dp : 1.0f;
+                }
+                ((float *) (p.blob + p.a[A_DX]))[bi] = deff;
+                ((float *) (p.blob + p.a[A_DMIN]))[bi] = dmin;
+                ((float *) (p.blob + p.a[A_BETA]))[bi] = dprev / deff;
+                ((float *) (p.blob + p.a[A_GAMMA]))[bi] = q3 ? 0.0f : -(dmin / deff);
+            }
+            if (t < 16) ((uint16_t *) (p.blob + p.a[A_WEXT]))[bi * 16 + t] = q3 ? (uint16_t) 0 : f2h((float) (x2->scales[t] >> 4));
             return;
         }
     } else if (p.wtype == Q2A_TYPE_Q6_K) {

@@ -5,7 +5,7 @@
 //                               launches; no workgroup waits for another one's progress.
 //   k_embed_gather              row t of the destination := row input_ids[t] of the table, a byte copy in 16-byte
 //                               pieces; audio positions are left to the GEMM's epilogue.
-//   k_qrow_gather               the same from a table of ggml blocks (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K): the raw row through
+//   k_qrow_gather               the same from a table of ggml blocks (Q4_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K): the raw row through
 //                               LDS, decoded there to ggml's dequantize_row_* values, stored as f32 / fp16 / bf16.
 #include <hip/hip_runtime.h>
 
@@ -134,17 +134,26 @@ __global__ __launch_bounds__(256) void k_embed_gather(const IdT * ids, int n, in
 //   1. the raw blocks of the pass, global -> registers -> the wave's LDS strip in 16-byte pieces, every load issued
 //      before the first use (clamped index, no load under a branch);
 //   2. the scale table of the pass, one entry per scale group, built once from the block headers in LDS: Q4_K / Q5_K
-//      (d * sc, dmin * m) per 32 columns out of the 6-bit packing, Q6_K d * sc per 16 columns, Q8_0 / Q4_0 d per block.
+//      (d * sc, dmin * m) per 32 columns out of the 6-bit packing, Q6_K d * sc per 16 columns, Q8_0 / Q4_0 d per block,
+//      Q2_K (d * (sc & 15), dmin * (sc >> 4)) and Q3_K d * (sc - 32) per 16 columns.
 //      All of these products are exact in f32;
 //   3. the decode: lane l of step k owns the 16 / ES consecutive columns (64 k + l) * 16 / ES .. of the pass — one
 //      16-byte store per lane, 1024 contiguous bytes per wave store. Consecutive columns of one scale group are
 //      consecutive code bytes under one nibble / bit-pair selector in every format, so a lane reads 4 code bytes per 4
 //      columns (plus 4 high-bit bytes for Q5_K / Q6_K) and one table entry, and the two halves of a code byte are taken
 //      by different lanes (32 columns apart in Q4_K / Q5_K, 64 in Q6_K, 16 in Q4_0) that read the same LDS word.
+//      Q2_K / Q3_K: a block's 84 / 110 bytes are never split by value: a lane's four columns are four consecutive qs
+//      bytes under one 2-bit selector (the four selectors of a byte are 32 columns apart, taken by other lanes), for
+//      Q3_K plus the four hmask bytes of the same columns under one bit selector. Q2_K blocks lie on dword boundaries
+//      (84 = 21 dwords), every read a whole aligned dword; Q3_K blocks of odd index start 2 bytes past one (110 = 27.5
+//      dwords), so a lane reads the two aligned dwords around its four bytes and funnels them (v_alignbyte), and only
+//      the table build, once per 16 columns, reads the 12 scale bytes and d as halfwords.
 // The LDS strip is the wave's own: no workgroup barrier, the waves of a workgroup do not wait for each other.
 constexpr int QSEG = 4096;
 
 template <int TYPE> struct qfmt;   // BB bytes per block of BC columns; a table entry of TW floats per TC columns
+template <> struct qfmt<Q2A_TYPE_Q2_K> { static constexpr int BB = 84, BC = 256, TC = 16, TW = 2; };
+template <> struct qfmt<Q2A_TYPE_Q3_K> { static constexpr int BB = 110, BC = 256, TC = 16, TW = 1; };
 template <> struct qfmt<Q2A_TYPE_Q4_K> { static constexpr int BB = 144, BC = 256, TC = 32, TW = 2; };
 template <> struct qfmt<Q2A_TYPE_Q5_K> { static constexpr int BB = 176, BC = 256, TC = 32, TW = 2; };
 template <> struct qfmt<Q2A_TYPE_Q6_K> { static constexpr int BB = 210, BC = 256, TC = 16, TW = 1; };
@@ -166,6 +175,14 @@ __device__ __forceinline__ uint32_t lds2x2(const uint8_t * p) {
     return (uint32_t) q[0] | ((uint32_t) q[1] << 16);
 }
 
+// four consecutive bytes at a 2-byte aligned LDS address as two aligned dword reads and a funnel shift (the dword behind
+// must be readable: true of every qs / hmask position of a Q3_K block, whose last 14 bytes are scales and d)
+__device__ __forceinline__ uint32_t lds4_funnel(const uint8_t * p) {
+    const uint32_t a = (uint32_t) (uintptr_t) p & 3u;
+    const uint32_t * q = (const uint32_t *) (p - a);
+    return __builtin_amdgcn_alignbyte(q[1], q[0], a);
+}
+
 // the scale table of `cols` columns of blocks at L
 template <int TYPE>
 __device__ __forceinline__ void q_build_tab(const uint8_t * L, float * tab, int cols, int lane) {
@@ -179,6 +196,22 @@ __device__ __forceinline__ void q_build_tab(const uint8_t * L, float * tab, int 
             const uint32_t sc = j < 4 ? (s0 & 63) : ((s2 & 0xF) | ((s0 >> 6) << 4));
             const uint32_t m = j < 4 ? (s1 & 63) : ((s2 >> 4) | ((s1 >> 6) << 4));
             ((float2 *) tab)[e] = float2{h2f(dd & 0xFFFF) * (float) sc, h2f(dd >> 16) * (float) m};
+        } else if constexpr (TYPE == Q2A_TYPE_Q2_K) {
+            // header words: scales[16] = words 0..3, {d | dmin << 16} = word 20; both products exact (11 x 4 bits)
+            const int j = e & 15;
+            const uint32_t * hw = (const uint32_t *) (L + (e >> 4) * F::BB);
+            const uint32_t sc = (hw[j >> 2] >> (8 * (j & 3))) & 0xFF, dd = hw[20];
+            ((float2 *) tab)[e] = float2{h2f(dd & 0xFFFF) * (float) (sc & 0xF), h2f(dd >> 16) * (float) (sc >> 4)};
+        } else if constexpr (TYPE == Q2A_TYPE_Q3_K) {
+            // 6-bit scale j: low four bits in a nibble of scales[j % 8], high two in scales[8 + j % 4] (dequantize_row_q3_K's
+            // aux words); the block is 2-byte aligned, its scale bytes read as halfwords
+            const int j = e & 15;
+            const uint8_t * blk = L + (e >> 4) * F::BB;
+            const uint16_t * sh = (const uint16_t *) (blk + 96);
+            auto byte = [&](int i) { return (uint32_t) (sh[i >> 1] >> (8 * (i & 1))) & 0xFFu; };
+            const uint32_t lo4 = j < 8 ? (byte(j) & 0xF) : (byte(j - 8) >> 4);
+            const uint32_t hi2 = (byte(8 + (j & 3)) >> (2 * (j >> 2))) & 3;
+            tab[e] = h2f(*(const uint16_t *) (blk + 108)) * (float) ((int) (lo4 | (hi2 << 4)) - 32);
         } else if constexpr (TYPE == Q2A_TYPE_Q6_K) {
             const uint8_t * blk = L + (e >> 4) * F::BB;
             tab[e] = h2f(*(const uint16_t *) (blk + 208)) * (float) ((const int8_t *) blk)[192 + (e & 15)];
@@ -202,6 +235,29 @@ __device__ __forceinline__ void q_decode4(const uint8_t * L, const float * tab, 
         if constexpr (TYPE == Q2A_TYPE_Q5_K) wq |= ((lds4(blk + 16 + l) >> j) & 0x01010101u) << 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) y[i] = __builtin_fmaf(dm.x, (float) ((wq >> (8 * i)) & 0xFF), -dm.y);
+    } else if constexpr (TYPE == Q2A_TYPE_Q2_K) {
+        // column k of a block: bit pair (k % 128) / 32 of qs[32 (k / 128) + k % 32]; y = dl * q - ml, ggml's multiply then
+        // subtract, uncontracted
+#pragma clang fp contract(off)
+        const int b = c >> 8, k = c & 255;
+        const uint8_t * blk = L + b * F::BB;
+        const float2 dm = ((const float2 *) tab)[c >> 4];
+        const uint32_t wq = (lds4(blk + 16 + 32 * (k >> 7) + (k & 31)) >> (2 * ((k >> 5) & 3))) & 0x03030303u;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float t = dm.x * (float) ((wq >> (8 * i)) & 0xFF);
+            y[i] = t - dm.y;
+        }
+    } else if constexpr (TYPE == Q2A_TYPE_Q3_K) {
+        // the same pair from qs (block byte 32 on), the third bit = bit k / 32 of hmask[k % 32]; (d * (sc - 32)) * (q - 4)
+        const int b = c >> 8, k = c & 255;
+        const uint8_t * blk = L + b * F::BB;
+        const float dl = tab[c >> 4];
+        const uint32_t lo = (lds4_funnel(blk + 32 + 32 * (k >> 7) + (k & 31)) >> (2 * ((k >> 5) & 3))) & 0x03030303u;
+        const uint32_t hi = (lds4_funnel(blk + (k & 31)) >> (k >> 5)) & 0x01010101u;
+        const uint32_t wq = lo | (hi << 2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[i] = dl * (float) ((int) ((wq >> (8 * i)) & 0xFF) - 4);
     } else if constexpr (TYPE == Q2A_TYPE_Q6_K) {
         // run r of half h: nibble r / 2 of ql[64 h + 32 (r & 1) + l], bits 2 r .. 2 r + 1 of qh[32 h + l]; (d * sc) * (q - 32)
         const int b = c >> 8, h = (c >> 7) & 1, r = (c >> 5) & 3, l = c & 31;
@@ -355,7 +411,9 @@ hipError_t q2a_launch_embed_gather(const q2a_embed_gather_args & a, hipStream_t 
 
 hipError_t q2a_launch_embed_gather_q(const q2a_embed_gather_q_args & a, hipStream_t s) {
     const int t = a.ggml_type;
-    if (t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K && t != Q2A_TYPE_Q6_K) return hipErrorInvalidValue;
+    if (t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q2_K && t != Q2A_TYPE_Q3_K && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K &&
+        t != Q2A_TYPE_Q6_K)
+        return hipErrorInvalidValue;
     if (a.out_dt != Q2A_DT_F32 && a.out_dt != Q2A_DT_F16 && a.out_dt != Q2A_DT_BF16) return hipErrorInvalidValue;
     const int es = a.out_dt == Q2A_DT_F32 ? 4 : 2;
     if (!a.ids || (a.width != 4 && a.width != 8) || a.n_tokens < 1 || a.n_tokens > Q2A_IDS_MAX_TOKENS || !a.rows || a.vocab < 1 || !a.out ||
@@ -366,6 +424,8 @@ hipError_t q2a_launch_embed_gather_q(const q2a_embed_gather_q_args & a, hipStrea
     switch (t) {
         case Q2A_TYPE_Q4_0: launch_gather_q_dt<Q2A_TYPE_Q4_0>(a, s); break;
         case Q2A_TYPE_Q8_0: launch_gather_q_dt<Q2A_TYPE_Q8_0>(a, s); break;
+        case Q2A_TYPE_Q2_K: launch_gather_q_dt<Q2A_TYPE_Q2_K>(a, s); break;
+        case Q2A_TYPE_Q3_K: launch_gather_q_dt<Q2A_TYPE_Q3_K>(a, s); break;
         case Q2A_TYPE_Q4_K: launch_gather_q_dt<Q2A_TYPE_Q4_K>(a, s); break;
         case Q2A_TYPE_Q5_K: launch_gather_q_dt<Q2A_TYPE_Q5_K>(a, s); break;
         default: launch_gather_q_dt<Q2A_TYPE_Q6_K>(a, s); break;

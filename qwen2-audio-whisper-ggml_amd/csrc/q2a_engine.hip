@@ -416,7 +416,11 @@ hipEvent_t prof_event(q2a_engine * e) {
         if (on_) { (void) hipEventRecord(r_.b, s); (e)->pending.push_back(r_); }      \
     } while (0)
 
-int ln_mode(const q2a_engine * e) { return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 0 ? 0 : e->blk == 256 ? 1 : 2; }
+// (5: Q8_K with the raw 16-sums for Q2_K weights, q2a_ln_args; q8k_mode: either Q8_K form)
+int ln_mode(const q2a_engine * e) {
+    return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 0 ? 0 : e->blk != 256 ? 2 : kq_sum16(e->wtype) ? 5 : 1;
+}
+bool q8k_mode(int mode) { return mode == 1 || mode == 5; }
 
 #define LAUNCH(x)                                                                     \
     do {                                                                              \
@@ -489,10 +493,10 @@ q2a_gemm_args resid_gemm(const q2a_engine * e, int l, int which, int M, float * 
 int fc1_epi(const q2a_engine * e, int M, int path) {
     const int mode = ln_mode(e);
     if (mode == 0 || mode == 3 || mode == 4) return Q2A_EPI_GELU_H;
-    if (mode == 1 && path == 2 && q2a_gemm_wide_tiles(M, e->d.F, e->gblk) &&
+    if (q8k_mode(mode) && path == 2 && q2a_gemm_wide_tiles(M, e->d.F, e->gblk) &&
         q2a_gemm_pipe8(gemm_base(e, 0, 2, e->actD, M), e->gblk))   // (never Q6_K: its mode has no 8-phase kernel)
         return Q2A_EPI_GELU_Q8K;
-    return mode == 1 && path != 1 ? Q2A_EPI_PRE_H : Q2A_EPI_GELU_H;
+    return q8k_mode(mode) && path != 1 ? Q2A_EPI_PRE_H : Q2A_EPI_GELU_H;
 }
 
 q2a_gemm_args fc1_gemm(const q2a_engine * e, int l, int M, int epi) {
@@ -508,6 +512,7 @@ q2a_gemm_args fc1_gemm(const q2a_engine * e, int l, int M, int epi) {
     } else if (epi == Q2A_EPI_GELU_Q8K) {
         // fused fc1 + GELU + Q8_K quantization of the fc2 input (one Q8_K block per 256-column tile)
         a.outH = e->actF; a.ldo = d.F; a.qdy = e->dyF; a.qaext = e->aextF;
+        a.q_sum16 = mode == 5;
     } else {
         // the fp16 pre-activation (Q2A_EPI_PRE_H) or the GELU output, exactly fp16-valued (LUT), for the quantizer
         a.outH = (q2a_half *) e->hF; a.ldo = d.F; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
@@ -549,7 +554,7 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
         if (mode == 3) {
             const int64_t n = (int64_t) M * d.D;
             PLAUNCH(e, s, Q2A_PROF_QUANT, launch_split3(e->attF, e->actD, d.D, n, s));
-        } else if (mode == 1 || mode == 2) {
+        } else if (q8k_mode(mode) || mode == 2) {
             q2a_quant_args qa{e->attF, nullptr, M, d.D, mode, e->actD, e->dyD, e->aextD, e->dy_ld};
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_act(qa, s));
         }
@@ -571,8 +576,8 @@ int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
             // fc1 wrote its fp16 pre-activation (plain stores); the Q8_K quantizer of the fc2 input applies the
             // GELU table from LDS on the way (same codes as the GELU epilogue + quantizer below)
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_gelu_quant_q8k(a.outH, M, d.F, e->g<const uint16_t *>(G_GELU), e->actF,
-                                                                   e->dyF, e->aextF, e->dy_ld, s));
-        } else if (epi == Q2A_EPI_GELU_H && (mode == 1 || mode == 2)) {
+                                                                   e->dyF, e->aextF, e->dy_ld, s, mode == 5));
+        } else if (epi == Q2A_EPI_GELU_H && (q8k_mode(mode) || mode == 2)) {
             // GELU output is exactly fp16-valued (LUT): keep it as fp16, then quantize for fc2
             q2a_quant_args qa{nullptr, a.outH, M, d.F, mode, e->actF, e->dyF, e->aextF, e->dy_ld};
             PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_act(qa, s));
@@ -922,8 +927,10 @@ struct proj_operand {
     int32_t * chunk_count;
     int32_t * report;
 };
-// the conversion the weight type asks for: 0 fp16, 1 Q8_K, 2 Q8_0, and 4 bf16 for a bf16 projector (q2a_ln_args' modes)
-int proj_mode(const q2a_projector * p) { return p->act == Q2A_ACT_BF16 ? 4 : p->blk == 0 ? 0 : p->blk == 256 ? 1 : 2; }
+// the conversion the weight type asks for: 0 fp16, 1 Q8_K (5: its raw-16-sum form, Q2_K), 2 Q8_0, and 4 bf16 for a bf16 projector (q2a_ln_args' modes)
+int proj_mode(const q2a_projector * p) {
+    return p->act == Q2A_ACT_BF16 ? 4 : p->blk == 0 ? 0 : p->blk != 256 ? 2 : kq_sum16(p->wtype) ? 5 : 1;
+}
 
 // grows the workspace (after everything queued on s: calls on one handle are ordered on one stream) and cuts it up
 int proj_workspace(q2a_projector * p, int64_t rows, hipStream_t s, proj_operand & o, bool with_map = false, int64_t ids_tokens = 0) {
@@ -1039,8 +1046,8 @@ int embed_qtable_check(const q2a_embed_qtable * qt, const q2a_embeds_src & src, 
     if (!qt) { set_err("inputs_embeds: the quantized table is required"); return Q2A_ERR_ARG; }
     if (src.embed_table) { set_err("inputs_embeds: a quantized table goes with embed_table NULL"); return Q2A_ERR_ARG; }
     const int t = qt->ggml_type;
-    if ((t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K && t != Q2A_TYPE_Q6_K) || qt->reserved != 0) {
-        set_err("inputs_embeds: quantized table of ggml type %d (Q4_0, Q8_0, Q4_K, Q5_K, Q6_K), reserved %d", t, qt->reserved);
+    if ((t != Q2A_TYPE_Q4_0 && t != Q2A_TYPE_Q8_0 && t != Q2A_TYPE_Q2_K && t != Q2A_TYPE_Q3_K && t != Q2A_TYPE_Q4_K && t != Q2A_TYPE_Q5_K && t != Q2A_TYPE_Q6_K) || qt->reserved != 0) {
+        set_err("inputs_embeds: quantized table of ggml type %d (Q4_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K), reserved %d", t, qt->reserved);
         return Q2A_ERR_ARG;
     }
     if (qt->n_cols != d_out || qt->n_cols % 256 != 0 || qt->vocab < 1) {
@@ -2071,10 +2078,10 @@ int q2a_test_pool_ln(q2a_engine * e, const float * x_dev, int n_clips, float * o
 // the audio-feature tail's pool kernel alone, straight from the caller's packed rows into the caller's buffers
 int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_clips, const int32_t * key_len, float * embd_dev,
                           void * codes_dev, float * dy_dev, void * aext_dev, int ld, void * stream) {
-    if (!e || !x_dev || n_clips <= 0 || !key_len || mode < 0 || mode == 3 || mode > 4) return Q2A_ERR_ARG;
+    if (!e || !x_dev || n_clips <= 0 || !key_len || mode < 0 || mode == 3 || mode > 5) return Q2A_ERR_ARG;
     if (!codes_dev) mode = -1;   // no operand: the f32 rows alone
     if (mode < 0 && !embd_dev) return Q2A_ERR_ARG;
-    if ((mode == 1 && (!dy_dev || !aext_dev || e->d.D % 256)) || (mode == 2 && (!dy_dev || e->d.D % 32))) return Q2A_ERR_ARG;
+    if ((q8k_mode(mode) && (!dy_dev || !aext_dev || e->d.D % 256)) || (mode == 2 && (!dy_dev || e->d.D % 32))) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
@@ -2082,7 +2089,7 @@ int q2a_test_pool_operand(q2a_engine * e, int mode, const float * x_dev, int n_c
     block_rows rows;
     if ((rc = hook_rows(e, ENC_PACKED, key_len, n_clips, s, rows, true))) return rc;
     if (rows.N_out == 0) return Q2A_OK;
-    if ((mode == 1 || mode == 2) && ld < rows.N_out) { set_err("ld %d below the %d output rows", ld, rows.N_out); return Q2A_ERR_ARG; }
+    if ((q8k_mode(mode) || mode == 2) && ld < rows.N_out) { set_err("ld %d below the %d output rows", ld, rows.N_out); return Q2A_ERR_ARG; }
     const meta_rows dev(e->meta, n_clips);
     q2a_pool_pack_args pa{x_dev, n_clips, e->d.D, rows.N_out, e->g<const float *>(G_LNP_W), e->g<const float *>(G_LNP_B),
                           dev.row_start, dev.out_start, embd_dev, mode, (q2a_half *) codes_dev, dy_dev, (q2a_half *) aext_dev, ld};
@@ -2101,14 +2108,14 @@ int q2a_test_fc1_path(q2a_engine * e, int path) {
 int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x, int M, int K, const float * g, const float * b,
                      void * out, float * dy, void * aext, int ld, void * stream) {
     if (!e || !x || !out || M <= 0 || K <= 0 || ld < M) return Q2A_ERR_ARG;
-    const bool quant = mode == 1 || mode == 2;
-    if (quant && (!dy || (mode == 1 && !aext))) return Q2A_ERR_ARG;
-    if (mode == 1 && K % 256) return Q2A_ERR_ARG;
+    const bool quant = q8k_mode(mode) || mode == 2;
+    if (quant && (!dy || (q8k_mode(mode) && !aext))) return Q2A_ERR_ARG;
+    if (q8k_mode(mode) && K % 256) return Q2A_ERR_ARG;
     if (mode == 2 && K % 32) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     if (producer == Q2A_OPERAND_LN) {
-        if (mode < 0 || mode > 4 || !g || !b || K % 4 || K > 2048) return Q2A_ERR_ARG;
+        if (mode < 0 || mode > 5 || !g || !b || K % 4 || K > 2048) return Q2A_ERR_ARG;
         q2a_ln_args ln{(const float *) x, M, K, g, b, mode, (q2a_half *) out, dy, (q2a_half *) aext, ld};
         LAUNCH(q2a_launch_layernorm(ln, s));
     } else if (producer == Q2A_OPERAND_QUANT_F32 || producer == Q2A_OPERAND_QUANT_H16) {
@@ -2118,9 +2125,9 @@ int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x, int
                           (q2a_half *) out, dy, (q2a_half *) aext, ld};
         LAUNCH(q2a_launch_quant_act(qa, s));
     } else if (producer == Q2A_OPERAND_GELU_Q8K) {
-        if (mode != 1 || (int64_t) M * K >= ((int64_t) 1 << 31)) return Q2A_ERR_ARG;
+        if (!q8k_mode(mode) || (int64_t) M * K >= ((int64_t) 1 << 31)) return Q2A_ERR_ARG;
         LAUNCH(q2a_launch_gelu_quant_q8k((const q2a_half *) x, M, K, e->g<const uint16_t *>(G_GELU), (q2a_half *) out, dy,
-                                         (q2a_half *) aext, ld, s));
+                                         (q2a_half *) aext, ld, s, mode == 5));
     } else {
         return Q2A_ERR_ARG;
     }
@@ -2248,7 +2255,7 @@ q2a_projector * q2a_projector_open_ex(const char * path, int device, int act) {
     std::vector<uint8_t> packed;
     uint64_t off[A_COUNT];
     if (q2a_pack_linear(mf->data + wt->offset, wt->type, N, K, packed, off, act) != Q2A_OK)
-        return fail(Q2A_ERR_UNSUPPORTED, "weight type not supported (F16, Q4_K, Q5_K, Q6_K, Q8_0, Q4_0)");
+        return fail(Q2A_ERR_UNSUPPORTED, "weight type not supported (F16, Q2_K, Q3_K, Q4_K, Q5_K, Q6_K, Q8_0, Q4_0)");
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) { (void) hipGetLastError(); return fail(Q2A_ERR_HIP, "no such HIP device"); }
     q2a_projector * p = new q2a_projector();

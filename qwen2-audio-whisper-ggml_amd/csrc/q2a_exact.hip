@@ -261,7 +261,8 @@ __global__ __launch_bounds__(256) void k_mel_ingest(const q2a_mel_ingest_args p)
 // LayerNorm (ggml_compute_forward_norm_f32 ggml.c:11941-11990: double sums, eps 1e-5) + affine (MUL, ADD),
 // fused with the conversion ggml applies to the next MUL_MAT's src1 (ggml.c:12462-12475):
 //   mode 0 fp16 RNE;  mode 1 Q8_K (quantize_row_q8_K_ref ggml-quants.c:3785-3822);
-//   mode 2 Q8_0 (x86 quantize_row_q8_0 ggml-quants.c:943-1000: d = amax/127, id = 127/amax, round-half-even).
+//   mode 2 Q8_0 (x86 quantize_row_q8_0 ggml-quants.c:943-1000: d = amax/127, id = 127/amax, round-half-even);
+//   mode 5 Q8_K with the min operand as the sixteen raw 16-sums (q2a_quant.h; Q2_K weights): mode 1's kernels, S16.
 // One wave per row; lane l owns float4 chunks l, l+64, ... so a 256-block is one float4 per lane.
 // ------------------------------------------------------------------------------------------------
 // (the f64 steps stay on the LDS pipe: the same butterfly on DPP / permlane swaps, bit-identical, measured slower —
@@ -274,13 +275,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // The NBQ Q8_K blocks of this wave's row (one of the 8 rows row0 .. row0 + 7 of a 512-thread workgroup, y[u] = the lane's
 // float4 of block u) quantized together: codes to `codes` (+ 256 u), the rows' d and bsum operands staged in LDS and
 // stored by the workgroup as whole sectors. Every wave of the workgroup calls it (a barrier); rows >= M store neither.
-template <int NBQ>
+template <int NBQ, bool S16 = false>
 __device__ __forceinline__ void quant_q8k_rows8(const float4 (&y)[NBQ], int lane, q2a_half * codes, int row0, int M,
                                                 float * dy, q2a_half * aext, int ld) {
     __shared__ float sd[8][NBQ];
     __shared__ __attribute__((aligned(16))) q2a_half sa[8][NBQ][16];
     const int r = threadIdx.x >> 6;
-    quant_q8k_blocks<NBQ>(y, lane, codes, 256, &sd[r][0], 1, &sa[r][0][0], 16);
+    quant_q8k_blocks<NBQ, S16>(y, lane, codes, 256, &sd[r][0], 1, &sa[r][0][0], 16);
     __syncthreads();
     const int t = threadIdx.x;
     if (t < NBQ * 8) {     // d: block column u, rows row0 .. row0 + 7 (32 B)
@@ -302,6 +303,7 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
                                              const float * __restrict__ b, q2a_half * outH, float * dy, q2a_half * aext,
                                              int nseg, int ld) {
     const int lane = threadIdx.x & 63;
+    constexpr bool Q8K = MODE == 1 || MODE == 5, S16 = MODE == 5;
     constexpr int RPB = NBQ ? 8 : 4;   // rows per workgroup
     const int row0 = blockIdx.x * RPB;
     const int row_raw = row0 + (threadIdx.x >> 6);
@@ -370,7 +372,7 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
         }
     }
     if constexpr (NBQ > 0 && LN) __syncthreads();   // sgb filled
-    if constexpr (MODE == 1 && NBQ > 0) {
+    if constexpr (Q8K && NBQ > 0) {
         // whole row resident: the NBQ Q8_K blocks of the row quantized with interleaved reductions
         float4 y[NBQ];
 #pragma unroll
@@ -386,7 +388,7 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
             }
         }
         // codes of a clamped duplicate row (past M) are the real last row's: rewriting them changes nothing
-        quant_q8k_rows8<NBQ>(y, lane, outH + (int64_t) row * D + 4 * lane, row0, M, dy, aext, ld);
+        quant_q8k_rows8<NBQ, S16>(y, lane, outH + (int64_t) row * D + 4 * lane, row0, M, dy, aext, ld);
         return;
     }
     if (NBQ && row_raw >= M) return;   // (after the workgroup's barrier)
@@ -418,9 +420,9 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
                 o[D + e] = (_Float16) (yy[e] - (float) h);
                 o[2 * D + e] = h;
             }
-        } else if (MODE == 1) {
+        } else if (Q8K) {
             const int bf = seg * (D / 256) + u;
-            quant_q8k_block(y, lane, o, dy + (int64_t) bf * ld + m, aext + ((int64_t) bf * ld + m) * 16);
+            quant_q8k_block<S16>(y, lane, o, dy + (int64_t) bf * ld + m, aext + ((int64_t) bf * ld + m) * 16);
         } else {
             const int bf = seg * (D / 32) + (4 * c) / 32;
             quant_q80_block(y, lane, o, dy + (int64_t) bf * ld + m);
@@ -445,6 +447,7 @@ __global__ __launch_bounds__(512) void k_rownorm5(
 
 // Q8_K quantizer for fp16 rows (the fc1 GELU output), 16 lanes per 256-block: a wave quantizes four blocks at
 // once with 16-B loads and stores (quant_q8k_row16: the arithmetic of quant_q8k_block, shorter reduction chains)
+template <bool S16>
 __global__ __launch_bounds__(256) void k_quant_q8k_h16(const q2a_half * __restrict__ X, int64_t nblocks, int bpr,
                                                        q2a_half * outH, float * dy, q2a_half * aext, int ld) {
     const int lane = threadIdx.x & 63, sub = lane & 15;
@@ -458,7 +461,7 @@ __global__ __launch_bounds__(256) void k_quant_q8k_h16(const q2a_half * __restri
     float v[16];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { v[e] = (float) h0[e]; v[8 + e] = (float) h1[e]; }
-    quant_q8k_row16(v, sub, outH + blk * 256 + sub * 16, dy + (int64_t) bf * ld + m, aext + ((int64_t) bf * ld + m) * 16);
+    quant_q8k_row16<S16>(v, sub, outH + blk * 256 + sub * 16, dy + (int64_t) bf * ld + m, aext + ((int64_t) bf * ld + m) * 16);
 }
 
 // GELU + Q8_K of the fc1 pre-activation (Q2A_EPI_PRE_H output, fp16). Persistent workgroups of 8 waves stage ggml's
@@ -484,6 +487,7 @@ __global__ __launch_bounds__(256) void k_quant_q8k_h16(const q2a_half * __restri
 constexpr int GQ_THREADS = 512;
 constexpr int GQ_WAVES = GQ_THREADS / 64;
 typedef __attribute__((address_space(3))) void * lds_vptr_t;
+template <bool S16>
 __global__ __launch_bounds__(GQ_THREADS) void k_gelu_quant_q8k_h16(const q2a_half * __restrict__ X, int M, int bpr,
                                                                    const uint16_t * __restrict__ gelu_tab, q2a_half * outH,
                                                                    float * dy, q2a_half * aext, int ld) {
@@ -586,13 +590,10 @@ __global__ __launch_bounds__(GQ_THREADS) void k_gelu_quant_q8k_h16(const q2a_hal
         }
         const int row = r0 + grp;
         float d;
-        int sb;
-        quant_q8k_row16c(v, sub, outH + row * K + bf * 256 + sub * 16, row < M, d, sb);
-        if ((sub & 1) == 0 && row < M) {   // bsum32 of sub-block sub / 2 as (hi, lo): rows r0 .. r0 + 3 = 128 B
-            const int hi = (sb >= 0) ? (sb >> 6) : -((-sb + 63) >> 6);   // floor(s / 64)
-            const int lo = sb - 64 * hi;
-            *(h2_t *) (aext + ((int64_t) bf * ld + row) * 16 + sub) = h2_t{(_Float16) (float) hi, (_Float16) (float) lo};
-        }
+        int sb, sb16;
+        quant_q8k_row16c(v, sub, outH + row * K + bf * 256 + sub * 16, row < M, d, sb, sb16);
+        // bsum32 of sub-block sub / 2 as (hi, lo), or the raw 16-sums: rows r0 .. r0 + 3 = 128 B
+        if (row < M) store_row16_sums(S16, sub, sb, sb16, aext + ((int64_t) bf * ld + row) * 16);
         const int q = cur.q;
         const float dq = __shfl(d, (lane & 3) * 16);         // d of row r0 + (lane & 3)
         if ((lane >> 2) == q) dd = dq;
@@ -718,6 +719,7 @@ __global__ __launch_bounds__(256) void k_pool_ln_varlen(const q2a_pool_varlen_ar
 template <int MODE, int NBQ>
 __device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
     const int lane = threadIdx.x & 63;
+    constexpr bool Q8K = MODE == 1 || MODE == 5, S16 = MODE == 5;
     constexpr int RPB = NBQ ? 8 : 4;
     const int row0 = blockIdx.x * RPB;
     const int n_raw = row0 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -746,9 +748,9 @@ __device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
             if (NBQ || ch < nch) o4[ch] = v[u];
         }
     }
-    if constexpr (MODE == 1 && NBQ > 0) {
+    if constexpr (Q8K && NBQ > 0) {
         // codes of a repeated last row are that row's own: rewriting them changes nothing
-        quant_q8k_rows8<NBQ>(v, lane, p.outH + (int64_t) n * D + 4 * lane, row0, p.N_tot, p.dy, p.aext, p.dy_ld);
+        quant_q8k_rows8<NBQ, S16>(v, lane, p.outH + (int64_t) n * D + 4 * lane, row0, p.N_tot, p.dy, p.aext, p.dy_ld);
     } else if constexpr (MODE >= 0) {
 #pragma unroll
         for (int u = 0; u < MAXC; ++u) {
@@ -761,8 +763,8 @@ __device__ __forceinline__ void pool_pack_rows(const q2a_pool_pack_args & p) {
             } else if (MODE == 4) {   // bf16 operand: the LayerNorm kernels' mode-4 conversion (RNE), one 8-B store
                 typedef __bf16 b4_t __attribute__((ext_vector_type(4)));
                 *(b4_t *) o = b4_t{(__bf16) v[u].x, (__bf16) v[u].y, (__bf16) v[u].z, (__bf16) v[u].w};
-            } else if (MODE == 1) {
-                quant_q8k_block(v[u], lane, o, p.dy + (int64_t) u * p.dy_ld + n, p.aext + ((int64_t) u * p.dy_ld + n) * 16);
+            } else if (Q8K) {
+                quant_q8k_block<S16>(v[u], lane, o, p.dy + (int64_t) u * p.dy_ld + n, p.aext + ((int64_t) u * p.dy_ld + n) * 16);
             } else {
                 quant_q80_block(v[u], lane, o, p.dy + (int64_t) (ch / 8) * p.dy_ld + n);
             }
@@ -787,8 +789,9 @@ __global__ __launch_bounds__(256) Q2A_SCALAR_F32 void k_poolnorm_pack_bf16(const
 }
 
 // rows of D = 1280 (the model width) into a Q8_K operand: 8 rows per 512-thread workgroup
+template <int MODE>
 __global__ __launch_bounds__(512) void k_poolnorm_pack5(const q2a_pool_pack_args p) {
-    pool_pack_rows<1, 5>(p);
+    pool_pack_rows<MODE, 5>(p);
 }
 
 }  // namespace
@@ -826,7 +829,7 @@ hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s) {
 
 hipError_t q2a_launch_layernorm(const q2a_ln_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048) return hipErrorInvalidValue;
-    if (a.mode == 1 && a.D % 256) return hipErrorInvalidValue;
+    if ((a.mode == 1 || a.mode == 5) && a.D % 256) return hipErrorInvalidValue;
     if (a.mode == 2 && a.D % 32) return hipErrorInvalidValue;
     const dim3 grid((a.M + 3) / 4), blk(256), grid8((a.M + 7) / 8), blk8(512);
     const bool d1280 = a.D == 1280;   // the model width: compile-time row length (k_rownorm NBQ = 5)
@@ -842,20 +845,29 @@ hipError_t q2a_launch_layernorm(const q2a_ln_args & a, hipStream_t s) {
     else if (a.mode == 1 && d1280)
         hipLaunchKernelGGL((k_rownorm5<1, true>), grid8, blk8, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
     else if (a.mode == 1) hipLaunchKernelGGL((k_rownorm<1, true>), grid, blk, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
+    else if (a.mode == 5 && d1280)
+        hipLaunchKernelGGL((k_rownorm5<5, true>), grid8, blk8, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
+    else if (a.mode == 5) hipLaunchKernelGGL((k_rownorm<5, true>), grid, blk, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
     else hipLaunchKernelGGL((k_rownorm<2, true>), grid, blk, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
     return hipGetLastError();
 }
 
 hipError_t q2a_launch_gelu_quant_q8k(const q2a_half * XH, int M, int K, const uint16_t * gelu_tab, q2a_half * outH,
-                                     float * dy, q2a_half * aext, int dy_ld, hipStream_t s) {
+                                     float * dy, q2a_half * aext, int dy_ld, hipStream_t s, bool sum16) {
     if (K % 256 != 0 || M <= 0 || (int64_t) M * K >= ((int64_t) 1 << 31)) return hipErrorInvalidValue;
     int dev = 0, ncu = 256;
     (void) hipGetDevice(&dev);
     (void) hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     const int64_t units = (int64_t) ((M + 15) / 16) * (K / 256);
     const unsigned grid = (unsigned) std::min<int64_t>((units + GQ_WAVES - 1) / GQ_WAVES, (int64_t) ncu);   // 144 KiB each
-    hipLaunchKernelGGL(k_gelu_quant_q8k_h16, dim3(grid), dim3(GQ_THREADS), 0, s, XH, M, K / 256, gelu_tab, outH, dy, aext, dy_ld);
+    if (sum16) hipLaunchKernelGGL(k_gelu_quant_q8k_h16<true>, dim3(grid), dim3(GQ_THREADS), 0, s, XH, M, K / 256, gelu_tab, outH, dy, aext, dy_ld);
+    else hipLaunchKernelGGL(k_gelu_quant_q8k_h16<false>, dim3(grid), dim3(GQ_THREADS), 0, s, XH, M, K / 256, gelu_tab, outH, dy, aext, dy_ld);
     return hipGetLastError();
+}
+
+hipError_t q2a_launch_gelu_quant_q8k(const q2a_half * XH, int M, int K, const uint16_t * gelu_tab, q2a_half * outH,
+                                     float * dy, q2a_half * aext, int dy_ld, hipStream_t s) {
+    return q2a_launch_gelu_quant_q8k(XH, M, K, gelu_tab, outH, dy, aext, dy_ld, s, false);
 }
 
 hipError_t q2a_launch_quant_act(const q2a_quant_args & a, hipStream_t s) {
@@ -866,9 +878,20 @@ hipError_t q2a_launch_quant_act(const q2a_quant_args & a, hipStream_t s) {
     const dim3 grid((a.M * nseg + 3) / 4), blk(256);
     // view X as [M*nseg][seg]: contiguous, and the block structure (256 / 32) never straddles a segment
     const float * X = a.XH ? (const float *) a.XH : a.X;
-    if (a.mode == 1 && a.XH) {
+    if (a.mode == 5) {   // Q8_K with raw 16-sums: mode 1's kernels (fp16 rows; f32 rows of the model width; f32 rows)
+        if (a.XH) {
+            const int64_t nb = (int64_t) a.M * (a.K / 256);
+            hipLaunchKernelGGL(k_quant_q8k_h16<true>, dim3((unsigned) ((nb + 15) / 16)), dim3(256), 0, s, a.XH, nb, a.K / 256, a.outH,
+                               a.dy, a.aext, a.dy_ld);
+        } else if (seg == 1280 && nseg == 1) {
+            hipLaunchKernelGGL((k_rownorm5<5, false>), dim3((a.M + 7) / 8), dim3(512), 0, s, X, a.M, seg, nullptr, nullptr,
+                               a.outH, a.dy, a.aext, 1, a.dy_ld);
+        } else {
+            hipLaunchKernelGGL((k_rownorm<5, false>), grid, blk, 0, s, X, a.M * nseg, seg, nullptr, nullptr, a.outH, a.dy, a.aext, nseg, a.dy_ld);
+        }
+    } else if (a.mode == 1 && a.XH) {
         const int64_t nb = (int64_t) a.M * (a.K / 256);
-        hipLaunchKernelGGL(k_quant_q8k_h16, dim3((unsigned) ((nb + 15) / 16)), dim3(256), 0, s, a.XH, nb, a.K / 256, a.outH,
+        hipLaunchKernelGGL(k_quant_q8k_h16<false>, dim3((unsigned) ((nb + 15) / 16)), dim3(256), 0, s, a.XH, nb, a.K / 256, a.outH,
                            a.dy, a.aext, a.dy_ld);
     } else if (a.mode == 1 && a.XH) {
         hipLaunchKernelGGL((k_rownorm<1, false, true>), grid, blk, 0, s, X, a.M * nseg, seg, nullptr, nullptr, a.outH, a.dy, a.aext, nseg, a.dy_ld);
@@ -901,11 +924,13 @@ hipError_t q2a_launch_pool_ln_varlen(const q2a_pool_varlen_args & a, hipStream_t
 
 hipError_t q2a_launch_pool_pack(const q2a_pool_pack_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048 || a.n_clips < 1 || a.N_tot < 1 || !a.X || !a.row_start || !a.out_start) return hipErrorInvalidValue;
-    if (a.mode < -1 || a.mode == 3 || a.mode > 4 || (a.mode < 0 ? !a.embd : !a.outH)) return hipErrorInvalidValue;
-    if (a.mode == 1 && (a.D % 256 || !a.dy || !a.aext || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
+    if (a.mode < -1 || a.mode == 3 || a.mode > 5 || (a.mode < 0 ? !a.embd : !a.outH)) return hipErrorInvalidValue;
+    if ((a.mode == 1 || a.mode == 5) && (a.D % 256 || !a.dy || !a.aext || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
     if (a.mode == 2 && (a.D % 32 || !a.dy || a.dy_ld < a.N_tot)) return hipErrorInvalidValue;
     const dim3 grid((a.N_tot + 3) / 4), blk(256);
-    if (a.mode == 1 && a.D == 1280) hipLaunchKernelGGL(k_poolnorm_pack5, dim3((a.N_tot + 7) / 8), dim3(512), 0, s, a);
+    if (a.mode == 1 && a.D == 1280) hipLaunchKernelGGL(k_poolnorm_pack5<1>, dim3((a.N_tot + 7) / 8), dim3(512), 0, s, a);
+    else if (a.mode == 5 && a.D == 1280) hipLaunchKernelGGL(k_poolnorm_pack5<5>, dim3((a.N_tot + 7) / 8), dim3(512), 0, s, a);
+    else if (a.mode == 5) hipLaunchKernelGGL(k_poolnorm_pack<5>, grid, blk, 0, s, a);
     else if (a.mode == 1) hipLaunchKernelGGL(k_poolnorm_pack<1>, grid, blk, 0, s, a);
     else if (a.mode == 2) hipLaunchKernelGGL(k_poolnorm_pack<2>, grid, blk, 0, s, a);
     else if (a.mode == 0) hipLaunchKernelGGL(k_poolnorm_pack<0>, grid, blk, 0, s, a);

@@ -63,6 +63,8 @@ extern "C" size_t q2a_row_size(int t, int64_t n) {
         case Q2A_TYPE_F16: return (size_t) n * 2;
         case Q2A_TYPE_Q4_0: return (size_t) (n / 32) * sizeof(q2a_block_q4_0);
         case Q2A_TYPE_Q8_0: return (size_t) (n / 32) * sizeof(q2a_block_q8_0);
+        case Q2A_TYPE_Q2_K: return (size_t) (n / 256) * sizeof(q2a_block_q2_K);
+        case Q2A_TYPE_Q3_K: return (size_t) (n / 256) * sizeof(q2a_block_q3_K);
         case Q2A_TYPE_Q4_K: return (size_t) (n / 256) * sizeof(q2a_block_q4_K);
         case Q2A_TYPE_Q5_K: return (size_t) (n / 256) * sizeof(q2a_block_q5_K);
         case Q2A_TYPE_Q6_K: return (size_t) (n / 256) * sizeof(q2a_block_q6_K);
@@ -73,6 +75,8 @@ extern "C" size_t q2a_row_size(int t, int64_t n) {
 
 static_assert(sizeof(q2a_block_q4_0) == 18, "q4_0");
 static_assert(sizeof(q2a_block_q8_0) == 34, "q8_0");
+static_assert(sizeof(q2a_block_q2_K) == 84, "q2_K");
+static_assert(sizeof(q2a_block_q3_K) == 110, "q3_K");
 static_assert(sizeof(q2a_block_q4_K) == 144, "q4_K");
 static_assert(sizeof(q2a_block_q5_K) == 176, "q5_K");
 static_assert(sizeof(q2a_block_q6_K) == 210, "q6_K");
@@ -211,7 +215,8 @@ extern "C" int64_t q2a_audio_token_rows(const void * ids_host, int32_t ids_width
 }
 
 // One ggml row -> f32, ggml's dequantize_row_* float operations in ggml's order (ggml-quants.c: q4_0 :1694, q8_0 :1734,
-// q4_K :2555-2577 with d1 = d * sc, m1 = dmin * m, y = d1 * q - m1; q5_K :2763-2788; q6_K :2977-3006, (d * sc) * q).
+// q4_K :2555-2577 with d1 = d * sc, m1 = dmin * m, y = d1 * q - m1; q5_K :2763-2788; q6_K :2977-3006, (d * sc) * q;
+// q2_K :1979-2009 with dl = d * (sc & 15), ml = dmin * (sc >> 4), y = dl * q - ml; q3_K :2327-2375, (d * (sc - 32)) * (q - 4)).
 // The value contract of the quantized embedding gather (q2a_embeds.hip) and of the bf16-contract weight pack.
 static inline void scale_min_k4(int j, const uint8_t * q, uint8_t * d, uint8_t * m);
 extern "C" int q2a_dequantize_row(int ggml_type, const void * row, float * y, int64_t n_cols) {
@@ -248,6 +253,25 @@ extern "C" int q2a_dequantize_row(int ggml_type, const void * row, float * y, in
                     const int v = ((j & 1) ? (q[l] >> 4) : (q[l] & 0xF)) + (q5 ? ((qh[l] >> j) & 1) << 4 : 0);
                     y[b * 256 + 32 * j + l] = d1 * v - m1;
                 }
+            }
+        }
+    } else if (ggml_type == Q2A_TYPE_Q2_K) {
+        for (int64_t b = 0; b < n_cols / 256; ++b) {
+            const q2a_block_q2_K * x = (const q2a_block_q2_K *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d), dmin = q2a_fp16_to_fp32(x->dmin);
+            for (int k = 0; k < 256; ++k) {
+                const uint8_t sc = x->scales[k / 16];
+                const float dl = d * (sc & 0xF), ml = dmin * (sc >> 4);
+                y[b * 256 + k] = dl * q2a_q2k_code(x, k) - ml;
+            }
+        }
+    } else if (ggml_type == Q2A_TYPE_Q3_K) {
+        for (int64_t b = 0; b < n_cols / 256; ++b) {
+            const q2a_block_q3_K * x = (const q2a_block_q3_K *) row + b;
+            const float d = q2a_fp16_to_fp32(x->d);
+            for (int k = 0; k < 256; ++k) {
+                const float dl = d * (q2a_q3k_scale(x, k / 16) - 32);
+                y[b * 256 + k] = dl * (q2a_q3k_code(x, k) - 4);
             }
         }
     } else if (ggml_type == Q2A_TYPE_Q6_K) {
@@ -305,9 +329,10 @@ static inline int nearest_int(float fval) {               // ggml-quants.c:1639-
     return (i & 0x007fffff) - 0x00400000;
 }
 
-// make_qkx2_quants, ggml-quants.c:1817-1896 (weighted least squares search for scale/min)
+// make_qkx2_quants, ggml-quants.c:1817-1896 (weighted least squares search for scale/min; use_mad: the candidates are
+// compared by weighted absolute error instead of squared error, Q2_K's choice)
 static float make_qkx2(int n, int nmax, const float * x, const float * w, uint8_t * L, float * the_min,
-                       uint8_t * Laux, float rmin, float rdelta, int nstep) {
+                       uint8_t * Laux, float rmin, float rdelta, int nstep, bool use_mad = false) {
     float mn = x[0], mx = x[0];
     float sum_w = w[0];
     float sum_x = sum_w * x[0];
@@ -330,7 +355,7 @@ static float make_qkx2(int n, int nmax, const float * x, const float * w, uint8_
         int l = nearest_int(iscale * (x[i] - mn));
         L[i] = (uint8_t) std::max(0, std::min(nmax, l));
         float diff = scale * L[i] + mn - x[i];
-        diff = diff * diff;
+        diff = use_mad ? fabsf(diff) : diff * diff;
         best += w[i] * diff;
     }
     for (int is = 0; is <= nstep; ++is) {
@@ -356,7 +381,7 @@ static float make_qkx2(int n, int nmax, const float * x, const float * w, uint8_
             float mad = 0;
             for (int i = 0; i < n; ++i) {
                 float diff = this_scale * Laux[i] + this_min - x[i];
-                diff = diff * diff;
+                diff = use_mad ? fabsf(diff) : diff * diff;
                 mad += w[i] * diff;
             }
             if (mad < best) {
@@ -378,6 +403,152 @@ static inline void scale_min_k4(int j, const uint8_t * q, uint8_t * d, uint8_t *
     } else {
         *d = (uint8_t) ((q[j + 4] & 0xF) | ((q[j - 4] >> 6) << 4));
         *m = (uint8_t) ((q[j + 4] >> 4) | ((q[j - 0] >> 6) << 4));
+    }
+}
+
+// make_q3_quants with do_rmse, ggml-quants.c:1715-1765: codes -nmax .. nmax-1 from -nmax / max, then up to five passes
+// that move one code at a time when it raises (sum w x l)^2 / (sum w l^2), w = x^2; L is returned offset by nmax
+static float make_q3_rmse(int n, int nmax, const float * x, int8_t * L) {
+    float max = 0, amax = 0;
+    for (int i = 0; i < n; ++i) {
+        const float ax = fabsf(x[i]);
+        if (ax > amax) { amax = ax; max = x[i]; }
+    }
+    if (amax < 1e-15f) {   // GROUP_MAX_EPS: all zero
+        for (int i = 0; i < n; ++i) L[i] = 0;
+        return 0.f;
+    }
+    const float iscale = -nmax / max;
+    float sumlx = 0, suml2 = 0;
+    for (int i = 0; i < n; ++i) {
+        int l = nearest_int(iscale * x[i]);
+        l = std::max(-nmax, std::min(nmax - 1, l));
+        L[i] = (int8_t) l;
+        const float w = x[i] * x[i];
+        sumlx += w * x[i] * l;
+        suml2 += w * l * l;
+    }
+    for (int itry = 0; itry < 5; ++itry) {
+        int n_changed = 0;
+        for (int i = 0; i < n; ++i) {
+            const float w = x[i] * x[i];
+            float slx = sumlx - w * x[i] * L[i];
+            if (slx > 0) {
+                float sl2 = suml2 - w * L[i] * L[i];
+                int new_l = nearest_int(x[i] * sl2 / slx);
+                new_l = std::max(-nmax, std::min(nmax - 1, new_l));
+                if (new_l != L[i]) {
+                    slx += w * x[i] * new_l;
+                    sl2 += w * new_l * new_l;
+                    if (sl2 > 0 && slx * slx * suml2 > sumlx * sumlx * sl2) {
+                        L[i] = (int8_t) new_l; sumlx = slx; suml2 = sl2;
+                        ++n_changed;
+                    }
+                }
+            }
+        }
+        if (!n_changed) break;
+    }
+    for (int i = 0; i < n; ++i) L[i] = (int8_t) (L[i] + nmax);
+    return sumlx / suml2;
+}
+
+// quantize_row_q2_K_ref, ggml-quants.c:1909-1977: sixteen sub-blocks of 16, 2-bit codes, the scale / min search with
+// |x| weights and the absolute-error measure, 4-bit scale | min per sub-block against the block's d / dmin
+extern "C" void q2a_quantize_row_q2_K(const float * x, void * vy, int64_t k) {
+    q2a_block_q2_K * y = (q2a_block_q2_K *) vy;
+    const int64_t nb = k / 256;
+    uint8_t L[256], Laux[16];
+    float weights[16], mins[16], scales[16];
+    const float q4scale = 15.f;
+    for (int64_t i = 0; i < nb; i++) {
+        float max_scale = 0, max_min = 0;
+        for (int j = 0; j < 16; ++j) {
+            for (int l = 0; l < 16; ++l) weights[l] = fabsf(x[16 * j + l]);
+            scales[j] = make_qkx2(16, 3, x + 16 * j, weights, L + 16 * j, &mins[j], Laux, -0.5f, 0.1f, 15, true);
+            if (scales[j] > max_scale) max_scale = scales[j];
+            if (mins[j] > max_min) max_min = mins[j];
+        }
+        if (max_scale > 0) {
+            const float iscale = q4scale / max_scale;
+            for (int j = 0; j < 16; ++j) y[i].scales[j] = (uint8_t) nearest_int(iscale * scales[j]);
+            y[i].d = q2a_fp32_to_fp16(max_scale / q4scale);
+        } else {
+            for (int j = 0; j < 16; ++j) y[i].scales[j] = 0;
+            y[i].d = q2a_fp32_to_fp16(0.f);
+        }
+        if (max_min > 0) {
+            const float iscale = q4scale / max_min;
+            for (int j = 0; j < 16; ++j) y[i].scales[j] |= (uint8_t) (nearest_int(iscale * mins[j]) << 4);
+            y[i].dmin = q2a_fp32_to_fp16(max_min / q4scale);
+        } else {
+            y[i].dmin = q2a_fp32_to_fp16(0.f);
+        }
+        for (int j = 0; j < 16; ++j) {
+            const float d = q2a_fp16_to_fp32(y[i].d) * (y[i].scales[j] & 0xF);
+            if (!d) continue;
+            const float dm = q2a_fp16_to_fp32(y[i].dmin) * (y[i].scales[j] >> 4);
+            for (int ii = 0; ii < 16; ++ii) {
+                const int l = nearest_int((x[16 * j + ii] + dm) / d);
+                L[16 * j + ii] = (uint8_t) std::max(0, std::min(3, l));
+            }
+        }
+        for (int j = 0; j < 256; j += 128)
+            for (int l = 0; l < 32; ++l)
+                y[i].qs[j / 4 + l] = (uint8_t) (L[j + l] | (L[j + l + 32] << 2) | (L[j + l + 64] << 4) | (L[j + l + 96] << 6));
+        x += 256;
+    }
+}
+
+// quantize_row_q3_K_ref, ggml-quants.c:2251-2325: sixteen sub-blocks of 16 with 6-bit signed scales (the largest mapped
+// to -32), codes q - 4 in -4 .. 3: two bits in qs, the third in hmask (weight j: bit j / 32 of hmask[j % 32])
+extern "C" void q2a_quantize_row_q3_K(const float * x, void * vy, int64_t k) {
+    q2a_block_q3_K * y = (q2a_block_q3_K *) vy;
+    const int64_t nb = k / 256;
+    int8_t L[256];
+    float scales[16];
+    for (int64_t i = 0; i < nb; i++) {
+        float max_scale = 0, amax = 0;
+        for (int j = 0; j < 16; ++j) {
+            scales[j] = make_q3_rmse(16, 4, x + 16 * j, L + 16 * j);
+            const float scale = fabsf(scales[j]);
+            if (scale > amax) { amax = scale; max_scale = scales[j]; }
+        }
+        memset(y[i].scales, 0, 12);
+        if (max_scale) {
+            const float iscale = -32.f / max_scale;
+            for (int j = 0; j < 16; ++j) {
+                int8_t l = (int8_t) nearest_int(iscale * scales[j]);
+                l = (int8_t) (std::max(-32, std::min(31, (int) l)) + 32);
+                if (j < 8) y[i].scales[j] = (uint8_t) (l & 0xF);
+                else y[i].scales[j - 8] |= (uint8_t) ((l & 0xF) << 4);
+                l >>= 4;
+                y[i].scales[j % 4 + 8] |= (uint8_t) (l << (2 * (j / 4)));
+            }
+            y[i].d = q2a_fp32_to_fp16(1 / iscale);
+        } else {
+            y[i].d = q2a_fp32_to_fp16(0.f);
+        }
+        for (int j = 0; j < 16; ++j) {
+            const int8_t sc = (int8_t) (q2a_q3k_scale(&y[i], j) - 32);
+            const float d = q2a_fp16_to_fp32(y[i].d) * sc;
+            if (!d) continue;
+            for (int ii = 0; ii < 16; ++ii) {
+                int l = nearest_int(x[16 * j + ii] / d);
+                l = std::max(-4, std::min(3, l));
+                L[16 * j + ii] = (int8_t) (l + 4);
+            }
+        }
+        memset(y[i].hmask, 0, 32);
+        for (int j = 0; j < 256; ++j)
+            if (L[j] > 3) {
+                y[i].hmask[j % 32] |= (uint8_t) (1 << (j / 32));
+                L[j] -= 4;
+            }
+        for (int j = 0; j < 256; j += 128)
+            for (int l = 0; l < 32; ++l)
+                y[i].qs[j / 4 + l] = (uint8_t) (L[j + l] | (L[j + l + 32] << 2) | (L[j + l + 64] << 4) | (L[j + l + 96] << 6));
+        x += 256;
     }
 }
 
@@ -820,6 +991,8 @@ int ftype_to_wtype(int ft) {
         case Q2A_FTYPE_MOSTLY_F16: return Q2A_TYPE_F16;
         case Q2A_FTYPE_MOSTLY_Q4_0: return Q2A_TYPE_Q4_0;
         case Q2A_FTYPE_MOSTLY_Q8_0: return Q2A_TYPE_Q8_0;
+        case Q2A_FTYPE_MOSTLY_Q2_K: return Q2A_TYPE_Q2_K;
+        case Q2A_FTYPE_MOSTLY_Q3_K: return Q2A_TYPE_Q3_K;
         case Q2A_FTYPE_MOSTLY_Q4_K: return Q2A_TYPE_Q4_K;
         case Q2A_FTYPE_MOSTLY_Q5_K: return Q2A_TYPE_Q5_K;
         case Q2A_FTYPE_MOSTLY_Q6_K: return Q2A_TYPE_Q6_K;
@@ -918,6 +1091,8 @@ extern "C" int q2a_quantize_model(const char * in_path, const char * out_path, i
     int ftype;
     void (*qrow)(const float *, void *, int64_t);
     switch (qtype) {
+        case Q2A_TYPE_Q2_K: ftype = Q2A_FTYPE_MOSTLY_Q2_K; qrow = q2a_quantize_row_q2_K; break;
+        case Q2A_TYPE_Q3_K: ftype = Q2A_FTYPE_MOSTLY_Q3_K; qrow = q2a_quantize_row_q3_K; break;
         case Q2A_TYPE_Q4_K: ftype = Q2A_FTYPE_MOSTLY_Q4_K; qrow = q2a_quantize_row_q4_K; break;
         case Q2A_TYPE_Q5_K: ftype = Q2A_FTYPE_MOSTLY_Q5_K; qrow = q2a_quantize_row_q5_K; break;
         case Q2A_TYPE_Q6_K: ftype = Q2A_FTYPE_MOSTLY_Q6_K; qrow = q2a_quantize_row_q6_K; break;

@@ -20,6 +20,8 @@ enum q2a_ggml_type {
     Q2A_TYPE_F16 = 1,
     Q2A_TYPE_Q4_0 = 2,
     Q2A_TYPE_Q8_0 = 8,
+    Q2A_TYPE_Q2_K = 10,
+    Q2A_TYPE_Q3_K = 11,
     Q2A_TYPE_Q4_K = 12,
     Q2A_TYPE_Q5_K = 13,
     Q2A_TYPE_Q6_K = 14,
@@ -32,6 +34,8 @@ enum q2a_ggml_ftype {
     Q2A_FTYPE_MOSTLY_F16 = 1,
     Q2A_FTYPE_MOSTLY_Q4_0 = 2,
     Q2A_FTYPE_MOSTLY_Q8_0 = 7,
+    Q2A_FTYPE_MOSTLY_Q2_K = 10,
+    Q2A_FTYPE_MOSTLY_Q3_K = 11,
     Q2A_FTYPE_MOSTLY_Q4_K = 12,
     Q2A_FTYPE_MOSTLY_Q5_K = 13,
     Q2A_FTYPE_MOSTLY_Q6_K = 14,
@@ -43,13 +47,27 @@ enum q2a_ggml_ftype {
 #define Q2A_QK8_0 32
 #define Q2A_QK4_0 32
 
-// block layouts (ggml/src/ggml-common.h:143-149, 186-191, 282-297, 299-326, 329-335)
+// block layouts (ggml/src/ggml-common.h:143-149, 186-191, 253-280, 282-297, 299-326, 329-335)
 typedef struct { uint16_t d; uint8_t qs[16]; } q2a_block_q4_0;           // 18 B / 32 weights
 typedef struct { uint16_t d; int8_t qs[32]; } q2a_block_q8_0;            // 34 B / 32 weights
+typedef struct { uint8_t scales[16]; uint8_t qs[64]; uint16_t d, dmin; } q2a_block_q2_K;                  // 84 B / 256
+typedef struct { uint8_t hmask[32]; uint8_t qs[64]; uint8_t scales[12]; uint16_t d; } q2a_block_q3_K;    // 110 B / 256
 typedef struct { uint16_t d, dmin; uint8_t scales[12]; uint8_t qs[128]; } q2a_block_q4_K;  // 144 B / 256
 typedef struct { uint16_t d, dmin; uint8_t scales[12]; uint8_t qh[32]; uint8_t qs[128]; } q2a_block_q5_K;  // 176 B / 256
 typedef struct { uint8_t ql[128]; uint8_t qh[64]; int8_t scales[16]; uint16_t d; } q2a_block_q6_K;         // 210 B / 256
 typedef struct { float d; int8_t qs[256]; int16_t bsums[16]; } q2a_block_q8_K;             // 292 B / 256
+
+// Q2_K / Q3_K field access (dequantize_row_q2_K / _q3_K's indexing, ggml-quants.c:1979-2009, 2327-2375), shared by the
+// dequantizer, the quantizers and the blob packer. Weight k of a block: 2-bit pair (k % 128) / 32 of qs[32 (k / 128) +
+// k % 32]; Q3_K's third bit is bit k / 32 of hmask[k % 32] (code 0..7, value code - 4); its sub-block scale j = k / 16 is
+// 6 bits, the low four in a nibble of scales[j % 8], the high two in scales[8 + j % 4] (0..63, value scale - 32).
+static inline int q2a_q2k_code(const q2a_block_q2_K * x, int k) { return (x->qs[32 * (k / 128) + k % 32] >> (2 * ((k % 128) / 32))) & 3; }
+static inline int q2a_q3k_code(const q2a_block_q3_K * x, int k) {
+    return ((x->qs[32 * (k / 128) + k % 32] >> (2 * ((k % 128) / 32))) & 3) | (((x->hmask[k % 32] >> (k / 32)) & 1) << 2);
+}
+static inline int q2a_q3k_scale(const q2a_block_q3_K * x, int j) {
+    return (j < 8 ? x->scales[j] & 0xF : x->scales[j - 8] >> 4) | (((x->scales[8 + j % 4] >> (2 * (j / 4))) & 3) << 4);
+}
 
 // whisper_hparams order as stored (qwen2-whisper.cpp:1374-1384)
 typedef struct {
@@ -80,11 +98,13 @@ int q2a_write_synthetic_projector(const char * path, int d_in, int d_out, int ft
 
 // Re-quantize a F16/F32 model file the way whisper.cpp's quantize flow does (examples/common-ggml.cpp:41-244
 // with to_quant {".*"} and skip {"embed_positions.weight","conv1.bias","conv2.bias"}; only 2-D tensors).
-// qtype: Q2A_TYPE_Q4_K / Q2A_TYPE_Q5_K / Q2A_TYPE_Q6_K / Q2A_TYPE_Q8_0 / Q2A_TYPE_Q4_0. Byte-identical to
+// qtype: Q2A_TYPE_Q2_K / Q3_K / Q4_K / Q5_K / Q6_K / Q8_0 / Q4_0. Byte-identical to
 // ggml_quantize_chunk. 0 on success.
 int q2a_quantize_model(const char * in_path, const char * out_path, int qtype, int n_threads);
 
 // Row quantizers (ggml "_ref" weight quantizers, byte-exact): k must be a multiple of the block size.
+void q2a_quantize_row_q2_K(const float * x, void * y, int64_t k);   // quantize_row_q2_K_ref ggml-quants.c:1909
+void q2a_quantize_row_q3_K(const float * x, void * y, int64_t k);   // quantize_row_q3_K_ref ggml-quants.c:2251
 void q2a_quantize_row_q4_K(const float * x, void * y, int64_t k);   // quantize_row_q4_K_ref ggml-quants.c:2483
 void q2a_quantize_row_q5_K(const float * x, void * y, int64_t k);   // quantize_row_q5_K_ref ggml-quants.c:2676
 void q2a_quantize_row_q6_K(const float * x, void * y, int64_t k);   // quantize_row_q6_K_ref ggml-quants.c:2907

@@ -1286,14 +1286,11 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { v[e] = (float) h0[e]; v[8 + e] = (float) h1[e]; }
                 float d;
-                int sm;
-                quant_q8k_row16c(v, sub, p.outH + (int64_t) min(m, p.M - 1) * p.ldo + n0 + sub * 16, m < p.M, d, sm);
+                int sm, sm16;
+                quant_q8k_row16c(v, sub, p.outH + (int64_t) min(m, p.M - 1) * p.ldo + n0 + sub * 16, m < p.M, d, sm, sm16);
                 if (sub == 0) sd[rl] = d;
-                if ((sub & 1) == 0) {   // the bsum operand pair (64·hi + lo = bsum32, both exact in fp16)
-                    const int hi = (sm >= 0) ? (sm >> 6) : -((-sm + 63) >> 6);
-                    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-                    *(h2_t *) (sa + rl * 16 + sub) = h2_t{(_Float16) (float) hi, (_Float16) (float) (sm - 64 * hi)};
-                }
+                // the bsum operand pair (64·hi + lo = bsum32, both exact in fp16), or the raw 16-sums (Q2_K weights)
+                store_row16_sums(p.q_sum16 != 0, sub, sm, sm16, sa + rl * 16);
             }
             __syncthreads();
             // the pass's side outputs are contiguous in their block-major arrays (rows m0 + 128ps ..): d 512 B, bsum
@@ -1351,8 +1348,11 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void k_gemm(const q2a_gemm_args p_
                 const int m = m0 + ps * PRQ + rl;
                 if (m < p.M) {
                     const float4 y = *(const float4 *) (tl + rl * RS + 4 * lane);
-                    quant_q8k_block(y, lane, p.outH + (int64_t) m * p.ldo + n0 + 4 * lane, p.qdy + (int64_t) kb * p.dy_ld + m,
-                                    p.qaext + ((int64_t) kb * p.dy_ld + m) * 16);
+                    q2a_half * const co = p.outH + (int64_t) m * p.ldo + n0 + 4 * lane;
+                    float * const dq = p.qdy + (int64_t) kb * p.dy_ld + m;
+                    q2a_half * const aq = p.qaext + ((int64_t) kb * p.dy_ld + m) * 16;
+                    if (p.q_sum16) quant_q8k_block<true>(y, lane, co, dq, aq);
+                    else quant_q8k_block<false>(y, lane, co, dq, aq);
                 }
             }
             __syncthreads();

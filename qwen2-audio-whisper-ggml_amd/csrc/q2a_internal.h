@@ -60,7 +60,12 @@ struct q2a_gemm_args {
     int64_t ldo;
     q2a_half * outH;                  // (Q2A_EPI_GELU_F: optional fp16 copy of outF, same row stride)
     int o_rpg, o_gstride, o_off;      // output row remap for outH: (m / o_rpg) * o_gstride + (m % o_rpg) + o_off
-    int o_dup;                        // Q2A_EPI_GELU_H: also store the row at column offset o_dup (0 = no copy)
+    union {                           // (one slot: the struct's size and layout stay, so an object compiled before
+                                      //  q_sum16 existed, which zeroes the struct, still passes a valid one)
+        int o_dup;                    // Q2A_EPI_GELU_H: also store the row at column offset o_dup (0 = no copy)
+        int q_sum16;                  // Q2A_EPI_GELU_Q8K: 1 = qaext gets each block's sixteen raw 16-sums (q2a_ln_args
+                                      //   mode 5, Q2_K weights) instead of the eight (hi, lo) pairs
+    };
     const float * pe;
     int T;                            // positions per clip
     q2a_half *qh, *ql, *kh, *kl, *vt;
@@ -242,6 +247,8 @@ hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s);
 //   2: Q8_0 as fp16 codes + dy[M][D/32]  (Q8_0 / Q4_0 weights)
 //   3: fp16 split [hi | lo | hi] rows of 3D (F32 weights: exact-f32-class products against [Wh | Wh | Wl])
 //   4: bf16 RNE [M][D]                 (bf16-activation mode)
+//   5: mode 1 with aext = the block's sixteen raw 16-sums instead of eight (hi, lo) pairs (Q2_K weights); codes and dy
+//      are mode 1's bit for bit. The same value selects it in q2a_quant_args and q2a_pool_pack_args.
 struct q2a_ln_args {
     const float * X;
     int M, D;
@@ -271,6 +278,10 @@ hipError_t q2a_launch_quant_act(const q2a_quant_args & a, hipStream_t s);
 // then Q8_K quantization — the same codes as Q2A_EPI_GELU_H + q2a_launch_quant_act(mode 1, XH). XH [M][K], K % 256 == 0.
 hipError_t q2a_launch_gelu_quant_q8k(const q2a_half * XH, int M, int K, const uint16_t * gelu_tab, q2a_half * outH,
                                      float * dy, q2a_half * aext, int dy_ld, hipStream_t s);
+// sum16: aext gets the raw 16-sums (q2a_ln_args mode 5). An overload and not a defaulted argument, as q2a_pack_linear
+// below: a plugin object compiled before `sum16` existed must still find the nine-argument symbol in this libq2a.so.
+hipError_t q2a_launch_gelu_quant_q8k(const q2a_half * XH, int M, int K, const uint16_t * gelu_tab, q2a_half * outH,
+                                     float * dy, q2a_half * aext, int dy_ld, hipStream_t s, bool sum16);
 
 // One ggml weight matrix [N][K] (raw ggml rows, host memory; F16 / Q4_K / Q8_0 / Q4_0) packed into the GEMM's
 // operand layout: fp16 W' [N][K] plus the block-major scale arrays, at byte offsets off[0..5] = W, DX, DMIN, WEXT,
@@ -376,7 +387,7 @@ struct q2a_embed_gather_q_args {
     int64_t n_tokens;
     int64_t audio_id;
     const void * rows;           // 16-byte aligned
-    int ggml_type;               // Q2A_TYPE_Q4_0 / Q8_0 / Q4_K / Q5_K / Q6_K
+    int ggml_type;               // Q2A_TYPE_Q4_0 / Q8_0 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K
     int64_t vocab, n_cols, row_bytes;
     void * out;                  // 16-byte aligned
     int64_t out_ld_bytes;        // a multiple of 16

@@ -47,7 +47,24 @@ __device__ __forceinline__ float first_max_value(float amax, float local_first, 
     return gm ? v : amax;
 }
 
-// quantize one 256-block (one float4 per lane) to Q8_K codes; writes codes, d and the bsum hi/lo operand
+// The min operand aext[16] of a block comes in two forms. The (hi, lo) form (S16 = false; Q4_K / Q5_K weights, and Q3_K
+// whose min operand is zero): the eight 32-sums as pairs with bsum32_j = 64 hi + lo, against WEXT = (64 m_j, m_j). The
+// raw form (S16 = true; Q2_K weights, 16-wide sub-blocks): the sixteen 16-sums themselves (|s| <= 16 * 127 = 2032, exact
+// in fp16) against WEXT = the sixteen 4-bit mins. The lane reduction of the raw form stops one step earlier; codes and d
+// are the same in both, bit for bit.
+//
+// a lane's share of the raw form in the float4-per-lane kernels: s = the 16-sum of the lane's quad (sub-block lane >> 2);
+// lanes 8j store sub-blocks 2j and 2j + 1 (the second fetched from lane + 4) as one dword
+__device__ __forceinline__ void store_sum16_pair(int s, int lane, q2a_half * aext) {
+    const int t = (int) dpp_u<DPP_ROR12>((uint32_t) s);   // lane + 4's 16-sum
+    if ((lane & 7) == 0) {
+        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+        *(h2_t *) (aext + (lane >> 2)) = h2_t{(_Float16) (float) s, (_Float16) (float) t};
+    }
+}
+
+// quantize one 256-block (one float4 per lane) to Q8_K codes; writes codes, d and the bsum operand
+template <bool S16 = false>
 __device__ __forceinline__ void quant_q8k_block(float4 y, int lane, q2a_half * codes, float * dy_out, q2a_half * aext) {
     // max |x| and the signed value of its FIRST occurrence (strict '>' scan, :3793-3798)
     float vv[4] = {y.x, y.y, y.z, y.w};
@@ -72,6 +89,7 @@ __device__ __forceinline__ void quant_q8k_block(float4 y, int lane, q2a_half * c
     int s = q[0] + q[1] + q[2] + q[3];
     s += (int) dpp_u<DPP_XOR1>((uint32_t) s);
     s += (int) dpp_u<DPP_XOR2>((uint32_t) s);
+    if constexpr (S16) { store_sum16_pair(s, lane, aext); return; }
     s += (int) dpp_u<DPP_ROR12>((uint32_t) s);   // + lane + 4: lanes 8j now hold lanes 8j .. 8j + 7 (others unused)
     if ((lane & 7) == 0) {
         const int j = lane >> 3;
@@ -87,9 +105,28 @@ __device__ __forceinline__ void quant_q8k_block(float4 y, int lane, q2a_half * c
 // (DPP within the row). codes: this lane's 16 codes; aext: the row's 16-half bsum operand.
 
 // the arithmetic of quant_q8k_row16 with this lane's 16 codes stored (when st) and the block's d and this lane
-// PAIR's bsum32 (sub-block sub / 2) returned instead of stored
+// PAIR's bsum32 (sub-block sub / 2) returned instead of stored; s16_out: this lane's own 16-sum (sub-block sub of the
+// raw form)
+__device__ __forceinline__ void quant_q8k_row16c(const float (&v)[16], int sub, q2a_half * codes, bool st, float & d_out,
+                                                 int & s_out, int & s16_out);
 __device__ __forceinline__ void quant_q8k_row16c(const float (&v)[16], int sub, q2a_half * codes, bool st, float & d_out,
                                                  int & s_out) {
+    int s16;
+    quant_q8k_row16c(v, sub, codes, st, d_out, s_out, s16);
+}
+// the (hi, lo) pair of a 32-sum / the raw 16-sum, stored by the lanes that hold them: sub-block sub's slot(s) of aext
+__device__ __forceinline__ void store_row16_sums(bool s16_form, int sub, int s32, int s16, q2a_half * aext) {
+    if (s16_form) {
+        aext[sub] = (_Float16) (float) s16;
+    } else if ((sub & 1) == 0) {
+        const int hi = (s32 >= 0) ? (s32 >> 6) : -((-s32 + 63) >> 6);   // floor(s / 64)
+        const int lo = s32 - 64 * hi;
+        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+        *(h2_t *) (aext + sub) = h2_t{(_Float16) (float) hi, (_Float16) (float) lo};
+    }
+}
+__device__ __forceinline__ void quant_q8k_row16c(const float (&v)[16], int sub, q2a_half * codes, bool st, float & d_out,
+                                                 int & s_out, int & s16_out) {
     // this lane's first element of largest |x| (a backward scan keeps the earliest on ties), then the block max
     float lm = v[15];
 #pragma unroll
@@ -133,28 +170,25 @@ __device__ __forceinline__ void quant_q8k_row16c(const float (&v)[16], int sub, 
 #pragma unroll
     for (int e = 0; e < 16; e += 2) s2 = s2 + f2_t{q[e], q[e + 1]};
     int s = (int) (s2[0] + s2[1]);
+    s16_out = s;
     s += (int) dpp_u<DPP_XOR1>((uint32_t) s);                  // bsum32 of sub-block j = sub / 2
     d_out = d;
     s_out = s;
 }
 
+template <bool S16 = false>
 __device__ __forceinline__ void quant_q8k_row16(const float (&v)[16], int sub, q2a_half * codes, float * dy_out,
                                                 q2a_half * aext) {
     float d;
-    int s;
-    quant_q8k_row16c(v, sub, codes, true, d, s);
+    int s, s16;
+    quant_q8k_row16c(v, sub, codes, true, d, s, s16);
     if (sub == 0) *dy_out = d;
-    if ((sub & 1) == 0) {
-        const int hi = (s >= 0) ? (s >> 6) : -((-s + 63) >> 6);   // floor(s / 64)
-        const int lo = s - 64 * hi;
-        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-        *(h2_t *) (aext + sub) = h2_t{(_Float16) (float) hi, (_Float16) (float) lo};
-    }
+    store_row16_sums(S16, sub, s, s16, aext);
 }
 
 // NB independent 256-blocks, one float4 per lane each (block u = lanes 0..63 x 4 of y[u]): quant_q8k_block's
 // arithmetic with the NB reduction chains interleaved (the LayerNorm kernel's row is NB = D/256 blocks)
-template <int NB>
+template <int NB, bool S16 = false>
 __device__ __forceinline__ void quant_q8k_blocks(const float4 (&y)[NB], int lane, q2a_half * codes, int64_t code_stride,
                                                  float * dy_out, int64_t dy_stride, q2a_half * aext, int64_t aext_stride) {
     float amax[NB], mx[NB];
@@ -193,6 +227,11 @@ __device__ __forceinline__ void quant_q8k_blocks(const float4 (&y)[NB], int lane
     for (int u = 0; u < NB; ++u) s[u] += (int) dpp_u<DPP_XOR1>((uint32_t) s[u]);
 #pragma unroll
     for (int u = 0; u < NB; ++u) s[u] += (int) dpp_u<DPP_XOR2>((uint32_t) s[u]);
+    if constexpr (S16) {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) store_sum16_pair(s[u], lane, aext + u * aext_stride);
+        return;
+    }
 #pragma unroll
     for (int u = 0; u < NB; ++u) s[u] += (int) dpp_u<DPP_ROR12>((uint32_t) s[u]);   // + lane + 4: lanes 8j: their 8 lanes
     if ((lane & 7) == 0) {

@@ -101,7 +101,8 @@ def embeds_src(ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int,
 
 # ggml types of a quantized embedding table (include/q2a_encoder.h, q2a_embed_qtable): (bytes, columns) of a block
 TYPE_Q4_0, TYPE_Q8_0, TYPE_Q4_K, TYPE_Q5_K, TYPE_Q6_K = 2, 8, 12, 13, 14
-_QBLOCK = {TYPE_Q4_0: (18, 32), TYPE_Q8_0: (34, 32), TYPE_Q4_K: (144, 256), TYPE_Q5_K: (176, 256), TYPE_Q6_K: (210, 256)}
+TYPE_Q2_K, TYPE_Q3_K = 10, 11
+_QBLOCK = {TYPE_Q4_0: (18, 32), TYPE_Q8_0: (34, 32), TYPE_Q2_K: (84, 256), TYPE_Q3_K: (110, 256), TYPE_Q4_K: (144, 256), TYPE_Q5_K: (176, 256), TYPE_Q6_K: (210, 256)}
 
 
 def quant_row_size(ggml_type: int, n_cols: int) -> int:
@@ -121,13 +122,13 @@ class EmbedQTable(C.Structure):
 class QuantTable:
     """A quantized embedding table for Engine.inputs_embeds(embed_table=...) and the _q calls: rows, a CUDA uint8 tensor
     [vocab][row_bytes] (row_bytes a multiple of 16 and >= quant_row_size(ggml_type, n_cols), 16-byte aligned) holding
-    each row's ggml blocks (Q4_0, Q8_0, Q4_K, Q5_K or Q6_K) as they lie in a GGUF file's token_embd.weight. The tensor is
+    each row's ggml blocks (Q4_0, Q8_0, Q2_K, Q3_K, Q4_K, Q5_K or Q6_K) as they lie in a GGUF file's token_embd.weight. The tensor is
     kept alive by the object; .desc is the q2a_embed_qtable of the C calls."""
 
     def __init__(self, rows, ggml_type: int, n_cols: int):
         import torch
         if ggml_type not in _QBLOCK:
-            raise ValueError(f"ggml type {ggml_type}: Q4_0 (2), Q8_0 (8), Q4_K (12), Q5_K (13) or Q6_K (14)")
+            raise ValueError(f"ggml type {ggml_type}: Q4_0 (2), Q8_0 (8), Q2_K (10), Q3_K (11), Q4_K (12), Q5_K (13) or Q6_K (14)")
         if n_cols < 256 or n_cols % 256:
             raise ValueError(f"n_cols {n_cols}: a multiple of 256")
         if not (hasattr(rows, "is_cuda") and rows.is_cuda and rows.dtype == torch.uint8 and rows.dim() == 2 and rows.is_contiguous()

@@ -13,7 +13,9 @@ import numpy as np
 MAGIC = 0x67676D6C
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0, TYPE_Q4_K, TYPE_Q8_K = 0, 1, 2, 8, 12, 15
 TYPE_Q5_K, TYPE_Q6_K = 13, 14
-FTYPE_TO_WTYPE = {0: TYPE_F32, 1: TYPE_F16, 2: TYPE_Q4_0, 7: TYPE_Q8_0, 12: TYPE_Q4_K, 13: TYPE_Q5_K, 14: TYPE_Q6_K}
+TYPE_Q2_K, TYPE_Q3_K = 10, 11
+FTYPE_TO_WTYPE = {0: TYPE_F32, 1: TYPE_F16, 2: TYPE_Q4_0, 7: TYPE_Q8_0, 10: TYPE_Q2_K, 11: TYPE_Q3_K,
+                  12: TYPE_Q4_K, 13: TYPE_Q5_K, 14: TYPE_Q6_K}
 HPARAM_NAMES = ("n_vocab", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer",
                 "n_text_ctx", "n_text_state", "n_text_head", "n_text_layer", "n_mels", "ftype")
 
@@ -27,6 +29,10 @@ def row_size(t: int, n: int) -> int:
         return (n // 32) * 18
     if t == TYPE_Q8_0:
         return (n // 32) * 34
+    if t == TYPE_Q2_K:
+        return (n // 256) * 84
+    if t == TYPE_Q3_K:
+        return (n // 256) * 110
     if t == TYPE_Q4_K:
         return (n // 256) * 144
     if t == TYPE_Q5_K:
@@ -51,18 +57,41 @@ class Tensor:
             return self.data.view(np.float32).reshape(tuple(reversed(self.ne)))
         if self.type == TYPE_F16:
             return self.data.view(np.float16).astype(np.float32).reshape(tuple(reversed(self.ne)))
-        if self.type in (TYPE_Q5_K, TYPE_Q6_K):
+        if self.type in (TYPE_Q2_K, TYPE_Q3_K, TYPE_Q5_K, TYPE_Q6_K):
             return self._dequant_kq()
         raise ValueError("quantized tensor has no plain f32 view")
 
     def kq(self) -> dict:
-        """The integer view of a Q5_K / Q6_K tensor, rows = prod(ne[1:]), nb = ne[0] / 256 blocks per row:
+        """The integer view of a Q2_K / Q3_K / Q5_K / Q6_K tensor, rows = prod(ne[1:]), nb = ne[0] / 256 blocks per row:
+        Q2_K: d, dmin f32 [rows][nb]; sc, m int32 [rows][nb][16] (4-bit); q int32 [rows][K] in 0..3
+              (weight = d*sc*q - dmin*m per 16-weight sub-block, dequantize_row_q2_K ggml-quants.c:1979)
+        Q3_K: d f32 [rows][nb]; sc int32 [rows][nb][16] in 0..63; q int32 [rows][K] in 0..7
+              (weight = d*(sc - 32)*(q - 4) per 16-weight sub-block, dequantize_row_q3_K ggml-quants.c:2327)
         Q5_K: d, dmin f32 [rows][nb]; sc, m int32 [rows][nb][8] (6-bit, get_scale_min_k4); q int32 [rows][K] in 0..31
               (weight = d*sc*q - dmin*m per 32-weight sub-block, dequantize_row_q5_K ggml-quants.c:2763)
         Q6_K: d f32 [rows][nb]; sc int32 [rows][nb][16] (int8); q int32 [rows][K] in 0..63
               (weight = d*sc*(q - 32) per 16-weight sub-block, dequantize_row_q6_K ggml-quants.c:2977)"""
         K = self.ne[0]
         rows, nb = int(np.prod(self.ne)) // K, K // 256
+        if self.type in (TYPE_Q2_K, TYPE_Q3_K):
+            q3 = self.type == TYPE_Q3_K
+            blk = self.data.reshape(rows, nb, 110 if q3 else 84)
+            qs = blk[:, :, 32:96] if q3 else blk[:, :, 16:80]
+            # weight k: 2-bit pair (k % 128) / 32 of qs[32 (k / 128) + k % 32]
+            qs = qs.astype(np.int32).reshape(rows, nb, 2, 1, 32)
+            q = (qs >> (2 * np.arange(4, dtype=np.int32))[:, None]) & 3       # [rows][nb][2][4][32]
+            if not q3:
+                s = blk[:, :, 0:16].astype(np.int32)
+                d = blk[:, :, 80:82].copy().view(np.float16).astype(np.float32)[..., 0]
+                dmin = blk[:, :, 82:84].copy().view(np.float16).astype(np.float32)[..., 0]
+                return {"d": d, "dmin": dmin, "sc": s & 0xF, "m": s >> 4, "q": q.reshape(rows, K)}
+            hm = blk[:, :, 0:32].astype(np.int32)[:, :, None, :]               # third bit: bit k / 32 of hmask[k % 32]
+            hi = ((hm >> np.arange(8, dtype=np.int32)[:, None]) & 1).reshape(rows, nb, 2, 4, 32)
+            s = blk[:, :, 96:108].astype(np.int32)
+            lo4 = np.concatenate([s[..., 0:8] & 0xF, s[..., 0:8] >> 4], axis=-1)                    # [rows][nb][16]
+            hi2 = np.concatenate([(s[..., 8:12] >> (2 * g)) & 3 for g in range(4)], axis=-1)          # j -> 8 + j % 4, 2 (j / 4)
+            d = blk[:, :, 108:110].copy().view(np.float16).astype(np.float32)[..., 0]
+            return {"d": d, "sc": lo4 | (hi2 << 4), "q": (q | (hi << 2)).reshape(rows, K)}
         if self.type == TYPE_Q5_K:
             blk = self.data.reshape(rows, nb, 176)
             d = blk[:, :, 0:2].copy().view(np.float16).astype(np.float32)[..., 0]
@@ -89,15 +118,24 @@ class Tensor:
             q[:, :, :, 2] = (ql[:, :, :, 0] >> 4) | (((qh >> 4) & 3) << 4)
             q[:, :, :, 3] = (ql[:, :, :, 1] >> 4) | (((qh >> 6) & 3) << 4)
             return {"d": d, "sc": sc, "q": q.reshape(rows, K)}
-        raise ValueError("not a Q5_K / Q6_K tensor")
+        raise ValueError("not a Q2_K / Q3_K / Q5_K / Q6_K tensor")
 
     def _dequant_kq(self) -> np.ndarray:
-        """dequantize_row_q5_K / dequantize_row_q6_K, their f32 operations in their order"""
+        """dequantize_row_q2_K / _q3_K / _q5_K / _q6_K, their f32 operations in their order"""
         K = self.ne[0]
         v = self.kq()
         rows, nb = v["d"].shape
         f = np.float32
-        if self.type == TYPE_Q5_K:
+        if self.type == TYPE_Q2_K:
+            dl = (v["d"][..., None] * v["sc"].astype(f)).astype(f)         # d * (sc & 15)
+            ml = (v["dmin"][..., None] * v["m"].astype(f)).astype(f)       # min * (sc >> 4)
+            q = v["q"].reshape(rows, nb, 16, 16).astype(f)
+            y = ((dl[..., None] * q).astype(f) - ml[..., None]).astype(f)
+        elif self.type == TYPE_Q3_K:
+            dl = (v["d"][..., None] * (v["sc"] - 32).astype(f)).astype(f)  # d * (sc - 32)
+            q = (v["q"] - 4).reshape(rows, nb, 16, 16).astype(f)
+            y = (dl[..., None] * q).astype(f)
+        elif self.type == TYPE_Q5_K:
             d1 = (v["d"][..., None] * v["sc"].astype(f)).astype(f)         # d * sc
             m1 = (v["dmin"][..., None] * v["m"].astype(f)).astype(f)       # min * m
             q = v["q"].reshape(rows, nb, 8, 32).astype(f)

@@ -2,7 +2,7 @@
 // for the unchanged ggml file"; the reference ships no quantize executable).
 //
 //   q2a_tool gen-model OUT {tiny|full|L,D,H,M} {f32|f16} [seed] [threads]
-//   q2a_tool quantize IN OUT {q4_k|q5_k|q6_k|q8_0|q4_0} [threads]
+//   q2a_tool quantize IN OUT {q2_k|q3_k|q4_k|q5_k|q6_k|q8_0|q4_0} [threads]
 //   q2a_tool synth-clip OUT.f32 N_SAMPLES CLIP_INDEX
 //   q2a_tool gen-projector OUT D_IN D_OUT {f32|f16} [seed]   (Qwen2-Audio multi-modal projector, q2a_format.cpp)
 //   q2a_tool mel MODEL WAV OUT   (normalised log-mel of WAV, raw f32 [n_mels][n_len]: the input of q2a_main -mel.
@@ -23,7 +23,7 @@
 static int usage() {
     fprintf(stderr,
             "usage:\n  q2a_tool gen-model OUT {tiny|full|L,D,H,M} {f32|f16} [seed] [threads]\n"
-            "  q2a_tool quantize IN OUT {q4_k|q5_k|q6_k|q8_0|q4_0} [threads]\n"
+            "  q2a_tool quantize IN OUT {q2_k|q3_k|q4_k|q5_k|q6_k|q8_0|q4_0} [threads]\n"
             "  q2a_tool synth-clip OUT.f32 N_SAMPLES CLIP_INDEX\n"
             "  q2a_tool gen-projector OUT D_IN D_OUT {f32|f16} [seed]\n"
             "  q2a_tool mel MODEL WAV OUT\n");
@@ -89,7 +89,7 @@ int main(int argc, char ** argv) {
     }
     if (cmd == "quantize" && argc >= 5) {
         const std::string t = argv[4];
-        const int qt = t == "q4_k" ? Q2A_TYPE_Q4_K : t == "q5_k" ? Q2A_TYPE_Q5_K : t == "q6_k" ? Q2A_TYPE_Q6_K : t == "q8_0" ? Q2A_TYPE_Q8_0 : t == "q4_0" ? Q2A_TYPE_Q4_0 : -1;
+        const int qt = t == "q2_k" ? Q2A_TYPE_Q2_K : t == "q3_k" ? Q2A_TYPE_Q3_K : t == "q4_k" ? Q2A_TYPE_Q4_K : t == "q5_k" ? Q2A_TYPE_Q5_K : t == "q6_k" ? Q2A_TYPE_Q6_K : t == "q8_0" ? Q2A_TYPE_Q8_0 : t == "q4_0" ? Q2A_TYPE_Q4_0 : -1;
         if (qt < 0) return usage();
         return q2a_quantize_model(argv[2], argv[3], qt, argc > 5 ? atoi(argv[5]) : 8);
     }
