@@ -49,7 +49,7 @@ typedef struct {
     int32_t device;
     int64_t weight_bytes;   /* device bytes of the packed weight blob */
     int64_t workspace_bytes;
-    int32_t act;            /* Q2A_ACT_REFERENCE or Q2A_ACT_BF16 (from the blob) */
+    int32_t act;            /* Q2A_ACT_REFERENCE, Q2A_ACT_BF16 or Q2A_ACT_MXFP8 (from the blob) */
     int32_t reserved;
 } q2a_info;
 
@@ -65,9 +65,18 @@ q2a_engine * q2a_open(const char * model_path, int device);
  *                      bf16, inter-op activations (LN outputs, Q/K/V, attention probabilities and output, GELU
  *                      output) in bf16, bf16 MFMA with f32 accumulation; the residual stream, LN statistics,
  *                      softmax and the conv front end stay as in the reference contract. A different numerical
- *                      contract from the reference CPU path: its error is reported separately. */
+ *                      contract from the reference CPU path: its error is reported separately.
+ *   Q2A_ACT_MXFP8      the bf16 contract with the four weight GEMMs of a block on OCP MXFP8 operands (e4m3 elements, one
+ *                      e8m0 scale per 32 along K) for both the weights (quantized at pack time from the dequantize_row_*
+ *                      values) and the activations (quantized from the bf16 contract's operand at that point), block-scaled
+ *                      fp8 MFMA with f32 accumulation; everything else is the bf16 contract's. Serves
+ *                      the plain encode kinds: the padded and variable-length kinds, the audio-feature and inputs_embeds
+ *                      calls and q2a_test_gemm_epi answer Q2A_ERR_UNSUPPORTED, q2a_set_bf16_key_lengths Q2A_ERR_ARG;
+ *                      q2a_projector_open_ex, q2a_pack_model_compact and q2a_group_open refuse it (Q2A_ERR_UNSUPPORTED),
+ *                      q2a_group_open_with an engine of it. */
 #define Q2A_ACT_REFERENCE 0
 #define Q2A_ACT_BF16 1
+#define Q2A_ACT_MXFP8 2
 q2a_engine * q2a_open_ex(const char * model_path, int device, int act);
 int64_t q2a_pack_model_ex(const char * model_path, int act, void ** host_blob);
 
@@ -319,10 +328,13 @@ int q2a_test_fc1_path(q2a_engine * e, int path);
  * GELU table only: M and K are free (any model file serves), within the launchers' own limits.
  *   producer  Q2A_OPERAND_LN         LayerNorm(x; g, b) + conversion: x f32 [M][K], g, b f32 [K], K % 4 == 0, K <= 2048;
  *                                    mode 0 fp16, 1 Q8_K, 2 Q8_0, 3 the F32 files' split [M][3K] = hi | lo | hi, 4 bf16,
- *                                    5 Q8_K with raw 16-sums (the operand of Q2_K weights; K % 256 == 0)
+ *                                    5 Q8_K with raw 16-sums (the operand of Q2_K weights; K % 256 == 0),
+ *                                    6 MXFP8 (K % 32 == 0): out = the e4m3 bytes [M][K], dy_dev = the e8m0 scale bytes
+ *                                    [M][K/32] row-major (ld unused), aext unused
  *             Q2A_OPERAND_QUANT_F32  quantizer of f32 rows x [M][K] (the O-projection operand; K > 2048: the 1024-wide
  *                                    segments of the fc2 operand), mode 1, 2 or 5, K % 256 == 0, K <= 8192
- *             Q2A_OPERAND_QUANT_H16  the same on fp16 rows x [M][K]
+ *             Q2A_OPERAND_QUANT_H16  the same on fp16 rows x [M][K]; mode 6: MXFP8 of bf16 rows x [M][K], K % 32 == 0,
+ *                                    out and dy_dev as LN mode 6
  *             Q2A_OPERAND_GELU_Q8K   GELU table + Q8_K of fp16 pre-activation rows x [M][K], mode 1 or 5, M * K < 2^31
  *   out       [M][K] 2-byte elements (mode 3: [M][3K]): fp16 / bf16 values, or the integer codes held in fp16
  *   dy        modes 1, 2, 5: the block scales, block-major f32 [K/256 or K/32][ld], block bf of row m at dy[bf * ld + m]

@@ -15,6 +15,8 @@ namespace q2a_blob {
 bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act) {
     memset(&h, 0, sizeof(h));
     // bf16-activation mode: every linear weight dequantized to bf16 [N][K] (no block scales, no splits)
+    // MXFP8 mode: the dequantized weight as e4m3 bytes [N][K] in the W slot, e8m0 scale bytes [N][K/32] in the DX slot
+    const bool mx8 = act == Q2A_ACT_MXFP8;
     h.magic = BLOB_MAGIC; h.version = BLOB_VERSION; h.hp = hp; h.wtype = wtype; h.blk = act ? 0 : blk_of(wtype); h.n_bins = 201;
     h.act = act;
     const dims d = dims_of(hp);
@@ -50,7 +52,8 @@ bool plan(blob_header & h, const q2a_hparams & hp, int wtype, int act) {
             int N, K;
             mat_dims(d, w, N, K);
             uint64_t * a = lo + L_MAT0 + w * A_COUNT;
-            a[A_W] = take((uint64_t) N * K * 2 * kx);
+            a[A_W] = take((uint64_t) N * K * (mx8 ? 1 : 2 * kx));
+            if (mx8) a[A_DX] = take((uint64_t) N * (K / 32));
             if (h.blk) a[A_DX] = take((uint64_t) N * (K / h.blk) * 4);
             if (h.blk && kq_minmax(wtype)) {
                 a[A_DMIN] = take((uint64_t) N * (K / 256) * 4);
@@ -100,7 +103,8 @@ const char * header_problem(const blob_header & h) {
     if (d.D <= 0 || d.D % 128 || d.D != d.H * 64 || d.T <= 0 || d.T % 2 || d.M <= 0 || d.M % 4 || d.T > (1 << 20) ||
         d.M > 4096)
         return "not a q2a weight blob (unsupported shapes)";
-    if ((h.compact != 0 && h.compact != 1) || (h.act != Q2A_ACT_REFERENCE && h.act != Q2A_ACT_BF16) ||
+    if ((h.compact != 0 && h.compact != 1) || (h.act != Q2A_ACT_REFERENCE && h.act != Q2A_ACT_BF16 && h.act != Q2A_ACT_MXFP8) ||
+        (h.act == Q2A_ACT_MXFP8 && h.compact) ||
         q2a_row_size(h.wtype, d.D) == 0 || (blk_of(h.wtype) == 256 && d.D % 256))
         return "not a q2a weight blob (bad type fields)";
     blob_header p;
@@ -163,7 +167,12 @@ void expand_rows(const uint8_t * src, int wtype, int K, int Ntot, int r0, int r1
         const uint8_t * row = src + (size_t) r * rs;
         const int n = dst_row0 + r;
         uint16_t * wr = W + (size_t) n * K;
-        if (act) {   // bf16-activation mode: dequantized weight, RNE to bf16
+        if (act == Q2A_ACT_MXFP8) {   // dequantized weight, MX-quantized per 32 along K: bytes [N][K], scale codes [N][K/32]
+            dequant_row(row, wtype, K, tmp.data());
+            uint8_t * w8 = blob + a[A_W] + (size_t) n * K;
+            uint8_t * sc = blob + a[A_DX] + (size_t) n * (K / 32);
+            for (int b = 0; b < K / 32; ++b) q2a_mx8_quantize_block(tmp.data() + 32 * b, w8 + 32 * b, sc + b);
+        } else if (act) {   // bf16-activation mode: dequantized weight, RNE to bf16
             dequant_row(row, wtype, K, tmp.data());
             for (int k = 0; k < K; ++k) wr[k] = f32_to_bf16(tmp[k]);
         } else if (wtype == Q2A_TYPE_F16) {
@@ -294,6 +303,7 @@ int pack(const char * path, std::vector<uint8_t> & out, int act, bool compact) {
         return Q2A_ERR_UNSUPPORTED;
     }
     if (mf->n_mel_filt != d.M || mf->n_fft_filt != 201) { set_err("bad mel filter shape"); return Q2A_ERR_FORMAT; }
+    if (act == Q2A_ACT_MXFP8 && compact) { set_err("compact blob: no MXFP8 transport form"); return Q2A_ERR_UNSUPPORTED; }
     blob_header h;
     if (!plan(h, hp, wtype, act)) { set_err("too many layers"); return Q2A_ERR_UNSUPPORTED; }
     // the compact transport form is written directly (its size, not the device layout's: 0.38 vs 1.40 GB for Q4_K)
@@ -478,7 +488,7 @@ uint64_t q2a_pack_layout(int wtype, int N, int K, uint64_t off[6]) {
 
 int q2a_pack_linear(const uint8_t * raw, int wtype, int N, int K, std::vector<uint8_t> & out, uint64_t off[6], int act) {
     uint64_t o = q2a_pack_layout(wtype, N, K, off);
-    if (!o) return Q2A_ERR_UNSUPPORTED;
+    if (!o || act == Q2A_ACT_MXFP8) return Q2A_ERR_UNSUPPORTED;   // (MXFP8: the engine's blob alone)
     if (act) {   // bf16 weights: the W section alone (expand_rows reads no other offset)
         for (int i = 0; i < A_COUNT; ++i) off[i] = 0;
         o = ((uint64_t) N * K * 2 + 255) & ~uint64_t(255);

@@ -86,6 +86,14 @@ struct q2a_engine {
     int kx = 1;
     bool bf16 = false;       // bf16-activation mode (Q2A_ACT_BF16): bf16 weights and inter-op activations
     int gblk = 0;            // the GEMM launcher's blk: blk, Q2A_BLK_Q6K for Q6_K weights, or Q2A_BLK_BF16
+    // MXFP8-activation mode (Q2A_ACT_MXFP8): the bf16 contract (act16) with the four weight GEMMs of a block
+    // on q2a_launch_gemm_mx8; bf16 stays false (the key-length kinds, the feature calls and the bf16 opt-in are not its)
+    bool mx8 = false;
+    bool act16() const { return bf16 || mx8; }   // bf16 inter-op activations and the bf16 attention
+    uint8_t * a8D = nullptr;     // MXFP8 operand bytes [rows][D] / [rows][F] and their scale bytes [rows][D/32] / [rows][F/32]
+    uint8_t * a8F = nullptr;
+    uint8_t * scD = nullptr;
+    uint8_t * scF = nullptr;
     uint8_t * blob = nullptr;
     bool own_blob = false;
     int64_t blob_size = 0;
@@ -225,8 +233,9 @@ int engine_adopt_header(q2a_engine * e) {
     e->blk = e->h.blk;
     e->f32 = e->wtype == Q2A_TYPE_F32;
     e->bf16 = e->h.act == Q2A_ACT_BF16;
-    e->kx = e->f32 && !e->bf16 ? 3 : 1;
-    e->gblk = e->bf16 ? Q2A_BLK_BF16 : gblk_of(e->wtype);
+    e->mx8 = e->h.act == Q2A_ACT_MXFP8;
+    e->kx = e->f32 && !e->act16() ? 3 : 1;
+    e->gblk = e->act16() ? Q2A_BLK_BF16 : gblk_of(e->wtype);   // (MXFP8: its own launcher; this one is never called)
     e->TP = ((e->d.T + 63) / 64) * 64;
     return Q2A_OK;
 }
@@ -310,8 +319,11 @@ int reserve(q2a_engine * e, int B) {
     const size_t o_kh = take((size_t) BT * d.D * 2);
     const size_t o_kl = take((size_t) BT * d.D * 2);
     const size_t o_vt = take((size_t) B * d.H * 64 * e->TP * 2);
-    const bool vlo = !e->bf16 && q2a_attention_wants_vlo();
+    const bool vlo = !e->act16() && q2a_attention_wants_vlo();
     const size_t o_vtl = vlo ? take((size_t) B * d.H * 64 * e->TP * 2) : 0;
+    // MXFP8: byte operands and their scale arrays beside the bf16 rows they are quantized from (actD / actF)
+    const size_t o_a8D = e->mx8 ? take((size_t) BT * d.D) : 0, o_a8F = e->mx8 ? take((size_t) BT * d.F) : 0;
+    const size_t o_scD = e->mx8 ? take((size_t) BT * (d.D / 32)) : 0, o_scF = e->mx8 ? take((size_t) BT * (d.F / 32)) : 0;
     size_t o_dyD = 0, o_dyF = 0, o_aD = 0, o_aF = 0, o_att = 0, o_hF = 0, o_part = 0;
     // split-K partials of the small-tile residual GEMMs (O-proj, fc2): up to 4 x [rows][D] f32. Sized for every
     // row count that takes the small-tile path (M <= 26 112 at D = 1280), whatever the capacity, so whether a
@@ -353,6 +365,7 @@ int reserve(q2a_engine * e, int B) {
     e->vt = (q2a_half *) (b + o_vt);
     e->vtl = vlo ? (q2a_half *) (b + o_vtl) : nullptr;
     e->part = split ? (float *) (b + o_part) : nullptr;
+    if (e->mx8) { e->a8D = b + o_a8D; e->a8F = b + o_a8F; e->scD = b + o_scD; e->scF = b + o_scF; }
     if (quant) {
         e->dyD = (float *) (b + o_dyD); e->dyF = (float *) (b + o_dyF);
         e->aextD = (q2a_half *) (b + o_aD); e->aextF = (q2a_half *) (b + o_aF);
@@ -418,7 +431,7 @@ hipEvent_t prof_event(q2a_engine * e) {
 
 // (5: Q8_K with the raw 16-sums for Q2_K weights, q2a_ln_args; q8k_mode: either Q8_K form)
 int ln_mode(const q2a_engine * e) {
-    return e->bf16 ? 4 : e->f32 ? 3 : e->blk == 0 ? 0 : e->blk != 256 ? 2 : kq_sum16(e->wtype) ? 5 : 1;
+    return e->mx8 ? 6 : e->bf16 ? 4 : e->f32 ? 3 : e->blk == 0 ? 0 : e->blk != 256 ? 2 : kq_sum16(e->wtype) ? 5 : 1;
 }
 bool q8k_mode(int mode) { return mode == 1 || mode == 5; }
 
@@ -467,7 +480,7 @@ hipError_t launch_zero_vt_pad(q2a_half * vt, int64_t rows, int T, int TP, hipStr
 // (outputs into the workspace; the hook replaces the output pointers only)
 // the V layout of a block: row-major like K (v_rows) under the reference contract, and under the bf16 contract exactly
 // when the call carries key lengths (its key-length attention reads rows; the plain bf16 encode keeps V^T)
-int v_rows_of(const q2a_engine * e, bool lens) { return !e->bf16 || lens ? 1 : 0; }
+int v_rows_of(const q2a_engine * e, bool lens) { return !e->act16() || lens ? 1 : 0; }
 
 q2a_gemm_args qkv_gemm(const q2a_engine * e, int l, int M, bool lens = false) {
     q2a_gemm_args a = gemm_base(e, l, 0, e->actD, M);
@@ -476,7 +489,7 @@ q2a_gemm_args qkv_gemm(const q2a_engine * e, int l, int M, bool lens = false) {
     a.v_rows = v_rows_of(e, lens);
     // ggml_scale(Q, 1/sqrt(dh)) (:2054); the reference-contract attention also wants log2(e) folded in (its
     // softmax runs in log2 units): one f32 multiply by fl(log2 e)/8, 2^-3 being exact
-    a.qscale = (1.0f / sqrtf((float) (e->d.D / e->d.H))) * (e->bf16 ? 1.0f : Q2A_LOG2E);
+    a.qscale = (1.0f / sqrtf((float) (e->d.D / e->d.H))) * (e->act16() ? 1.0f : Q2A_LOG2E);
     return a;
 }
 
@@ -492,7 +505,7 @@ q2a_gemm_args resid_gemm(const q2a_engine * e, int l, int which, int M, float * 
 // fc1: which epilogue the block launches at M rows under fc1 path `path` (q2a_test_fc1_path), and its arguments
 int fc1_epi(const q2a_engine * e, int M, int path) {
     const int mode = ln_mode(e);
-    if (mode == 0 || mode == 3 || mode == 4) return Q2A_EPI_GELU_H;
+    if (mode == 0 || mode == 3 || mode == 4 || mode == 6) return Q2A_EPI_GELU_H;
     if (q8k_mode(mode) && path == 2 && q2a_gemm_wide_tiles(M, e->d.F, e->gblk) &&
         q2a_gemm_pipe8(gemm_base(e, 0, 2, e->actD, M), e->gblk))   // (never Q6_K: its mode has no 8-phase kernel)
         return Q2A_EPI_GELU_Q8K;
@@ -504,7 +517,7 @@ q2a_gemm_args fc1_gemm(const q2a_engine * e, int l, int M, int epi) {
     const int mode = ln_mode(e);
     q2a_gemm_args a = gemm_base(e, l, 2, e->actD, M);
     a.bias = e->lv<const float *>(l, L_B1);
-    if (mode == 0 || mode == 3 || mode == 4) {
+    if (mode == 0 || mode == 3 || mode == 4 || mode == 6) {   // (6: bf16 rows as mode 4, for the MXFP8 quantizer)
         // F32 weights: the GELU output is exactly fp16 (LUT), so the fc2 operand is [h | 0 | h] (middle third
         // stays zero from the workspace memset) against [W2h | W2h | W2l]
         a.outH = e->actF; a.ldo = (int64_t) d.F * e->kx; a.o_rpg = M; a.o_gstride = 0; a.o_off = 0;
@@ -520,9 +533,48 @@ q2a_gemm_args fc1_gemm(const q2a_engine * e, int l, int M, int epi) {
     return a;
 }
 
+// ---- MXFP8 contract: weight GEMM `which` of layer l on the operand bytes / scales of its K
+hipError_t launch_mx8(const q2a_engine * e, int l, int which, q2a_gemm_args a, int epi, hipStream_t s) {
+    const bool kd = a.K == e->d.D;
+    a.A = (const q2a_half *) (kd ? e->a8D : e->a8F);
+    return q2a_launch_gemm_mx8(a, kd ? e->scD : e->scF, e->blob + e->mat(l, which)[A_DX], epi, s);
+}
+
+// the block under the MXFP8 contract: the bf16 contract's block (plain kind) with every weight-GEMM operand MX-quantized
+// — LN1 / LN2 from the f32 row in registers (mode 6), the bf16 attention output and the bf16 GELU output by the quantizer
+int run_block_mx8(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
+    const dims & d = e->d;
+    const int M = rows.M;
+    if (rows.key_len) { set_err("MXFP8 contract: plain encode only"); return Q2A_ERR_UNSUPPORTED; }
+    if (e->vt_pad_dirty) {   // (q2a_test_attention_bf16 wrote V rows over the V^T image's zero pad columns)
+        LAUNCH(launch_zero_vt_pad(e->vt, (int64_t) e->cap_clips * d.H * 64, d.T, e->TP, s));
+        e->vt_pad_dirty = false;
+    }
+    q2a_ln_args ln{rows.X, M, d.D, e->lv<const float *>(l, L_LN1W), e->lv<const float *>(l, L_LN1B), 6, (q2a_half *) e->a8D,
+                   (float *) e->scD, nullptr, 0};
+    PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln, s));
+    PLAUNCH(e, s, Q2A_PROF_GEMM_QKV, launch_mx8(e, l, 0, qkv_gemm(e, l, M), Q2A_EPI_QKV, s));
+    {
+        q2a_attn_args at{e->qh, e->ql, e->kh, e->kl, e->vt, rows.B, d.T, d.D, d.H, e->TP, e->actD, nullptr, 1};
+        at.vtl = nullptr;
+        at.v_rows = 0;
+        PLAUNCH(e, s, Q2A_PROF_ATTN, launch_attention(at, rows, s));
+    }
+    PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_mx8(e->actD, M, d.D, e->a8D, e->scD, s));
+    PLAUNCH(e, s, Q2A_PROF_GEMM_O, launch_mx8(e, l, 1, resid_gemm(e, l, 1, M, rows.X), Q2A_EPI_RESID, s));
+    ln.g = e->lv<const float *>(l, L_LN2W);
+    ln.b = e->lv<const float *>(l, L_LN2B);
+    PLAUNCH(e, s, Q2A_PROF_LN, q2a_launch_layernorm(ln, s));
+    PLAUNCH(e, s, Q2A_PROF_GEMM_FC1, launch_mx8(e, l, 2, fc1_gemm(e, l, M, Q2A_EPI_GELU_H), Q2A_EPI_GELU_H, s));
+    PLAUNCH(e, s, Q2A_PROF_QUANT, q2a_launch_quant_mx8(e->actF, M, d.F, e->a8F, e->scF, s));
+    PLAUNCH(e, s, Q2A_PROF_GEMM_FC2, launch_mx8(e, l, 3, resid_gemm(e, l, 3, M, rows.X), Q2A_EPI_RESID, s));
+    return Q2A_OK;
+}
+
 // one pre-LN encoder block on the M rows of `rows` (qwen2-whisper.cpp:2014-2155). Everything but the attention is a
 // function of M alone (rows are independent); dy_ld stays the workspace's stride.
 int run_block(q2a_engine * e, int l, const block_rows & rows, hipStream_t s) {
+    if (e->mx8) return run_block_mx8(e, l, rows, s);
     const dims & d = e->d;
     const int M = rows.M;
     float * X = rows.X;
@@ -824,7 +876,7 @@ int hook_rows(q2a_engine * e, encode_kind kind, const int32_t * key_len, int B, 
     const meta_rows dev(e->meta, B);
     rows = block_rows{B, B * e->d.T, e->X, nullptr, nullptr, 0};
     if (kind == ENC_PLAIN) return Q2A_OK;
-    if (e->bf16 && !e->bf16_key_lengths) {
+    if (e->act16() && !e->bf16_key_lengths) {   // (an MXFP8 engine has no opt-in: q2a_test_attention_bf16 alone gets past)
         set_err("key lengths: reference activation contract only (bf16: q2a_set_bf16_key_lengths)");
         return Q2A_ERR_UNSUPPORTED;
     }
@@ -907,7 +959,11 @@ hipError_t launch_gather_rows(const float * X, float * Xp, const int32_t * row_s
 // the key-length kinds, the feature sinks (feats) among them, exist for the reference activation contract, and for the
 // bf16 contract where the engine opted in (q2a_set_bf16_key_lengths)
 int lens_supported(const q2a_engine * e, encode_kind kind, bool feats) {
-    if (kind == ENC_PLAIN || !e->bf16 || e->bf16_key_lengths) return Q2A_OK;
+    if (kind == ENC_PLAIN || !e->act16() || e->bf16_key_lengths) return Q2A_OK;
+    if (e->mx8) {
+        set_err("%s: not served under the MXFP8 activation contract", feats ? "audio features" : kind == ENC_PADDED ? "padded encode" : "variable-length encode");
+        return Q2A_ERR_UNSUPPORTED;
+    }
     set_err("%s: reference activation contract only (bf16: q2a_set_bf16_key_lengths)",
             feats ? "audio features" : kind == ENC_PADDED ? "padded encode" : "variable-length encode");
     return Q2A_ERR_UNSUPPORTED;
@@ -1268,8 +1324,10 @@ int q2a_internal_engine_blob(const q2a_engine * e, const void ** blob, int64_t *
     return Q2A_OK;
 }
 
+static bool known_act(int act) { return act == Q2A_ACT_REFERENCE || act == Q2A_ACT_BF16 || act == Q2A_ACT_MXFP8; }
+
 static int64_t pack_model(const char * path, int act, bool compact, void ** host_blob) {
-    if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("unknown activation mode %d", act); return Q2A_ERR_ARG; }
+    if (!known_act(act)) { set_err("unknown activation mode %d", act); return Q2A_ERR_ARG; }
     std::vector<uint8_t> v;
     const int rc = pack(path, v, act, compact);
     if (rc) return rc;
@@ -1312,7 +1370,7 @@ void q2a_free_host_blob(void * p) { free(p); }
 q2a_engine * q2a_open(const char * model_path, int device) { return q2a_open_ex(model_path, device, Q2A_ACT_REFERENCE); }
 
 q2a_engine * q2a_open_ex(const char * model_path, int device, int act) {
-    if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("unknown activation mode %d", act); return nullptr; }
+    if (!known_act(act)) { set_err("unknown activation mode %d", act); return nullptr; }
     q2a_engine * e = new q2a_engine();
     std::vector<uint8_t> v;
     if (engine_init(e, device) || pack(model_path, v, act)) { q2a_close(e); return nullptr; }
@@ -1408,7 +1466,7 @@ int q2a_get_info(const q2a_engine * e, q2a_info * info) {
     info->n_audio_ctx = e->d.T; info->n_audio_state = e->d.D; info->n_audio_head = e->d.H;
     info->n_audio_layer = e->d.L; info->n_mels = e->d.M; info->wtype = e->wtype; info->n_out = e->d.TO;
     info->device = e->device; info->weight_bytes = e->blob_size; info->workspace_bytes = (int64_t) e->ws_bytes + (int64_t) e->xp_clips * e->d.T * e->d.D * 4;
-    info->act = e->bf16 ? Q2A_ACT_BF16 : Q2A_ACT_REFERENCE;
+    info->act = e->mx8 ? Q2A_ACT_MXFP8 : e->bf16 ? Q2A_ACT_BF16 : Q2A_ACT_REFERENCE;
     info->reserved = 0;
     return Q2A_OK;
 }
@@ -1913,6 +1971,18 @@ int q2a_test_linear(q2a_engine * e, int layer, int which, const float * x, int M
     int N, K;
     mat_dims(d, which, N, K);
     q2a_half * A = nullptr;
+    if (e->mx8) {   // x -> bf16 rows -> the quantizer -> the block-scaled GEMM with a plain fl32(acc) store
+        const bool kd = K == d.D;
+        q2a_half * rows16 = kd ? e->actD : e->actF;
+        const int64_t n = (int64_t) M * K;
+        hipLaunchKernelGGL(k_to_bf16, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, s, x, rows16, n);
+        LAUNCH(hipGetLastError());
+        LAUNCH(q2a_launch_quant_mx8(rows16, M, K, kd ? e->a8D : e->a8F, kd ? e->scD : e->scF, s));
+        q2a_gemm_args a = gemm_base(e, layer, which, nullptr, M);
+        a.outF = y; a.ldo = N;
+        LAUNCH(launch_mx8(e, layer, which, a, Q2A_EPI_STORE_F, s));
+        return Q2A_OK;
+    }
     if ((rc = stage_operand(e, which, x, M, e->dy_ld, s, &A))) return rc;
     q2a_gemm_args a = gemm_base(e, layer, which, A, M);
     a.outF = y; a.ldo = N;
@@ -1954,6 +2024,7 @@ int q2a_test_gemm_regime(q2a_engine * e, int which, int epi, int M) {
 int q2a_test_gemm_epi(q2a_engine * e, int layer, int which, int epi, const float * x, int M, void * const * out, int ld,
                       void * stream) {
     if (!e || layer < 0 || layer >= e->d.L || which < 0 || which > 3 || M <= 0 || !x || !out || !out[0]) return Q2A_ERR_ARG;
+    if (e->mx8) { set_err("q2a_test_gemm_epi: not served under the MXFP8 activation contract"); return Q2A_ERR_UNSUPPORTED; }
     const bool q8k = epi == Q2A_EPI_GELU_Q8K;
     if (q8k && (ld < M || ld % 256 || !out[1] || !out[2])) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
@@ -2024,6 +2095,7 @@ int q2a_test_block_varlen(q2a_engine * e, int layer, float * x, int n_clips, con
 
 int q2a_test_block_taps(q2a_engine * e, int layer, float * x, int n_clips, void * const * taps, void * stream) {
     if (!e || !taps) return Q2A_ERR_ARG;
+    if (e->mx8) { set_err("q2a_test_block_taps: not served under the MXFP8 activation contract"); return Q2A_ERR_UNSUPPORTED; }
     for (int i = 0; i < 4; ++i) e->taps[i] = taps[i];
     const int rc = test_block(e, ENC_PLAIN, layer, x, n_clips, nullptr, stream);
     for (int i = 0; i < 4; ++i) e->taps[i] = nullptr;
@@ -2112,10 +2184,15 @@ int q2a_test_operand(q2a_engine * e, int producer, int mode, const void * x, int
     if (quant && (!dy || (q8k_mode(mode) && !aext))) return Q2A_ERR_ARG;
     if (q8k_mode(mode) && K % 256) return Q2A_ERR_ARG;
     if (mode == 2 && K % 32) return Q2A_ERR_ARG;
+    if (mode == 6 && (K % 32 || !dy || (producer != Q2A_OPERAND_LN && producer != Q2A_OPERAND_QUANT_H16))) return Q2A_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
+    if (mode == 6 && producer == Q2A_OPERAND_QUANT_H16) {   // MXFP8 of bf16 rows: bytes to out, scale bytes [M][K/32] to dy
+        LAUNCH(q2a_launch_quant_mx8((const q2a_half *) x, M, K, (uint8_t *) out, (uint8_t *) dy, s));
+        return Q2A_OK;
+    }
     if (producer == Q2A_OPERAND_LN) {
-        if (mode < 0 || mode > 5 || !g || !b || K % 4 || K > 2048) return Q2A_ERR_ARG;
+        if (mode < 0 || mode > 6 || !g || !b || K % 4 || K > 2048) return Q2A_ERR_ARG;
         q2a_ln_args ln{(const float *) x, M, K, g, b, mode, (q2a_half *) out, dy, (q2a_half *) aext, ld};
         LAUNCH(q2a_launch_layernorm(ln, s));
     } else if (producer == Q2A_OPERAND_QUANT_F32 || producer == Q2A_OPERAND_QUANT_H16) {
@@ -2140,7 +2217,7 @@ static int test_attention(q2a_engine * e, encode_kind kind, const float * q, con
                           const int32_t * key_len, float * out, void * stream) {
     if (!e || n_clips <= 0 || (kind != ENC_PLAIN && !key_len) || (kind == ENC_PACKED && (!q || !k || !v || !out))) return Q2A_ERR_ARG;
     // (the reference contract's kernels, whatever q2a_set_bf16_key_lengths says: the bf16 ones have q2a_test_attention_bf16)
-    if (e->bf16 && kind != ENC_PLAIN) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
+    if (e->act16() && kind != ENC_PLAIN) { set_err("key lengths: reference activation contract only"); return Q2A_ERR_UNSUPPORTED; }
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = call_stream(stream);
     int rc = reserve(e, n_clips);
@@ -2234,6 +2311,7 @@ q2a_projector * q2a_projector_open(const char * path, int device) { return q2a_p
 
 // Q2A_ACT_BF16: the weight as a bf16 engine's linears (q2a_pack_linear with act), the bf16 x bf16 GEMM, no block scales
 q2a_projector * q2a_projector_open_ex(const char * path, int device, int act) {
+    if (act == Q2A_ACT_MXFP8) { set_err("projector: no MXFP8 activation contract (Q2A_ERR_UNSUPPORTED)"); return nullptr; }
     if (act != Q2A_ACT_REFERENCE && act != Q2A_ACT_BF16) { set_err("projector: unknown activation mode %d", act); return nullptr; }
     const bool bf16 = act == Q2A_ACT_BF16;
     char err[256] = {0};

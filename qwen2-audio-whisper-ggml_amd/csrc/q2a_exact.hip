@@ -406,6 +406,12 @@ __device__ __forceinline__ void rownorm_rows(const float * __restrict__ X, int M
         }
         q2a_half * o = outH + (int64_t) row * (MODE == 3 ? 3 * D : D) + 4 * c;
         const int m = row / nseg, seg = row - m * nseg;
+        if constexpr (MODE == 6) {
+            // MXFP8 operand from the row in registers: a 32-block is the float4 of 8 consecutive lanes (D % 32 == 0, so a
+            // block's lanes are all here or all past the row's end); bytes [M][D], scale bytes [M][D/32] in the dy slot
+            quant_mx8_block(y, lane, (uint8_t *) outH + (int64_t) row * D + 4 * c, (uint8_t *) dy + (int64_t) row * (D / 32) + c / 8);
+            continue;
+        }
         if (MODE == 0) {
             o[0] = (_Float16) y.x; o[1] = (_Float16) y.y; o[2] = (_Float16) y.z; o[3] = (_Float16) y.w;
         } else if (MODE == 4) {   // bf16-activation mode: RNE to bf16, bits in the fp16-typed slots
@@ -830,10 +836,13 @@ hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s) {
 hipError_t q2a_launch_layernorm(const q2a_ln_args & a, hipStream_t s) {
     if (a.D % 4 != 0 || a.D > 2048) return hipErrorInvalidValue;
     if ((a.mode == 1 || a.mode == 5) && a.D % 256) return hipErrorInvalidValue;
-    if (a.mode == 2 && a.D % 32) return hipErrorInvalidValue;
+    if ((a.mode == 2 || a.mode == 6) && a.D % 32) return hipErrorInvalidValue;
     const dim3 grid((a.M + 3) / 4), blk(256), grid8((a.M + 7) / 8), blk8(512);
     const bool d1280 = a.D == 1280;   // the model width: compile-time row length (k_rownorm NBQ = 5)
-    if (a.mode == 0 && d1280)
+    if (a.mode == 6 && d1280)
+        hipLaunchKernelGGL((k_rownorm5<6, true>), grid8, blk8, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
+    else if (a.mode == 6) hipLaunchKernelGGL((k_rownorm<6, true>), grid, blk, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
+    else if (a.mode == 0 && d1280)
         hipLaunchKernelGGL((k_rownorm5<0, true>), grid8, blk8, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);
     else if (a.mode == 4 && d1280)
         hipLaunchKernelGGL((k_rownorm5<4, true>), grid8, blk8, 0, s, a.X, a.M, a.D, a.g, a.b, a.outH, a.dy, a.aext, 1, a.dy_ld);

@@ -9,6 +9,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -79,6 +80,45 @@ typedef struct {
 uint16_t q2a_fp32_to_fp16(float f);   // IEEE binary16, round-to-nearest-even (== F16C _cvtss_sh(x, 0))
 float    q2a_fp16_to_fp32(uint16_t h);
 size_t   q2a_row_size(int ggml_type, int64_t ncols);   // bytes of one row (ggml_row_size)
+
+// OCP MXFP8 of 32 consecutive finite values: one e8m0 scale code and 32 e4m3fn bytes. amax = max|x|;
+// amax == 0: code 127; else code = max(exponent field of amax - 8, 0), i.e. floor(log2 amax) - 8 + 127 clamped at 0 (the
+// upper clamp at 254 cannot bind: a finite f32 gives at most 246). Elements: x * 2^(127 - code) (exact), clamped to
+// +-448 (the values of (448, 512) saturate there; below 464 they would round to 448 anyway), rounded to nearest even.
+// The device kernels (k_rownorm mode 6, k_quant_mx8) run the same operations; this is the packer's form.
+static inline uint8_t q2a_e4m3_rne(float v) {   // |v| <= 448, finite
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    const uint8_t sign = (uint8_t) ((u >> 24) & 0x80);
+    u &= 0x7FFFFFFFu;
+    float a;
+    memcpy(&a, &u, 4);
+    if (a < 0.015625f) {   // below 2^-6, the smallest normal: subnormal codes in units of 2^-9 (a * 512 is exact)
+        const float t = a * 512.0f + 12582912.0f;   // + 1.5 * 2^23: the f32 add rounds to an integer, to nearest even
+        uint32_t q;
+        memcpy(&q, &t, 4);
+        return (uint8_t) (sign | (q & 0xF));        // 0 .. 8 (8 = the smallest normal)
+    }
+    const uint32_t r = u + 0x7FFFFu + ((u >> 20) & 1u);   // nearest even at 3 mantissa bits
+    return (uint8_t) (sign | (((r >> 20) - (120u << 3)) & 0x7F));   // rebias 127 -> 7
+}
+static inline void q2a_mx8_quantize_block(const float * x, uint8_t * q, uint8_t * scale) {
+    float amax = 0.0f;
+    for (int i = 0; i < 32; ++i) { const float a = x[i] < 0 ? -x[i] : x[i]; if (a > amax) amax = a; }
+    uint32_t u;
+    memcpy(&u, &amax, 4);
+    const int ef = (int) (u >> 23);
+    const int code = amax == 0.0f ? 127 : (ef > 8 ? ef - 8 : 0);
+    const uint32_t iu = (uint32_t) (254 - code) << 23;
+    float inv;
+    memcpy(&inv, &iu, 4);
+    *scale = (uint8_t) code;
+    for (int i = 0; i < 32; ++i) {
+        float v = x[i] * inv;
+        v = v > 448.0f ? 448.0f : v < -448.0f ? -448.0f : v;
+        q[i] = q2a_e4m3_rne(v);
+    }
+}
 
 // ---- deterministic synthetic inputs (SURVEY.md §8d "Synthetic inputs") ----------------------------
 uint64_t q2a_splitmix64(uint64_t x);

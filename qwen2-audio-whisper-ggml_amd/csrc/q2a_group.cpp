@@ -170,6 +170,7 @@ int q2a_group_split(int n_clips, int n_devices, int i, int * first, int * count)
 
 q2a_group * q2a_group_open(const char * model_path, const int * devices, int n_devices, int act) {
     if (!model_path || n_devices < 0 || (n_devices > 0 && !devices)) { gerr("invalid arguments"); return nullptr; }
+    if (act == Q2A_ACT_MXFP8) { gerr("group: no MXFP8 activation contract (its blob has no transport form)"); return nullptr; }
     std::vector<int> dev;
     if (!group_devices(devices, n_devices, -1, dev)) return nullptr;
     const int n = (int) dev.size();
@@ -221,6 +222,11 @@ q2a_group * q2a_group_open_with(q2a_engine * base, const int * devices, int n_de
     int bdev = -1;
     if (!base || n_devices < 0 || (n_devices > 0 && !devices)) { gerr("invalid arguments"); return nullptr; }
     if (q2a_internal_engine_blob(base, &src, &nb, &bdev) != Q2A_OK) return nullptr;
+    q2a_info bi;
+    if (q2a_get_info(base, &bi) == Q2A_OK && bi.act == Q2A_ACT_MXFP8) {   // as q2a_group_open: groups do not serve it
+        gerr("group: no MXFP8 activation contract");
+        return nullptr;
+    }
     std::vector<int> dev;
     if (!group_devices(devices, n_devices, bdev, dev)) return nullptr;
     int root = -1;

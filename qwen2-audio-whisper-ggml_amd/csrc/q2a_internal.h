@@ -170,6 +170,15 @@ q2a_gemm_plan q2a_gemm_plan_of(const q2a_gemm_args & a, int epi, int blk, int cu
 // the same for the arguments as a caller of q2a_launch_gemm holds them (its checks and split decision applied first)
 q2a_gemm_plan q2a_gemm_plan_for(const q2a_gemm_args & a, int epi, int blk);
 
+// ---- MXFP8 contract (q2a_gemm_mx8.hip) ------------------------------------------------------------
+// The block-scaled GEMM: A = e4m3 bytes [M][K] with e8m0 scale bytes [M][K/32], W = the same [N][K] / [N][K/32];
+// K % 128 == 0, N % 128 == 0. Of q2a_gemm_args it reads A / W (as bytes; lda = ldw = K), M, N, K, bias and the fields of
+// the epilogue: Q2A_EPI_QKV (bf16 Q.qscale / K rows, bf16 V^T image; qh, kh, vt, D, H, T, TP, qscale), Q2A_EPI_RESID (outF,
+// ldo, in place), Q2A_EPI_GELU_H (outH bf16, ldo, gelu_tab), Q2A_EPI_STORE_F (outF = fl32(acc), ldo).
+hipError_t q2a_launch_gemm_mx8(const q2a_gemm_args & a, const uint8_t * a_scale, const uint8_t * w_scale, int epi, hipStream_t s);
+// bf16 rows X [M][K] -> MXFP8 operand: bytes out [M][K], scale bytes sc [M][K/32]; K % 32 == 0
+hipError_t q2a_launch_quant_mx8(const q2a_half * X, int M, int K, uint8_t * out, uint8_t * sc, hipStream_t s);
+
 struct q2a_attn_args {
     const q2a_half *qh, *ql, *kh, *kl, *vt;
     int n_clips, T, D, H, TP;
@@ -249,6 +258,8 @@ hipError_t q2a_launch_mel_ingest(const q2a_mel_ingest_args & a, hipStream_t s);
 //   4: bf16 RNE [M][D]                 (bf16-activation mode)
 //   5: mode 1 with aext = the block's sixteen raw 16-sums instead of eight (hi, lo) pairs (Q2_K weights); codes and dy
 //      are mode 1's bit for bit. The same value selects it in q2a_quant_args and q2a_pool_pack_args.
+//   6: OCP MXFP8, D % 32 == 0: outH = the e4m3 bytes [M][D], dy = the e8m0 scale bytes [M][D/32],
+//      row-major (dy_ld and aext unused)    (MXFP8-activation mode)
 struct q2a_ln_args {
     const float * X;
     int M, D;

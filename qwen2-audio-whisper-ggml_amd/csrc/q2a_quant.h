@@ -264,4 +264,31 @@ __device__ __forceinline__ void quant_q80_block(float4 y, int lane, q2a_half * c
 // Rows are [M*nseg][D] (a quantizer run splits a long row into nseg segments of D); the block scales are
 // written block-major: block bf of logical row m (= row / nseg) goes to dy[bf * ld + m] (aext likewise x16).
 
+// OCP MXFP8 (the host form is q2a_mx8_quantize_block). amax = the 32-block's max |x| (every lane of the
+// block holds it): the e8m0 code, and the exact factor 2^(127 - code) the elements are multiplied by.
+__device__ __forceinline__ uint32_t mx8_code(float amax) {
+    const uint32_t ef = __float_as_uint(amax) >> 23;
+    return amax == 0.0f ? 127u : (ef > 8u ? ef - 8u : 0u);
+}
+__device__ __forceinline__ float mx8_inv(uint32_t code) { return __uint_as_float((254u - code) << 23); }
+// four scaled values -> four e4m3fn bytes (RNE), element 0 in the low byte. Clamped to +-448 first: that is the
+// saturation (what lies in (448, 464) rounds to 448 by itself), whatever the conversion does past the format's range
+__device__ __forceinline__ uint32_t mx8_pack4(float a, float b, float c, float d, float inv) {
+    auto cl = [&](float v) { return fminf(fmaxf(v * inv, -448.0f), 448.0f); };
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(cl(a), cl(b), 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(cl(c), cl(d), r, true);
+    return (uint32_t) r;
+}
+// one lane's float4 of a row whose 32-blocks are 8 consecutive lanes (k_rownorm's layout): bytes to out8, the block's
+// scale code from its first lane to sc
+__device__ __forceinline__ void quant_mx8_block(float4 y, int lane, uint8_t * out8, uint8_t * sc) {
+    float amax = fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w)));
+    amax = fmaxf(amax, __shfl_xor(amax, 1));
+    amax = fmaxf(amax, __shfl_xor(amax, 2));
+    amax = fmaxf(amax, __shfl_xor(amax, 4));
+    const uint32_t code = mx8_code(amax);
+    *(uint32_t *) out8 = mx8_pack4(y.x, y.y, y.z, y.w, mx8_inv(code));
+    if ((lane & 7) == 0) *sc = (uint8_t) code;
+}
+
 }  // namespace

@@ -72,6 +72,11 @@ _KINDS = {"plain": ENCODE_PLAIN, "padded": ENCODE_PADDED, "varlen": ENCODE_VARLE
 # activation contracts (include/q2a_encoder.h)
 ACT_REFERENCE = 0
 ACT_BF16 = 1
+# the bf16 contract with the weight GEMMs on OCP MXFP8 operands. Plain encode kinds only: the padded /
+# variable-length kinds, audio_features*, inputs_embeds* and test_gemm_epi raise rc -6, set_bf16_key_lengths rc -4;
+# Projector, Group and pack_model(compact=True) refuse it. test_operand takes mode 6 (OPERAND_LN on f32 rows,
+# OPERAND_QUANT_H16 on bf16 rows): out_ptr the e4m3 bytes [M][K], dy_ptr the e8m0 scale bytes [M][K/32]
+ACT_MXFP8 = 2
 
 # element types of a feature destination (include/q2a_encoder.h, q2a_feat_dst)
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2

@@ -21,7 +21,7 @@ struct cli {
     std::string model = "models/ggml-base.en.bin";
     std::vector<std::string> files;
     int threads = 4, offset_ms = 0, duration_ms = 0, reps = 1, device = 0, processors = 1, gpus = 0;
-    bool no_prints = false, batch = false, long_audio = false, bf16 = false, device_set = false;
+    bool no_prints = false, batch = false, long_audio = false, bf16 = false, mxfp8 = false, device_set = false;
     std::string dump, mel;
 };
 
@@ -46,6 +46,8 @@ void usage(const char * argv0) {
             "                              weights, a host thread per device)\n"
             "  -bf16,     --bf16-act       bf16-activation contract (Q2A_ACT_BF16, BASELINE configs[4]); not the\n"
             "                              reference's numerics: see DESIGN.md\n"
+            "  -mxfp8,    --mxfp8-act      MXFP8 activation contract (Q2A_ACT_MXFP8: block-scaled fp8 weight GEMMs,\n"
+            "                              DESIGN.md 2c); one device, no -b over several\n"
             "  -np,       --no-prints      only print results\n",
             argv0);
 }
@@ -69,6 +71,7 @@ bool parse(int argc, char ** argv, cli & c) {
         else if (a == "-mel" || a == "--mel-file") { if (!(v = next())) return false; c.mel = v; }
         else if (a == "-b" || a == "--batch") c.batch = true;
         else if (a == "-bf16" || a == "--bf16-act") c.bf16 = true;
+        else if (a == "-mxfp8" || a == "--mxfp8-act") c.mxfp8 = true;
         else if (a == "-la" || a == "--long-audio") c.long_audio = true;
         else if (a == "-np" || a == "--no-prints") c.no_prints = true;
         else if (a[0] == '-' && a != "-") { fprintf(stderr, "error: unknown argument: %s\n", a.c_str()); return false; }
@@ -117,7 +120,9 @@ void quiet(enum ggml_log_level, const char *, void *) {}
 int main(int argc, char ** argv) {
     cli c;
     if (!parse(argc, argv, c)) { usage(argv[0]); return 1; }
+    if (c.bf16 && c.mxfp8) { fprintf(stderr, "error: -bf16 and -mxfp8 exclude each other\n"); return 1; }
     if (c.bf16) setenv("Q2A_ACT", "bf16", 1);   // the whisper_* paths read it in whisper_init
+    if (c.mxfp8) setenv("Q2A_ACT", "mxfp8", 1);
     if (c.no_prints) whisper_log_set(quiet, nullptr);
     whisper_context_params cp = whisper_context_default_params();
     cp.gpu_device = c.device;
@@ -154,7 +159,8 @@ int main(int argc, char ** argv) {
         // more than one device: a q2a_group over the context's loaded weights (contiguous clip ranges, one host thread
         // per device; -ng N, or every visible device when -dev was not given); else the context's own engine
         q2a_engine * e = q2a_whisper_context_engine(ctx);
-        const int ndev = c.gpus > 0 ? c.gpus : c.device_set ? 1 : q2a_device_count();
+        // (-mxfp8 stays on the -dev device unless -ng asks for a group, which that contract refuses)
+        const int ndev = c.gpus > 0 ? c.gpus : (c.device_set || c.mxfp8) ? 1 : q2a_device_count();
         q2a_group * grp = nullptr;
         if (c.gpus > 0 || ndev > 1) {   // (an explicit -ng always takes the group path, -ng 1 included)
             std::vector<int> devs{c.device};
