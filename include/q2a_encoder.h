@@ -253,6 +253,48 @@ int q2a_encode_device_mel(q2a_engine * e, int kind, const float * mel_dev, int64
 int q2a_encode_host_mel(q2a_engine * e, int kind, const float * const * mel, const int32_t * n_len, const int32_t * seek,
                         const int32_t * key_len, int n_clips, float * out_host, int32_t * out_len, int32_t * status);
 
+/* ---- native-rate PCM: resampled to 16 kHz mono f32 on the device ----------------------------------
+ * Every entry point above takes 16 kHz mono f32. These calls produce it from audio as it arrives: int16 or f32, one or
+ * two interleaved channels, 8 .. 192 kHz. Value contract, for a clip of n_in frames at `rate` Hz:
+ *   x[k]   the f32 value of frame k: s16 mono float(s) / 32768, s16 stereo float(l + r) / 65536 (q2a_read_wav's values
+ *          bit for bit), f32 mono the value, f32 stereo fl32(0.5f * (l + r)); 0 outside 0 <= k < n_in
+ *   L / M  = 16000 / rate reduced; n_out = (n_in * 16000 + rate - 1) / rate; output n sits at input time t_n = n M / L
+ *   rate == 16000:  y[n] = x[n] (conversion and downmix only)
+ *   otherwise       y[n] = sum over integer k with |s (k - t_n)| < Z of g(k - t_n) x[k],  s = min(1, L / M),
+ *                   g(t) = rho s sinc(rho s t) I0(beta sqrt(1 - (s t / Z)^2)) / I0(beta),  sinc(u) = sin(pi u) / (pi u),
+ *                   Z = 64, beta = 14.769656459379492, rho = 0.9475937167399596 (a Kaiser-windowed sinc)
+ * The coefficients are computed on the host in double and rounded once to f32; the kernel sums the f32 products in f32
+ * with FMAs in ascending k, one fixed order per output whatever else is in the batch. Supported: 8000 <= rate <= 192000
+ * with reduced L <= 640 (8, 11.025, 12, 16, 22.05, 24, 32, 44.1, 48, 88.2, 96, 176.4, 192 kHz among them); any other rate
+ * is Q2A_ERR_UNSUPPORTED. Serves engines of every activation contract. */
+enum { Q2A_PCM_S16 = 0, Q2A_PCM_F32 = 1 };
+typedef struct {
+    const void * data;   /* device; interleaved frames, aligned to the sample width */
+    int64_t n_frames;    /* >= 0 */
+    int32_t rate;        /* Hz */
+    int16_t format;      /* Q2A_PCM_* */
+    int16_t channels;    /* 1 or 2 */
+} q2a_pcm_src;
+
+/* n_out of n_frames frames at `rate` (host arithmetic, also exported from libq2a_host.so). Q2A_ERR_ARG for a negative
+ * n_frames or one whose product with 16000 leaves int64, Q2A_ERR_UNSUPPORTED for a rate outside the set above. */
+int64_t q2a_resampled_length(int64_t n_frames, int rate);
+
+/* src: host array [n_clips]. Writes clip c's n_out[c] samples to pcm_dev + c * pcm_stride (the layout
+ * q2a_encode_device and the others read) and n_samples_out[c] = n_out[c] (host, int32). Samples behind n_out[c] are not
+ * written. One launch per group of clips that share (L, M), the 16 kHz clips through a conversion kernel; the
+ * coefficient bank of a rate is built on its first use and kept in device memory (counted in
+ * q2a_info.workspace_bytes). Every check is made before anything is launched or written: Q2A_ERR_ARG for NULL or
+ * misaligned data with n_frames > 0, n_frames < 0, channels outside 1 .. 2, an unknown format, n_out > pcm_stride,
+ * n_out > INT32_MAX, n_clips < 0, NULL src / pcm_dev / n_samples_out with n_clips > 0; Q2A_ERR_UNSUPPORTED for the rate.
+ * Asynchronous on `stream` like the device entry points (NULL: stream 0). */
+int q2a_ingest_device(q2a_engine * e, const q2a_pcm_src * src, int n_clips, float * pcm_dev, int64_t pcm_stride,
+                      int32_t * n_samples_out, void * stream);
+/* Host convenience (synchronous): src[c].data are host pointers here; the clips are staged through the engine's staging
+ * buffers in chunks, ingested, and the 16 kHz PCM copied back, pcm_out[c] holding >= n_out[c] floats. The bytes are
+ * q2a_ingest_device's. */
+int q2a_ingest_host(q2a_engine * e, const q2a_pcm_src * src, int n_clips, float * const * pcm_out, int32_t * n_samples_out);
+
 /* ---- one process, several GPUs (ncclCommInitAll + a host thread per device) -----------------------
  * Replaces the single-device choice of whisper_backend_init_gpu (qwen2-whisper.cpp:1217-1279) for batches of
  * independent clips, and is what whisper_full_parallel (declared, never defined, include/qwen2-whisper.h:464-469)

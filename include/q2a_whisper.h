@@ -196,6 +196,11 @@ int q2a_whisper_encode_long(struct whisper_context * ctx, const float * samples,
  * *left / *right (may be NULL). Returns 0, or -1 (unreadable / not RIFF-WAVE) / -2 (unsupported format). */
 int q2a_read_wav(const char * path, float ** pcm, int64_t * n_samples, float ** left, float ** right);
 void q2a_wav_free(void * p);
+/* The same chunk walk without the 16 kHz rule and without a conversion: 16-bit PCM of any rate, mono or stereo, as the
+ * file holds it. *frames is malloc'ed (free with q2a_wav_free) and holds *n_frames interleaved frames of *channels
+ * samples (a truncated data chunk gives the whole frames that are there); *rate in Hz. The input of q2a_ingest_host
+ * (include/q2a_encoder.h). Same return codes. Also exported from libq2a_host.so. */
+int q2a_read_wav_native(const char * path, int16_t ** frames, int64_t * n_frames, int * channels, int * rate);
 
 #ifdef __cplusplus
 }

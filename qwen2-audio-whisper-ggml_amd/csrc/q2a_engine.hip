@@ -7,6 +7,7 @@
 // for the batch size, so a batch is ~11 launches per layer on one stream (capturable into a hipGraph).
 #include "q2a_encoder.h"
 #include "q2a_blob.h"
+#include "q2a_resample.h"
 
 #include <algorithm>
 #include <cmath>
@@ -148,6 +149,20 @@ struct q2a_engine {
     // q2a_test_block_taps: device buffers receiving the GEMM A operands of one block (LN1 -> QKV, attention -> O,
     // LN2 -> fc1, GELU -> fc2) as they were fed to the MFMA, for the per-layer divergence trace (NULL: off)
     void * taps[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    // native-rate ingestion (q2a_ingest_*): the coefficient bank and the workgroup geometry of every rate seen so far
+    // (built on first use), and the clip records of a call (device + pinned, grown on demand; ing_evt: the last upload)
+    struct ingest_rate { q2a_ingest_geom g; float * bank; size_t bytes; };
+    std::vector<ingest_rate> ing_rates;
+    q2a_ingest_clip * ing_meta = nullptr;
+    q2a_ingest_clip * ing_meta_host = nullptr;
+    int ing_cap = 0;
+    hipEvent_t ing_evt = nullptr;
+    size_t ingest_bytes() const {
+        size_t n = (size_t) ing_cap * sizeof(q2a_ingest_clip);
+        for (const auto & r : ing_rates) n += r.bytes;
+        return n;
+    }
 
     // optional per-kernel-class timing with HIP events on the launch stream (q2a_profile_*)
     bool prof = false;
@@ -1455,6 +1470,10 @@ void q2a_close(q2a_engine * e) {
     for (auto & r : e->pending) { (void) hipEventDestroy(r.a); (void) hipEventDestroy(r.b); }
     for (auto ev : e->pool) (void) hipEventDestroy(ev);
     if (e->own_blob && e->blob) (void) hipFree(e->blob);
+    for (auto & r : e->ing_rates) (void) hipFree(r.bank);
+    if (e->ing_meta) (void) hipFree(e->ing_meta);
+    if (e->ing_meta_host) (void) hipHostFree(e->ing_meta_host);
+    if (e->ing_evt) (void) hipEventDestroy(e->ing_evt);
     if (e->frange) (void) hipFree(e->frange);
     if (e->meta_evt) (void) hipEventDestroy(e->meta_evt);
     if (e->stream) (void) hipStreamDestroy(e->stream);
@@ -1465,7 +1484,7 @@ int q2a_get_info(const q2a_engine * e, q2a_info * info) {
     if (!e || !info) return Q2A_ERR_ARG;
     info->n_audio_ctx = e->d.T; info->n_audio_state = e->d.D; info->n_audio_head = e->d.H;
     info->n_audio_layer = e->d.L; info->n_mels = e->d.M; info->wtype = e->wtype; info->n_out = e->d.TO;
-    info->device = e->device; info->weight_bytes = e->blob_size; info->workspace_bytes = (int64_t) e->ws_bytes + (int64_t) e->xp_clips * e->d.T * e->d.D * 4;
+    info->device = e->device; info->weight_bytes = e->blob_size; info->workspace_bytes = (int64_t) e->ws_bytes + (int64_t) e->xp_clips * e->d.T * e->d.D * 4 + (int64_t) e->ingest_bytes();
     info->act = e->mx8 ? Q2A_ACT_MXFP8 : e->bf16 ? Q2A_ACT_BF16 : Q2A_ACT_REFERENCE;
     info->reserved = 0;
     return Q2A_OK;
@@ -1897,6 +1916,157 @@ int q2a_pcm_to_mel(q2a_engine * e, const float * pcm, int n_samples, float * mel
         mel_out[i] = (float) ((v + 4.0) / 4.0);
     }
     *n_len_out = n_len;
+    return Q2A_OK;
+}
+
+// ---- native-rate PCM ingestion (include/q2a_encoder.h; kernels: q2a_ingest.hip) ----------------------------------------
+// Every argument check of q2a_ingest_device / _host, and each clip's rate plan and output length. stride < 0: no
+// destination stride to hold against (the host call's pcm_out rows).
+static int ingest_check(const q2a_engine * e, const q2a_pcm_src * src, int n_clips, const void * dst, int64_t stride,
+                        const int32_t * n_samples_out, std::vector<q2a_rs_plan> & plans, std::vector<int32_t> & lens) {
+    if (!e || n_clips < 0 || (n_clips > 0 && (!src || !dst || !n_samples_out))) { set_err("invalid arguments"); return Q2A_ERR_ARG; }
+    plans.resize(n_clips);
+    lens.resize(n_clips);
+    for (int c = 0; c < n_clips; ++c) {
+        const q2a_pcm_src & k = src[c];
+        if (k.format != Q2A_PCM_S16 && k.format != Q2A_PCM_F32) { set_err("ingest: clip %d: unknown sample format %d", c, k.format); return Q2A_ERR_ARG; }
+        if (k.channels < 1 || k.channels > 2) { set_err("ingest: clip %d: %d channels (1 or 2)", c, k.channels); return Q2A_ERR_ARG; }
+        const uintptr_t width = k.format == Q2A_PCM_S16 ? 2 : 4;
+        if (k.n_frames < 0 || (k.n_frames > 0 && (!k.data || (uintptr_t) k.data % width))) {
+            set_err("ingest: clip %d: NULL or misaligned data, or a negative frame count", c);
+            return Q2A_ERR_ARG;
+        }
+        if (!q2a_rs_plan_of(k.rate, plans[c])) { set_err("ingest: clip %d: %d Hz is not a supported rate", c, k.rate); return Q2A_ERR_UNSUPPORTED; }
+        const int64_t n = q2a_rs_out_len(k.n_frames, k.rate);
+        if (n < 0 || n > INT32_MAX || (stride >= 0 && n > stride)) {
+            set_err("ingest: clip %d: %lld output samples do not fit (stride %lld)", c, (long long) n, (long long) stride);
+            return Q2A_ERR_ARG;
+        }
+        lens[c] = (int32_t) n;
+    }
+    return Q2A_OK;
+}
+
+// the engine's bank and geometry of a rate, built on first use: index into e->ing_rates
+static int ingest_rate(q2a_engine * e, const q2a_rs_plan & p, int & idx) {
+    for (idx = 0; idx < (int) e->ing_rates.size(); ++idx)
+        if (e->ing_rates[idx].g.L == p.L && e->ing_rates[idx].g.M == p.M) return Q2A_OK;
+    q2a_engine::ingest_rate r{};
+    if (!q2a_ingest_geom_of(p.L, p.M, p.H, p.T, r.g)) { set_err("ingest: no kernel geometry for L = %d, M = %d", p.L, p.M); return Q2A_ERR_UNSUPPORTED; }
+    std::vector<float> bank;
+    q2a_rs_bank(p, bank);
+    r.bytes = bank.size() * sizeof(float);
+    if (hipMalloc((void **) &r.bank, r.bytes) != hipSuccess) { (void) hipGetLastError(); set_err("ingest: coefficient bank allocation failed"); return Q2A_ERR_OOM; }
+    if (hipMemcpy(r.bank, bank.data(), r.bytes, hipMemcpyHostToDevice) != hipSuccess) { (void) hipFree(r.bank); set_err("ingest: coefficient bank upload failed"); return Q2A_ERR_HIP; }
+    e->ing_rates.push_back(r);
+    return Q2A_OK;
+}
+
+// the checked clips (device data) onto dst rows of `stride` floats: the records of the call uploaded once, grouped by
+// rate, then one launch per group
+static int ingest_run(q2a_engine * e, const q2a_pcm_src * src, int n_clips, const std::vector<q2a_rs_plan> & plans,
+                      const std::vector<int32_t> & lens, float * dst, int64_t stride, hipStream_t s) {
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<int> group(n_clips, -2);   // -1: the 16 kHz conversion, >= 0: e->ing_rates index, -2: nothing to write
+    int live = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        if (lens[c] == 0) continue;
+        ++live;
+        if (plans[c].T == 0) { group[c] = -1; continue; }
+        if (int rc = ingest_rate(e, plans[c], group[c])) return rc;
+    }
+    if (!live) return Q2A_OK;
+    if (live > 65535) { set_err("ingest: more than 65535 clips in one call"); return Q2A_ERR_ARG; }
+    if (live > e->ing_cap) {
+        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the records
+        if (e->ing_meta) (void) hipFree(e->ing_meta);
+        if (e->ing_meta_host) (void) hipHostFree(e->ing_meta_host);
+        e->ing_meta = nullptr; e->ing_meta_host = nullptr; e->ing_cap = 0;
+        const int cap = (live + 63) / 64 * 64;
+        HIP_TRY(hipMalloc((void **) &e->ing_meta, (size_t) cap * sizeof(q2a_ingest_clip)));
+        HIP_TRY(hipHostMalloc((void **) &e->ing_meta_host, (size_t) cap * sizeof(q2a_ingest_clip), hipHostMallocDefault));
+        e->ing_cap = cap;
+    }
+    if (!e->ing_evt) HIP_TRY(hipEventCreateWithFlags(&e->ing_evt, hipEventDisableTiming));
+    HIP_TRY(hipEventSynchronize(e->ing_evt));   // the previous upload has left the pinned records
+    struct run { int group, first, count; int64_t max_n; };
+    std::vector<run> runs;
+    int at = 0;
+    for (int g = -1; g < (int) e->ing_rates.size(); ++g) {
+        run r{g, at, 0, 0};
+        for (int c = 0; c < n_clips; ++c) {
+            if (group[c] != g) continue;
+            e->ing_meta_host[at++] = q2a_ingest_clip{src[c].data, dst + (int64_t) c * stride, src[c].n_frames, lens[c], src[c].format, src[c].channels};
+            r.max_n = std::max<int64_t>(r.max_n, lens[c]);
+            ++r.count;
+        }
+        if (r.count) runs.push_back(r);
+    }
+    HIP_TRY(hipMemcpyAsync(e->ing_meta, e->ing_meta_host, (size_t) at * sizeof(q2a_ingest_clip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->ing_evt, s));
+    for (const run & r : runs) {
+        if (r.group < 0) {
+            PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_ingest_convert(e->ing_meta + r.first, r.count, r.max_n, s));
+        } else {
+            const auto & ir = e->ing_rates[r.group];
+            PLAUNCH(e, s, Q2A_PROF_MEL, q2a_launch_ingest(ir.g, ir.bank, e->ing_meta + r.first, r.count, r.max_n, s));
+        }
+    }
+    return Q2A_OK;
+}
+
+int q2a_ingest_device(q2a_engine * e, const q2a_pcm_src * src, int n_clips, float * pcm_dev, int64_t pcm_stride,
+                      int32_t * n_samples_out, void * stream) {
+    std::vector<q2a_rs_plan> plans;
+    std::vector<int32_t> lens;
+    if (int rc = ingest_check(e, src, n_clips, pcm_dev, pcm_stride < 0 ? 0 : pcm_stride, n_samples_out, plans, lens)) return rc;
+    if (int rc = ingest_run(e, src, n_clips, plans, lens, pcm_dev, pcm_stride, call_stream(stream))) return rc;
+    for (int c = 0; c < n_clips; ++c) n_samples_out[c] = lens[c];
+    return Q2A_OK;
+}
+
+int q2a_ingest_host(q2a_engine * e, const q2a_pcm_src * src, int n_clips, float * const * pcm_out, int32_t * n_samples_out) {
+    std::vector<q2a_rs_plan> plans;
+    std::vector<int32_t> lens;
+    if (int rc = ingest_check(e, src, n_clips, pcm_out, -1, n_samples_out, plans, lens)) return rc;
+    for (int c = 0; c < n_clips; ++c)
+        if (lens[c] > 0 && !pcm_out[c]) { set_err("ingest: clip %d: NULL output", c); return Q2A_ERR_ARG; }
+    HIP_TRY(hipSetDevice(e->device));
+    auto frame_bytes = [&](int c) { return (size_t) (src[c].format == Q2A_PCM_S16 ? 2 : 4) * src[c].channels; };
+    // chunks of up to 64 clips and about 256 MB of source (one clip at least) through staging set 0 (in) and 1 (out)
+    for (int c0 = 0; c0 < n_clips;) {
+        int c1 = c0;
+        size_t in_bytes = 0;
+        int64_t stride = 4;
+        std::vector<size_t> at;
+        while (c1 < n_clips && c1 - c0 < 64 && (c1 == c0 || in_bytes < ((size_t) 256 << 20))) {
+            at.push_back(in_bytes);
+            in_bytes += ((size_t) src[c1].n_frames * frame_bytes(c1) + 15) & ~(size_t) 15;
+            stride = std::max<int64_t>(stride, (lens[c1] + 3) & ~3);
+            ++c1;
+        }
+        const int n = c1 - c0;
+        const size_t words = std::max(in_bytes / 4 + 4, (size_t) n * stride);
+        if (int rc = ensure_host_bufs(e, 1, (int64_t) words)) return rc;
+        q2a_engine::host_buf & in = e->hb[0], & out = e->hb[1];
+        std::vector<q2a_pcm_src> dsrc(src + c0, src + c1);
+        for (int c = 0; c < n; ++c) {
+            const size_t bytes = (size_t) src[c0 + c].n_frames * frame_bytes(c0 + c);
+            if (bytes) memcpy((uint8_t *) in.pin_in + at[c], src[c0 + c].data, bytes);
+            dsrc[c].data = bytes ? (const uint8_t *) in.d_in + at[c] : nullptr;
+        }
+        if (in_bytes) HIP_TRY(hipMemcpyAsync(in.d_in, in.pin_in, in_bytes, hipMemcpyHostToDevice, e->stream));
+        const std::vector<q2a_rs_plan> pl(plans.begin() + c0, plans.begin() + c1);
+        const std::vector<int32_t> ln(lens.begin() + c0, lens.begin() + c1);
+        if (int rc = ingest_run(e, dsrc.data(), n, pl, ln, out.d_in, stride, e->stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(out.pin_in, out.d_in, (size_t) n * stride * 4, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (int c = 0; c < n; ++c) {
+            if (ln[c]) memcpy(pcm_out[c0 + c], out.pin_in + (size_t) c * stride, (size_t) ln[c] * 4);
+            n_samples_out[c0 + c] = ln[c];
+        }
+        c0 = c1;
+    }
     return Q2A_OK;
 }
 

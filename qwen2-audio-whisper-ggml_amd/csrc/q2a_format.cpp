@@ -3,6 +3,7 @@
 // reference's shipped Debug build forms no FMAs), so that quantized bytes are identical.
 #include "q2a_format.h"
 #include "q2a_encoder.h"
+#include "q2a_resample.h"
 
 #include <algorithm>
 #include <cmath>
@@ -164,6 +165,15 @@ extern "C" int64_t q2a_packed_out_rows(const int32_t * key_len, int n_clips, int
     if (rows > INT32_MAX) return Q2A_ERR_ARG;
     out_start[n_clips] = (int32_t) rows;
     return rows;
+}
+
+// the 16 kHz length of a native-rate clip (include/q2a_encoder.h, q2a_ingest_*); here for the same reason
+extern "C" int64_t q2a_resampled_length(int64_t n_frames, int rate) {
+    q2a_rs_plan p;
+    if (n_frames < 0) return Q2A_ERR_ARG;
+    if (!q2a_rs_plan_of(rate, p)) return Q2A_ERR_UNSUPPORTED;
+    const int64_t n = q2a_rs_out_len(n_frames, rate);
+    return n < 0 ? (int64_t) Q2A_ERR_ARG : n;
 }
 
 // the destination rows of the audio-feature _to calls (include/q2a_encoder.h); here for the same reason

@@ -406,3 +406,34 @@ struct q2a_embed_gather_q_args {
     int32_t * report;
 };
 hipError_t q2a_launch_embed_gather_q(const q2a_embed_gather_q_args & a, hipStream_t s);
+
+// Native-rate PCM ingestion (q2a_ingest.hip; include/q2a_encoder.h q2a_ingest_*).
+// One clip of a launch, in device memory (uploaded per call). dst receives samples 0 .. n_out-1 and nothing else.
+struct q2a_ingest_clip {
+    const void * src;            // interleaved frames, aligned to the sample width
+    float * dst;
+    int64_t n_in;
+    int32_t n_out;
+    int16_t format, channels;    // Q2A_PCM_*, 1 or 2
+};
+// The workgroup geometry of one rate (L, M, H, T as q2a_rs_plan): a workgroup owns P output residues r0 .. r0+P-1 (mod L)
+// of Q consecutive periods of one clip. cl [Tp][P] is their coefficient rows, each shifted by its window's offset
+// against the first residue of its register group so that one input index serves the group; xl [M][Rw] the input span
+// in polyphase order (frame k_rel at (k_rel % M) * Rw + k_rel / M, Rw odd), yl [Q][P+1] the output tile.
+struct q2a_ingest_geom {
+    int L, M, H, T;
+    int P, logP;                 // residues per workgroup, a power of two (>= 4 where L >= 4, else L)
+    int wide;                    // 1: L < 4, a lane owns 4 periods of one residue; 0: one period of 4 residues
+    int Q;                       // periods per workgroup (the run)
+    int Tp;                      // taps walked: T + the largest shift inside a register group
+    int span, Rw;                // input frames staged per workgroup, and the polyphase row length
+    int n_groups;                // ceil(L / P)
+    int lds_bytes;
+};
+// false: no geometry fits the LDS (no supported rate)
+bool q2a_ingest_geom_of(int L, int M, int H, int T, q2a_ingest_geom & g);
+// The resampling launch of the n_clips clips (one rate) at clips_dev; max_n_out: the largest n_out among them.
+hipError_t q2a_launch_ingest(const q2a_ingest_geom & g, const float * bank, const q2a_ingest_clip * clips_dev, int n_clips,
+                             int64_t max_n_out, hipStream_t s);
+// The 16 kHz clips: conversion and downmix only.
+hipError_t q2a_launch_ingest_convert(const q2a_ingest_clip * clips_dev, int n_clips, int64_t max_n_out, hipStream_t s);

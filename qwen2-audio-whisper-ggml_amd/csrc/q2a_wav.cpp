@@ -98,4 +98,56 @@ extern "C" int q2a_read_wav(const char * path, float ** pcm, int64_t * n_samples
     return 0;
 }
 
+// 16-bit PCM of any rate, as the file holds it (interleaved frames): the input of q2a_ingest_host. The chunk walk is
+// q2a_read_wav's, without its 16 kHz rule and without a conversion.
+extern "C" int q2a_read_wav_native(const char * path, int16_t ** frames, int64_t * n_frames, int * channels, int * rate) {
+    if (!path || !frames || !n_frames || !channels || !rate) return -1;
+    *frames = nullptr;
+    *n_frames = 0;
+    *channels = *rate = 0;
+    std::vector<uint8_t> b;
+    if (!slurp(path, b) || b.size() < 12 || memcmp(b.data(), "RIFF", 4) != 0 || memcmp(b.data() + 8, "WAVE", 4) != 0) {
+        fprintf(stderr, "q2a_read_wav_native: '%s' is not a RIFF/WAVE file\n", path);
+        return -1;
+    }
+    int ch = 0, hz = 0, bits = 0, fmt = -1;
+    const uint8_t * data = nullptr;
+    size_t data_len = 0;
+    size_t pos = 12;
+    while (pos + 8 <= b.size()) {
+        const uint32_t len = rd32(b.data() + pos + 4);
+        const uint8_t * c = b.data() + pos + 8;
+        const size_t avail = b.size() - (pos + 8);
+        if (memcmp(b.data() + pos, "fmt ", 4) == 0 && len >= 16 && avail >= 16) {
+            fmt = rd16(c);
+            ch = rd16(c + 2);
+            hz = (int) rd32(c + 4);
+            bits = rd16(c + 14);
+            if (fmt == 0xFFFE && len >= 40 && avail >= 40) fmt = rd16(c + 24);   // extensible: sub-format GUID
+        } else if (memcmp(b.data() + pos, "data", 4) == 0) {
+            data = c;
+            data_len = len <= avail ? len : avail;   // a truncated or streamed file: take what is there
+            break;
+        }
+        pos += 8 + (size_t) len + (len & 1);
+    }
+    if (fmt < 0 || !data) {
+        fprintf(stderr, "q2a_read_wav_native: '%s' has no fmt/data chunk\n", path);
+        return -1;
+    }
+    if (fmt != 1 || bits != 16 || (ch != 1 && ch != 2) || hz <= 0) {
+        fprintf(stderr, "q2a_read_wav_native: WAV file '%s' must be 16-bit PCM, mono or stereo\n", path);
+        return -2;
+    }
+    const int64_t n = (int64_t) (data_len / (2 * (size_t) ch));   // whole frames only
+    int16_t * out = (int16_t *) malloc((size_t) (n > 0 ? n : 1) * ch * sizeof(int16_t));
+    if (!out) return -1;
+    memcpy(out, data, (size_t) n * ch * sizeof(int16_t));   // little-endian host
+    *frames = out;
+    *n_frames = n;
+    *channels = ch;
+    *rate = hz;
+    return 0;
+}
+
 extern "C" void q2a_wav_free(void * p) { free(p); }

@@ -39,6 +39,7 @@ EXPORTS = (
     "q2a_dequantize_row", "q2a_projector_apply_ids_q", "q2a_inputs_embeds_device_q", "q2a_inputs_embeds_device_mel_q",
     "q2a_test_embed_gather_q",
     "q2a_projector_open_ex", "q2a_projector_get_act",
+    "q2a_resampled_length", "q2a_ingest_device", "q2a_ingest_host", "q2a_read_wav_native",
 )
 
 # per-clip status of the encode calls (include/q2a_encoder.h): FAILED = the host call returned an error before this
@@ -102,6 +103,16 @@ def embeds_src(ids_ptr: int, ids_width: int, n_tokens: int, audio_token_id: int,
                table_ld: int = 0, report_ptr: int = 0) -> EmbedsSrc:
     p = lambda a: C.c_void_p(a) if a else None   # noqa: E731
     return EmbedsSrc(p(ids_ptr), ids_width, 0, n_tokens, audio_token_id, p(table_ptr), vocab, table_ld, p(report_ptr))
+
+
+# sample formats of native-rate PCM (include/q2a_encoder.h, q2a_pcm_src)
+PCM_S16, PCM_F32 = 0, 1
+
+
+class PcmSrc(C.Structure):
+    """q2a_pcm_src: one clip of interleaved frames as it arrives (Engine.ingest / ingest_host)."""
+    _fields_ = [("data", C.c_void_p), ("n_frames", C.c_int64), ("rate", C.c_int32), ("format", C.c_int16),
+                ("channels", C.c_int16)]
 
 
 # ggml types of a quantized embedding table (include/q2a_encoder.h, q2a_embed_qtable): (bytes, columns) of a block
@@ -302,6 +313,9 @@ def lib() -> C.CDLL:
         L.q2a_projector_close.argtypes = [vp]
         L.q2a_projector_get_dims.argtypes = [vp, i32p, i32p, i32p]
         L.q2a_projector_apply.argtypes = [vp, vp, C.c_int64, vp, vp]
+        if hasattr(L, "q2a_ingest_device"):   # (optional: earlier diagnostic builds load too)
+            L.q2a_ingest_device.argtypes = [vp, C.POINTER(PcmSrc), C.c_int, vp, C.c_int64, i32p, vp]
+            L.q2a_ingest_host.argtypes = [vp, C.POINTER(PcmSrc), C.c_int, C.POINTER(vp), i32p]
         _lib = L
     return _lib
 
@@ -367,6 +381,50 @@ class Engine:
                                        C.c_void_p(out_ptr), st.ctypes.data_as(C.POINTER(C.c_int32)),
                                        C.c_void_p(stream) if stream else None))
         return st
+
+    @staticmethod
+    def _pcm_srcs(waves, rates, ptr_of):
+        """The q2a_pcm_src array of clips [frames] or [frames][1 | 2], int16 or float32 (torch tensors or numpy arrays,
+        contiguous), and each clip's 16 kHz length."""
+        if len(waves) != len(rates):
+            raise ValueError("one rate per clip")
+        srcs = (PcmSrc * max(1, len(waves)))()
+        for c, (w, rate) in enumerate(zip(waves, rates)):
+            dt = str(w.dtype).replace("torch.", "")
+            if dt not in ("int16", "float32") or w.ndim not in (1, 2):
+                raise ValueError(f"clip {c}: int16 or float32, [frames] or [frames][channels]")
+            srcs[c] = PcmSrc(ptr_of(w) if w.shape[0] else None, w.shape[0], int(rate), PCM_S16 if dt == "int16" else PCM_F32,
+                             1 if w.ndim == 1 else w.shape[1])
+        return srcs
+
+    def ingest(self, waves, rates, stride: int | None = None, out=None, stream: int | None = None):
+        """q2a_ingest_device: native-rate clips on the device (torch CUDA tensors, int16 or float32, [frames] or
+        [frames][2]) resampled to 16 kHz mono f32. Returns (pcm, n_samples): pcm a CUDA float32 tensor [n_clips][stride]
+        (`out`, or a new one of stride = the longest clip), n_samples int32 — what encode_device, audio_features_device
+        and the others take as they are (pcm.data_ptr(), pcm.shape[1], n_samples). Samples behind a clip's length keep
+        what the tensor held (a new one: zeros). Asynchronous on `stream` (None: stream 0)."""
+        import torch
+        waves = [w.contiguous() for w in waves]
+        srcs = self._pcm_srcs(waves, rates, lambda w: w.data_ptr())
+        if out is None:
+            lens = [resampled_length(w.shape[0], int(r)) for w, r in zip(waves, rates)]
+            out = torch.zeros((len(waves), max(stride or 0, max(lens, default=0), 1)), dtype=torch.float32,
+                              device=waves[0].device if waves else "cuda")
+        ns = np.zeros(len(waves), dtype=np.int32)
+        _check(lib().q2a_ingest_device(self.h, srcs, len(waves), C.c_void_p(out.data_ptr()), C.c_int64(out.shape[1] if out.ndim == 2 else 0),
+                                       ns.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(stream) if stream else None))
+        _check(lib().q2a_get_info(self.h, C.byref(self.info)))   # (the banks count in workspace_bytes)
+        return out, ns
+
+    def ingest_host(self, waves, rates):
+        """q2a_ingest_host: the same for numpy arrays on the host; returns the list of 16 kHz float32 clips."""
+        waves = [np.ascontiguousarray(w) for w in waves]
+        srcs = self._pcm_srcs(waves, rates, lambda w: w.ctypes.data)
+        outs = [np.zeros(max(1, resampled_length(w.shape[0], int(r))), dtype=np.float32) for w, r in zip(waves, rates)]
+        ptrs = (C.c_void_p * max(1, len(waves)))(*[o.ctypes.data for o in outs])
+        ns = np.zeros(len(waves), dtype=np.int32)
+        _check(lib().q2a_ingest_host(self.h, srcs, len(waves), ptrs, ns.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [o[:n] for o, n in zip(outs, ns)]
 
     def encode_host(self, clips, offset_ms: int = 0, out: np.ndarray | None = None, offsets_ms=None,
                     raise_on_error: bool = True):
@@ -972,7 +1030,20 @@ def _host() -> C.CDLL:
         _host_lib.q2a_audio_token_rows.restype = C.c_int64
         _host_lib.q2a_audio_token_rows.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64]
         _host_lib.q2a_dequantize_row.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+        _host_lib.q2a_resampled_length.restype = C.c_int64
+        _host_lib.q2a_resampled_length.argtypes = [C.c_int64, C.c_int]
     return _host_lib
+
+
+def resampled_length(n_frames: int, rate: int) -> int:
+    """The 16 kHz length of n_frames frames at `rate` Hz (q2a_resampled_length): ceil(n_frames * 16000 / rate). Raises
+    Q2AError (rc -6) for a rate Engine.ingest does not serve, (rc -4) for a negative length. Host arithmetic."""
+    n = _host().q2a_resampled_length(n_frames, rate)
+    if n < 0:
+        err = Q2AError(f"q2a error {n}: q2a_resampled_length({n_frames}, {rate})")
+        err.rc = int(n)
+        raise err
+    return int(n)
 
 
 def varlen_rows(key_len, n_audio_ctx: int = 1500) -> tuple[int, np.ndarray]:

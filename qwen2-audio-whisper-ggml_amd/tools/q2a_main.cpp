@@ -135,6 +135,30 @@ int main(int argc, char ** argv) {
     for (const auto & f : c.files) {
         float * p = nullptr;
         int64_t n = 0;
+        // a 16-bit WAV at another rate: resampled to 16 kHz mono on the device (q2a_ingest_host)
+        int16_t * frames = nullptr;
+        int channels = 0, rate = 0;
+        if (f != "-" && q2a_read_wav_native(f.c_str(), &frames, &n, &channels, &rate) == 0 && rate != WHISPER_SAMPLE_RATE) {
+            const q2a_pcm_src src{frames, n, rate, Q2A_PCM_S16, (int16_t) channels};
+            const int64_t n_out = q2a_resampled_length(n, rate);
+            std::vector<float> pcm((size_t) (n_out > 0 ? n_out : 0) + 1);
+            float * dst = pcm.data();
+            int32_t got = 0;
+            const int rc = n_out < 0 ? (int) n_out : q2a_ingest_host(q2a_whisper_context_engine(ctx), &src, 1, &dst, &got);
+            q2a_wav_free(frames);
+            if (rc != Q2A_OK) {
+                fprintf(stderr, "error: failed to resample WAV file '%s' (%d Hz): %s\n", f.c_str(), rate, q2a_last_error());
+                pcms.emplace_back();
+                continue;
+            }
+            pcm.resize((size_t) got);
+            if (!c.no_prints)
+                fprintf(stderr, "%s: processing '%s' (%d Hz, %d ch -> %d samples, %.1f sec) on HIP device %d\n", __func__, f.c_str(),
+                        rate, channels, got, (double) got / WHISPER_SAMPLE_RATE, c.device);
+            pcms.push_back(std::move(pcm));
+            continue;
+        }
+        q2a_wav_free(frames);
         if (q2a_read_wav(f.c_str(), &p, &n, nullptr, nullptr) != 0) {
             fprintf(stderr, "error: failed to read WAV file '%s'\n", f.c_str());
             pcms.emplace_back();
